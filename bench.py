@@ -11,6 +11,7 @@ Workloads (config.workload):
      run also measures it and reports it under the key "c2" next to the C3 headline.
 
     python bench.py [--gpus N --steps K --warmup W] [--workload c2] [--global-batch 256] [--collective allreduce]
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR     # also writes the last timed step's outputs
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline`.
 """
@@ -377,7 +378,14 @@ def main():
     ap.add_argument('--rehearse', action='store_true',
                     help='rehearsal of the N>1 code path on a ONE-GPU box: every rank uses cuda:0 and the process group '
                          'is gloo instead of RCCL (which refuses two ranks on one device); not a measurement')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step of the headline workload returned (gradient and losses) to '
+                         'DIR/<name>.npy, so that two builds can be compared output for output')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if args.dump_outputs and args.workload != 'c3':
+        ap.error('--dump-outputs is implemented for the headline workload (c3) only')
     if args.no_extras:
         args.no_cpu_baseline = args.no_c2 = True
 
@@ -487,6 +495,7 @@ def main():
     # Philox key of the step: a device counter bumped on the stream at the end of every step, read by the sampler
     # kernels, so every replay of the captured graph draws fresh surface points (the reference resamples each step)
     seed_buf = torch.full((1,), 1234, dtype=torch.int64, device=dev)
+    last_out = {}
 
     def compute(_i=0):
         # total = ChamferDistanceLoss(sample(params), gt) + SilhouetteLoss(L1) + L1 depth loss  (train.py:243-262),
@@ -497,6 +506,7 @@ def main():
         out = vpn_amd.HotPathLossFunction.apply(params, kinds, cam, gt_points, gt_sil, gt_depth, n, seed_buf, rank * B,
                                                 H, W, sigma, gamma, z_far, 1.0, 1.0, 1.0, 1.0, 1.0, False, True)
         out[2].backward(one)
+        last_out['sil'], last_out['depth'] = out[0], out[1]     # replayed graphs rewrite these same tensors
         return out[2]
 
     def comm():
@@ -551,9 +561,12 @@ def main():
     sync()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        run_step(args.warmup + i)
+        last = run_step(args.warmup + i)
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'grad_params': last[0], 'loss_total': last[1], 'loss_silhouette': last_out['sil'],
+                                         'loss_depth': last_out['depth']})
     if multi:
         tmax = torch.tensor([dt], device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -824,6 +837,15 @@ def main():
         print(json.dumps(out), flush=True)
     if multi:
         dist.destroy_process_group()
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float32, copied to the host before any later step overwrites it.
+    The inputs are seeded and the Philox counter advances once per step, so the same arguments give the same step."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), t.detach().float().cpu().numpy())
 
 
 def emd_extra(B, n, dev, vpn_amd, with_cpu):

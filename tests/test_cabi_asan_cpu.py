@@ -29,6 +29,9 @@ def test_cabi_host_code_under_address_sanitizer():
     lib = b.build(verbose=False, asan=True)
     env = dict(os.environ, VPN_HIP_LIB=lib, LD_PRELOAD=runtime, PYTHONPATH=ROOT,
                ASAN_OPTIONS='detect_leaks=0:abort_on_error=0:exitcode=97')       # the interpreter's own leaks are not ours
+    # host code only, also on a machine with a GPU: the sanitizer runtime intercepts the HSA memory-pool allocations a
+    # visible device would get (and cannot serve them without xnack), so the child sees no device
+    env.update(HIP_VISIBLE_DEVICES='-1', ROCR_VISIBLE_DEVICES='-1', CUDA_VISIBLE_DEVICES='-1')
     out = subprocess.run([sys.executable, '-m', 'pytest', os.path.join(ROOT, 'tests', 'test_cabi_cpu.py'), os.path.join(ROOT, 'tests', 'test_emd.py'),
                           '-x', '-q', '-m', 'not gpu', '-p', 'no:cacheprovider'], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     tail = (out.stdout + out.stderr)[-3000:]

@@ -35,11 +35,19 @@ def oracle_loss(heads_out, batch, kinds, sample_num, seed, sample_base, size):
 
 
 def _run(rank, world):
-    ex = _example()
-    return ex.run(rank, world, torch.device('cpu'), oracle_loss, steps=STEPS, global_batch=GLOBAL_BATCH, K=K, feat=16,
-                  sample_num=SAMPLE_NUM, M=32, size=SIZE, bucket_cap_mb=0.01,      # tiny buckets: several all-reduces per step
-                  make_optimizer=lambda p: torch.optim.SGD(p, lr=0.05))           # SGD: weights are linear in the gradients
-                                                                                  # (Adam turns 1e-7 gradient noise into lr-sized steps)
+    # float64: with float32, BLAS kernels chosen by batch size and CPU (MKL's AVX2 path) give the two ranks' 2-sample
+    # forward passes results that differ from the single process's 4-sample pass by ~1 ulp, and the step's loss
+    # amplifies that to ~1e-5 in the weights: the comparison would measure the CPU's BLAS, not the loop
+    dtype = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float64)
+    try:
+        ex = _example()
+        return ex.run(rank, world, torch.device('cpu'), oracle_loss, steps=STEPS, global_batch=GLOBAL_BATCH, K=K, feat=16,
+                      sample_num=SAMPLE_NUM, M=32, size=SIZE, bucket_cap_mb=0.01,      # tiny buckets: several all-reduces per step
+                      make_optimizer=lambda p: torch.optim.SGD(p, lr=0.05))           # SGD: weights are linear in the gradients
+                                                                                      # (Adam turns 1e-7 gradient noise into lr-sized steps)
+    finally:
+        torch.set_default_dtype(dtype)
 
 
 def _worker(rank, world, port, out):

@@ -52,7 +52,13 @@ def test_g4_chamfer():
         p2 = g['p2'].clone().requires_grad_(True)
         m1, i1, m2, i2 = O.chamfer_nn(p1, p2)
         assert torch.equal(i1.int(), g['idx1']) and torch.equal(i2.int(), g['idx2'])
-        assert torch.equal(m1.detach(), g['min1']) and torch.equal(m2.detach(), g['min2'])
+        # the distances go through torch's CPU sqrt, which is correctly rounded on some CPUs and MKL's 1-ulp sqrt on others,
+        # off in different places per instruction set (see chamfer_nn_ieee): the reference's own distances are defined to
+        # that 1 ulp only, so both the fixture and the oracle are held to 1 ulp of each other and of the IEEE sqrt
+        e1, _, e2, _ = O.chamfer_nn_ieee(g['p1'], g['p2'])
+        for mine, ref, ieee in ((m1.detach(), g['min1'], e1), (m2.detach(), g['min2'], e2)):
+            for a, b in ((mine, ref), (mine, ieee), (ref, ieee)):
+                assert int((a.view(torch.int32) - b.view(torch.int32)).abs().max()) <= 1
         loss = O.chamfer_loss(p1, p2)
         assert rel_err(loss.detach(), g['loss']) <= TOL
         loss.backward()
