@@ -424,8 +424,12 @@ int vpn_trainstep_bwd(const float* params, const int32_t* kinds, uint64_t seed, 
  * G = 4 at B = 64): kernels of ANOTHER stream that need <= 32 KB of LDS and <= 4 waves per SIMD run beside it, which is
  * how TrainStepLossFunction uses it -- launch the auction first, so its workgroups are placed while the CUs are empty (a
  * workgroup that must wait for a slot only makes its partners spin, bounded as above).  Environment, performance only:
- * VPN_EMD_FLAT_WORK (default 4000: own bidders x targets per bid from which a round bids in the balanced form),
- * VPN_EMD_FLAT_MIN (default 16; 0 = team form only), VPN_EMD_TNUM / VPN_EMD_TMAX (team size of the team form). */
+ * VPN_EMD_FORM=team|local|streaming (the kernel; by default team for 128 <= n <= 2048, local for other n <= 4096,
+ * streaming above; an override is ignored where its kernel cannot take n),
+ * VPN_EMD_FLAT_MIN (default 1: own bidders from which a round after the first bids in the balanced form; 0 = team
+ * form only), VPN_EMD_FLAT_WORK (default 0: own bidders x targets per bid of the last balanced round from which it
+ * does), VPN_EMD_TNUM / VPN_EMD_TMAX (default 1024 / 16: lanes a round's own bidders are spread over / largest team),
+ * VPN_EMD_COOP_LAUNCH (above). */
 size_t vpn_emd_workspace(int B, int n);
 int vpn_emd_fwd(const float* xyz1, const float* xyz2, int B, int n, float eps, int iters,
                 float* dist, int32_t* assignment, void* workspace, int max_group, void* stream);

@@ -129,11 +129,11 @@ def test_emd_equals_oracle(emd, B, n, eps, iters):
 
 @pytest.mark.gpu
 def test_emd_both_kernels_agree(emd):
-    """n <= 2048 runs the pruned auction with static bidder ownership and the granule exchange (round 4), VPN_EMD_GRID1=1
-    round 3's pruned kernel (two box scans per bid, atomic max + counter barrier in memory), VPN_EMD_NOGRID=1 the same
-    rounds with the full scan (what 2048 < n <= 4096 uses), VPN_EMD_STREAMING=1 the streaming kernel (state in memory, two
-    barriers) that larger clouds use.  All four must equal the oracle bit for bit -- and therefore each other -- for every
-    group size."""
+    """128 <= n <= 2048 runs the pruned auction with static bidder ownership and the granule exchange (the team kernel),
+    VPN_EMD_FORM=local the replicated-state rounds with the full scan (what n < 128 and 2048 < n <= 4096 use),
+    VPN_EMD_FORM=streaming the streaming kernel (state in memory, two barriers) that larger clouds use; VPN_EMD_FORM=team
+    leaves n = 64 to the local kernel.  Every setting must equal the oracle bit for bit -- and therefore each other -- for
+    every group size."""
     import os
     from vpn_amd.ops import EmdFunction
     x1, x2 = _clouds(5, 700, 21)
@@ -144,15 +144,17 @@ def test_emd_both_kernels_agree(emd):
     cases = [(x1, x2, 0.005, 40), (y1, y2, 0.005, 40), (y2, y1, 0.01, 25), (x1[:, :64], x2[:, :64], 0.005, 30)]
     refs = [O.emd_auction(a, b, e, it) for a, b, e, it in cases]
     try:
-        for streaming, nogrid, grid1 in (('0', '0', '0'), ('0', '0', '1'), ('0', '1', '0'), ('1', '0', '0')):
-            os.environ['VPN_EMD_STREAMING'], os.environ['VPN_EMD_NOGRID'], os.environ['VPN_EMD_GRID1'] = streaming, nogrid, grid1
+        for form in (None, 'team', 'local', 'streaming'):
+            if form is None:
+                os.environ.pop('VPN_EMD_FORM', None)
+            else:
+                os.environ['VPN_EMD_FORM'] = form
             for (a, b, e, it), (rd, ra) in zip(cases, refs):
                 for G in (None, 1, 2, 4, 8, 16):
                     dist, assign = EmdFunction.apply(a.to(DEV), b.to(DEV), e, it, G)
-                    assert torch.equal(assign.cpu(), ra) and torch.equal(dist.cpu(), rd), (streaming, nogrid, grid1, G, a.shape)
+                    assert torch.equal(assign.cpu(), ra) and torch.equal(dist.cpu(), rd), (form, G, a.shape)
     finally:
-        for k in ('VPN_EMD_STREAMING', 'VPN_EMD_NOGRID', 'VPN_EMD_GRID1'):
-            os.environ.pop(k, None)
+        os.environ.pop('VPN_EMD_FORM', None)
 
 
 @pytest.mark.gpu
@@ -244,9 +246,9 @@ def test_emd_group_size_does_not_change_the_result():
 
 @pytest.mark.gpu
 def test_emd_cooperative_launch_is_opt_in_and_agrees(emd):
-    """Round 4: the group's grid is bounded by the occupancy query and launched plainly; VPN_EMD_COOP_LAUNCH=1 adds the
-    runtime's residency check (hipLaunchCooperativeKernel).  Same bits either way, for the team kernel (n <= 2048) and the
-    streaming one."""
+    """The group's grid is bounded by the occupancy query and launched plainly; VPN_EMD_COOP_LAUNCH=1 launches it
+    cooperatively (hipLaunchCooperativeKernel: the runtime's residency check, G = 1 if it refuses).  Same bits either
+    way, for the team kernel (n <= 2048) and the streaming one (n > 4096)."""
     import os
     from vpn_amd.ops import EmdFunction
     cases = [_clouds(3, 700, 41) + (0.005, 30), _clouds(1, 4500, 42) + (0.005, 8)]

@@ -8,15 +8,20 @@
 //   the winner takes the target, evicts its previous owner and raises the price (Assign :196-215);
 //   the last iteration assigns every remaining point to its bid;  dist = squared distance to the assigned target.
 //
-// MI355X design: ONE persistent workgroup (1024 lanes = 16 waves) per sample runs all iterations in a single
-// launch (the reference needs 7 x iters launches).  Targets and prices stream through LDS tiles (SoA, conflict
-// free); each wave takes one bidding point at a time, its 64 lanes scan the targets and a shuffle reduce yields
-// (best, lowest best index, second best).  All tie rules are deterministic (lowest index), unlike the reference's
-// last-writer-wins races (GetMax :189-191, `last` Assign), so the result is reproducible and equal to the CPU
-// oracle (oracle/vpn_oracle.py::emd_auction) bit for bit.  Parity with the CUDA extension itself is unpinned: it
+// MI355X design: G persistent workgroups (1024 lanes = 16 waves each; G = 1..16, bounded by the occupancy query) per
+// sample run all iterations in a single launch (the reference needs 7 x iters launches).  Three kernels, by n:
+//   emd_auction_team_kernel   128 <= n <= 2048 (the training call): replicated state in LDS, pruned Bid scan over a
+//                             cell grid, bids exchanged between the workgroups by tagged granules;
+//   emd_auction_local_kernel  n <= 4096 otherwise: replicated state in LDS, full Bid scan, one group barrier per round;
+//   emd_auction_kernel        larger clouds: state in memory, targets and prices stream through LDS tiles.
+// vpn_emd_fwd picks one (VPN_EMD_FORM=team|local|streaming overrides where that kernel takes n).  All tie rules are
+// deterministic (lowest index), unlike the reference's last-writer-wins races (GetMax :189-191, `last` Assign), so the
+// result is reproducible and equal to the CPU oracle (oracle/vpn_oracle.py::emd_auction) bit for bit, whichever
+// kernel and group size run it.  Parity with the CUDA extension itself is unpinned: it
 // cannot be built here (no nvcc) and ships no stored answers (its only check is test_emd, emd_module.py:81-95).
 #include "vpn_common.h"
 #include <stdlib.h>
+#include <string.h>
 
 #pragma clang fp contract(off)
 
@@ -66,9 +71,9 @@ __device__ inline void emd_st(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_REL
 // (emd_st / emd_ld); every wave waits for its own stores and atomics to be acknowledged (vmcnt counts stores on gfx9)
 // BEFORE the workgroup barrier; only then one lane adds to the group's counter and polls it with sc1 loads; the other
 // waves load shared state only after the second workgroup barrier.
-// Co-residency of the G workgroups is required while they spin: the host launches this kernel COOPERATIVELY when
-// G > 1 (the runtime rejects a grid that cannot be resident) and falls back to G = 1 otherwise.  As a last resort
-// the spin is bounded: after ~1 s (other work holding the CUs, a partitioned device) the workgroup gives up, flags
+// Co-residency of the G workgroups is required while they spin: the host bounds G by the occupancy query so that the
+// whole grid of its plain launch is resident (VPN_EMD_COOP_LAUNCH=1: a cooperative launch, the runtime rejects a grid
+// that cannot be resident and the host falls back to G = 1).  As a last resort the spin is bounded: after ~1 s (other work holding the CUs, a partitioned device) the workgroup gives up, flags
 // the sample and the kernel writes NaN distances for it instead of hanging the GPU.
 constexpr unsigned EMD_SPIN_LIMIT = 1u << 24;          // x s_sleep(1) = 64 cycles each: ~0.5 s at 2.1 GHz
 
@@ -393,297 +398,10 @@ __global__ __launch_bounds__(EMD_THREADS) void emd_auction_local_kernel(const fl
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// n <= EMD_GRID_MAX (the training call: n = SAMPLE_NUM * VP_NUM = 2048, train.py:193): the replicated-state rounds of
-// emd_auction_local_kernel with a PRUNED Bid scan.  At B = 64 the auction is bound by the arithmetic of the scan
-// (10 011 bidder scans x 2048 targets x 23 instructions per sample), and almost all of it is spent on targets that
-// cannot matter: a bidder's value for target j is v_j = (3 - |x_i - y_j|) - price_j with price_j >= 0, so a target
-// farther than R = 3 - S from the bidder (S = any lower bound of its final second-best value) is STRICTLY below the
-// runner-up: it changes neither best, nor second best, nor a tie.  The targets do not move during an auction, so
-// they are sorted once into a uniform 8 x 8 x 8 grid over their bounding box (counting sort in LDS; x-fastest cell
-// order makes every (y, z) row of cells one contiguous run of sorted targets).  A bidder's wave
-//   A. scans the 3 x 3 x 3 cells around the bidder (flattened into a per-wave list of target positions, so all 64 lanes
-//      work even when a row holds a dozen targets) and merges: (best, second best, index);
-//   B. takes S = that second best, R = 3 - S (+ margin), and if the cells covering [x - R, x + R]^3 go beyond block A,
-//      scans that larger box instead (its result replaces A's).  Fewer than two targets in A: the whole grid.
-// The cell of a coordinate is a monotone function of it and the box bounds go through the same function, so a target
-// outside the box differs from the bidder by more than R along some axis: exact, whatever the rounding.
-// Ties are resolved on ORIGINAL indices (the order inside a cell is whatever the counting sort's atomics gave, and
-// differs between the workgroups of a sample; nothing depends on it).  Bit-equal to the oracle like the other two.
-constexpr int EMD_GRID_MAX = 2048;
-constexpr int EG = 8, ENC = EG * EG * EG;
-constexpr int ELIST = 448;              // target positions of a box one wave flattens at a time
-
-struct EmdGrid { float mn[3], sc[3]; };
-__device__ inline int emd_cell1(float x, float mn, float sc) {
-    const int c = (int)((x - mn) * sc);                          // monotone in x (truncation toward zero included)
-    return min(max(c, 0), EG - 1);
-}
-
-// one target (sorted position kk) into the lane's running result; r.idx is a SORTED position here
-__device__ inline void emd_eval(Bid3& r, int kk, float x1, float y1, float z1, const float* tx, const float* ty, const float* tz,
-                                const float* tp, const int* orig) {
-    const float dx = tx[kk] - x1, dy = ty[kk] - y1, dz = tz[kk] - z1;                                  // :139-141
-    const float d = (3.0f - emd_sqrt(((dx * dx) + (dy * dy)) + (dz * dz))) - tp[kk];                    // :143
-    bool take = d > r.best;                                                                         // :144-151
-    if (__builtin_amdgcn_ballot_w64(d == r.best && r.idx >= 0))        // equal values: the lower ORIGINAL index wins (rare)
-        take = take || (d == r.best && r.idx >= 0 && orig[kk] < orig[r.idx]);
-    r.idx = take ? kk : r.idx;
-    r.better = __builtin_amdgcn_fmed3f(r.best, d, r.better);
-    r.best = fmaxf(r.best, d);
-}
-
-// wave64 reductions on the VALU (DPP row shifts + row broadcasts, result wave-uniform): a butterfly of ds_bpermute
-// shuffles costs ~70 cycles per step and value, and a bidder's scan is a chain of latencies
-#define EMD_DPPI(v, ctrl, rmask) __builtin_amdgcn_update_dpp((int)(v), (int)(v), ctrl, rmask, 0xf, false)
-__device__ inline float emd_wave_max(float v) {
-#define EMD_STEP(ctrl, rmask) v = fmaxf(v, __int_as_float(EMD_DPPI(__float_as_int(v), ctrl, rmask)))
-    EMD_STEP(0x111, 0xf); EMD_STEP(0x112, 0xf); EMD_STEP(0x114, 0xf); EMD_STEP(0x118, 0xf); EMD_STEP(0x142, 0xa); EMD_STEP(0x143, 0xc);
-#undef EMD_STEP
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-__device__ inline int emd_wave_min_i(int v) {
-#define EMD_STEP(ctrl, rmask) v = min(v, EMD_DPPI(v, ctrl, rmask))
-    EMD_STEP(0x111, 0xf); EMD_STEP(0x112, 0xf); EMD_STEP(0x114, 0xf); EMD_STEP(0x118, 0xf); EMD_STEP(0x142, 0xa); EMD_STEP(0x143, 0xc);
-#undef EMD_STEP
-    return __builtin_amdgcn_readlane(v, 63);
-}
-// the 64 lanes' results over disjoint target sets (ORIGINAL indices) -> the result over their union, in every lane:
-// largest value, lowest index among the lanes that hold it, second largest counting duplicates (= what folding the
-// lanes with emd_merge gives: the winner's own runner-up competes with every other lane's best)
-__device__ inline Bid3 emd_wave_merge(const Bid3& r) {
-    Bid3 o;
-    o.best = emd_wave_max(r.best);
-    o.idx = emd_wave_min_i((r.best == o.best && r.idx >= 0) ? r.idx : 0x7fffffff);
-    o.better = emd_wave_max((r.idx == o.idx && r.idx >= 0) ? r.better : r.best);
-    if (o.idx == 0x7fffffff) o.idx = -1;
-    return o;
-}
-
-// all targets of the cells [c0, c1] (per axis, inclusive) -> the merged result of the wave, with an ORIGINAL index
-__device__ inline Bid3 emd_scan_box(const int c0[3], const int c1[3], float x1, float y1, float z1, const float* tx, const float* ty,
-                                    const float* tz, const float* tp, const int* orig, const int* cell_start, int* wlist) {
-    const int lane = threadIdx.x & 63;
-    const int ny = c1[1] - c0[1] + 1, nz = c1[2] - c0[2] + 1, nrows = ny * nz;      // <= 64
-    int s0 = 0, len = 0;
-    if (lane < nrows) {
-        const int cy = c0[1] + lane % ny, cz = c0[2] + lane / ny, base = (cz * EG + cy) * EG;
-        s0 = cell_start[base + c0[0]];
-        len = cell_start[base + c1[0] + 1] - s0;
-    }
-    int off = len;                                               // inclusive prefix sum over the rows
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(off, o, 64); if (lane >= o) off += t; }
-    const int T = __shfl(off, 63, 64);
-    Bid3 r{-1e9f, -1e9f, -1};                                    // :116
-    // the rows' targets as ONE flat list, ELIST positions at a time: a lane writes the part of its row that falls into
-    // the window, then all 64 lanes evaluate the window (a row holds a dozen targets: row by row, 50 lanes would idle)
-    const int first = off - len;                                 // this lane's row covers flat positions [first, off)
-    for (int w0 = 0; w0 < T; w0 += ELIST) {
-        const int qlo = max(first, w0), qhi = min(off, w0 + ELIST);
-        for (int q = qlo; q < qhi; ++q) wlist[q - w0] = s0 + (q - first);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        const int cw = min(ELIST, T - w0);
-        for (int k = lane; k < cw; k += 64) emd_eval(r, wlist[k], x1, y1, z1, tx, ty, tz, tp, orig);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();                         // the list is rewritten by the next window / box
-    }
-    r.idx = r.idx >= 0 ? orig[r.idx] : -1;
-    return emd_wave_merge(r);
-}
-
-__global__ __launch_bounds__(EMD_THREADS) void emd_auction_grid_kernel(const float* __restrict__ xyz1,
-                                                                       const float* __restrict__ xyz2, int B, int n,
-                                                                       int npad, int G, float eps, int iters,
-                                                                       float* __restrict__ dist, int32_t* assignment,
-                                                                       float* wsf, unsigned* counters) {
-    extern __shared__ __attribute__((aligned(16))) float emd_lds[];      // 7 planes of npad floats + 5 arrays of npad ints
-    float* tx = emd_lds; float* ty = tx + npad; float* tz = ty + npad; float* tp = tz + npad;       // SORTED by cell
-    int* assign_l = reinterpret_cast<int*>(tp + npad);
-    int* inv_l = assign_l + npad;
-    int* ulist = inv_l + npad;
-    int* orig = ulist + npad;           // sorted position -> target
-    int* pos_of = orig + npad;          // target -> sorted position
-    float* bx = reinterpret_cast<float*>(pos_of + npad);         // the bidders' coordinates: a global load per bidder was
-    float* by = bx + npad; float* bz = by + npad;                // ~1 us at the head of every scan's latency chain
-    __shared__ int cell_start[ENC + 8];
-    __shared__ int cursor[ENC];
-    __shared__ int wlists[EMD_WAVES][ELIST];
-    __shared__ float red[EMD_WAVES][6];
-    __shared__ EmdGrid grid;
-    __shared__ int wcount[EMD_WAVES];
-    __shared__ int gave_up;
-    if (threadIdx.x == 0) gave_up = 0;
-    const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-    const int b = (q / G) * 8 + xcd, g = q % G;
-    if (b >= B) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* p1 = xyz1 + (size_t)b * n * 3;
-    const float* p2 = xyz2 + (size_t)b * n * 3;
-    float* base = wsf + (size_t)b * EMD_WS_PLANES * n;
-    unsigned long long* top = reinterpret_cast<unsigned long long*>(base);
-    int* gbid = reinterpret_cast<int*>(base + 6 * n);
-    float* ginc = base + 8 * n;
-    unsigned* counter = counters + 2 * b;
-    unsigned passed = 0;
-    bool ok = true;
-
-    // ---- the grid: bounding box of the targets, counting sort by cell (once per auction)
-    {
-        float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-        for (int j = tid; j < n; j += EMD_THREADS)
-#pragma unroll
-            for (int a = 0; a < 3; ++a) { const float c = p2[(size_t)j * 3 + a]; lo[a] = fminf(lo[a], c); hi[a] = fmaxf(hi[a], c); }
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) { lo[a] = fminf(lo[a], __shfl_xor(lo[a], o, 64)); hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o, 64)); }
-            if (lane == 0) { red[wave][a] = lo[a]; red[wave][3 + a] = hi[a]; }
-        }
-        for (int c = tid; c < ENC; c += EMD_THREADS) cursor[c] = 0;
-        __syncthreads();
-        if (tid < 3) {
-            float l = red[0][tid], h = red[0][3 + tid];
-            for (int w = 1; w < EMD_WAVES; ++w) { l = fminf(l, red[w][tid]); h = fmaxf(h, red[w][3 + tid]); }
-            grid.mn[tid] = l;
-            grid.sc[tid] = h > l ? (float)EG / (h - l) : 0.0f;      // a flat (or non-finite) extent: one layer of cells
-        }
-        __syncthreads();
-        for (int j = tid; j < n; j += EMD_THREADS) {
-            const int c = (emd_cell1(p2[(size_t)j * 3 + 2], grid.mn[2], grid.sc[2]) * EG + emd_cell1(p2[(size_t)j * 3 + 1], grid.mn[1], grid.sc[1])) * EG
-                          + emd_cell1(p2[(size_t)j * 3], grid.mn[0], grid.sc[0]);
-            atomicAdd(&cursor[c], 1);
-        }
-        __syncthreads();
-        // exclusive scan of the ENC counts: lanes of the first ENC / 64 waves, then across waves
-        int cnt = 0, incl = 0;
-        if (tid < ENC) { cnt = cursor[tid]; incl = cnt; }
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
-        if (lane == 63) wcount[wave] = incl;
-        __syncthreads();
-        if (tid < ENC) {
-            int before = 0;
-            for (int w = 0; w < wave; ++w) before += wcount[w];
-            cell_start[tid] = before + incl - cnt;
-            cursor[tid] = before + incl - cnt;
-        }
-        if (tid == 0) cell_start[ENC] = n;
-        __syncthreads();
-        for (int j = tid; j < n; j += EMD_THREADS) {
-            const float x = p2[(size_t)j * 3], y = p2[(size_t)j * 3 + 1], z = p2[(size_t)j * 3 + 2];
-            const int c = (emd_cell1(z, grid.mn[2], grid.sc[2]) * EG + emd_cell1(y, grid.mn[1], grid.sc[1])) * EG + emd_cell1(x, grid.mn[0], grid.sc[0]);
-            const int pos = atomicAdd(&cursor[c], 1);
-            tx[pos] = x; ty[pos] = y; tz[pos] = z; tp[pos] = 0.0f; orig[pos] = j; pos_of[j] = pos;
-        }
-        for (int j = tid; j < npad; j += EMD_THREADS) {
-            if (j >= n) { tx[j] = 0.0f; ty[j] = 0.0f; tz[j] = 0.0f; tp[j] = __builtin_inff(); orig[j] = 0x7fffffff; }
-            assign_l[j] = -1; inv_l[j] = -1;
-            const int jc = min(j, n - 1);
-            bx[j] = p1[(size_t)jc * 3]; by[j] = p1[(size_t)jc * 3 + 1]; bz[j] = p1[(size_t)jc * 3 + 2];
-        }
-    }
-    for (int j = g * EMD_THREADS + tid; j < 3 * n; j += G * EMD_THREADS) emd_st(top + j, 0ull);
-    ok = emd_group_sync(counter, passed, G, &gave_up);
-
-    const int per = (n + EMD_THREADS - 1) / EMD_THREADS, j0 = min(n, tid * per), j1 = min(n, j0 + per);
-    int* wlist = wlists[wave];
-    for (int it = 0; ok && it < iters; ++it) {
-        const bool last = it == iters - 1;
-        unsigned long long* top_w = top + (size_t)(it % 3) * n;
-        unsigned long long* top_z = top + (size_t)((it + 1) % 3) * n;
-        int* bid_w = gbid + (size_t)(it & 1) * n;
-        float* inc_w = ginc + (size_t)(it & 1) * n;
-        int cnt = 0;
-        for (int j = j0; j < j1; ++j) cnt += assign_l[j] == -1;
-        int scan = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int t2 = __shfl_up(scan, o, 64); if (lane >= o) scan += t2; }
-        if (lane == 63) wcount[wave] = scan;
-        __syncthreads();
-        int before = 0, U = 0;
-#pragma unroll
-        for (int w = 0; w < EMD_WAVES; ++w) { const int c = wcount[w]; before += w < wave ? c : 0; U += c; }
-        if (U == 0) break;
-        int pos = before + scan - cnt;
-        for (int j = j0; j < j1; ++j) if (assign_l[j] == -1) ulist[pos++] = j;
-        if (it >= 1) for (int j = g * EMD_THREADS + tid; j < n; j += G * EMD_THREADS) emd_st(top_z + j, 0ull);
-        __syncthreads();
-
-        // ---- Bid (:95-179), pruned
-        for (int u = g * EMD_WAVES + wave; u < U; u += G * EMD_WAVES) {
-            const int i = ulist[u];
-            const float x1 = bx[i], y1 = by[i], z1 = bz[i];
-            const float xyz[3] = {x1, y1, z1};
-            int a0[3], a1[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const int c = emd_cell1(xyz[a], grid.mn[a], grid.sc[a]);
-                a0[a] = max(c - 1, 0); a1[a] = min(c + 1, EG - 1);
-            }
-            Bid3 r = emd_scan_box(a0, a1, x1, y1, z1, tx, ty, tz, tp, orig, cell_start, wlist);
-            // every target outside [x - R, x + R]^3 is strictly below the runner-up found so far
-            const bool two = r.idx >= 0 && r.better > -1e8f;
-            const float R = two ? (3.0f - r.better) + 1.0e-5f : __builtin_inff();
-            int b0[3], b1[3];
-            bool inside = true;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                b0[a] = emd_cell1(xyz[a] - R, grid.mn[a], grid.sc[a]);
-                b1[a] = emd_cell1(xyz[a] + R, grid.mn[a], grid.sc[a]);
-                if (!(R < 1e30f)) { b0[a] = 0; b1[a] = EG - 1; }                // also a NaN radius: everything
-                inside = inside && b0[a] >= a0[a] && b1[a] <= a1[a];
-            }
-            if (!inside) {
-#pragma unroll
-                for (int a = 0; a < 3; ++a) { b0[a] = min(b0[a], a0[a]); b1[a] = max(b1[a], a1[a]); }
-                r = emd_scan_box(b0, b1, x1, y1, z1, tx, ty, tz, tp, orig, cell_start, wlist);
-            }
-            if (lane == 0) {
-                const float v = (r.best - r.better) + eps;                                  // :175-176
-                emd_st(bid_w + i, r.idx); emd_st(inc_w + i, v);
-                const unsigned long long key =
-                    ((unsigned long long)(unsigned)__float_as_int(v) << 32) | (unsigned)(0x7fffffff - i);
-                __hip_atomic_fetch_max(top_w + min(max(r.idx, 0), n - 1), key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        if (!(ok = emd_group_sync(counter, passed, G, &gave_up))) break;
-
-        // ---- Assign (:196-215) of ALL bidders on this workgroup's copy
-        for (int u = tid; u < U; u += EMD_THREADS) {
-            const int i = ulist[u];
-            const int t = min(max(emd_ld(bid_w + i), 0), n - 1);
-            if (last) { assign_l[i] = t; continue; }
-            const unsigned long long key = emd_ld(top_w + t);
-            const float v = emd_ld(inc_w + i);
-            if (0x7fffffff - (int)(unsigned)key != i) continue;
-            const int prev = inv_l[t];
-            if (prev != -1) assign_l[prev] = -1;
-            inv_l[t] = i;
-            assign_l[i] = t;
-            const int ps = pos_of[t];
-            tp[ps] = tp[ps] + v;                                // :211
-        }
-        __syncthreads();
-    }
-
-    if (!ok) {
-        for (int j = g * EMD_THREADS + tid; j < n; j += G * EMD_THREADS) { dist[(size_t)b * n + j] = __builtin_nanf(""); assignment[(size_t)b * n + j] = -1; }
-        return;
-    }
-    for (int j = g * EMD_THREADS + tid; j < n; j += G * EMD_THREADS) {        // CalcDist :217-226 + the assignment itself
-        const int t = assign_l[j];
-        assignment[(size_t)b * n + j] = t;
-        if (t < 0 || t >= n) { dist[(size_t)b * n + j] = __builtin_nanf(""); continue; }
-        const int ps = pos_of[t];
-        const float dx = bx[j] - tx[ps], dy = by[j] - ty[ps], dz = bz[j] - tz[ps];
-        dist[(size_t)b * n + j] = ((dx * dx) + (dy * dy)) + (dz * dz);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Round 4: the pruned auction again, rebuilt around two measurements.  (i) A late round of an easy auction (uniform
-// clouds) is ~100 bidders per sample: a chain of latencies -- in emd_auction_grid_kernel ~19 us per round, ~6 of them five
+// 128 <= n <= EMD_TEAM_MAX (the training call: n = SAMPLE_NUM * VP_NUM = 2048, train.py:193): a pruned Bid scan built
+// around two measurements of round 3's pruned kernel (a cell box scan per bid, atomic max + counter barrier in memory;
+// retired).  (i) A late round of an easy auction (uniform
+// clouds) is ~100 bidders per sample: a chain of latencies -- in that kernel ~19 us per round, ~6 of them five
 // dependent L2 round trips of the atomic-max / counter / read-back exchange.  (ii) The auction the training step really
 // runs (points on K small primitives against a cloud that fills the cube, train.py:193 early in training) keeps 500-1500
 // bidders per round and their radius grows to 2-3 cells: there that kernel is bound by VALU issue -- ~1000 wave-instructions
@@ -707,7 +425,8 @@ __global__ __launch_bounds__(EMD_THREADS) void emd_auction_grid_kernel(const flo
 //   * 16-bit state: 32 n + 18 n / G bytes of LDS + the cell table + the balanced form's lists (51.7 KB): ONE workgroup
 //     per CU with up to 128 VGPRs (both forms of the Bid phase inline without scratch), G = 4 at B = 64; the 32 KB of LDS
 //     and the wave slots it leaves are what the training step's other kernels run in beside it.
-// Same arithmetic, same tie rules: bit-equal to the oracle and to the other three kernels for every group size.
+// Same arithmetic, same tie rules: bit-equal to the oracle and to the other two kernels for every group size.
+constexpr int EMD_TEAM_MAX = 2048;     // largest n the team kernel takes (its LDS holds 32 n bytes of replicated state)
 #ifndef EMD_EG
 #define EMD_EG 8
 #endif
@@ -1584,42 +1303,91 @@ __global__ __launch_bounds__(256) void emd_bwd_kernel(const float* __restrict__ 
 
 using namespace vpn;
 
-// Largest group size G (power of two) such that the whole grid is resident: workgroups per CU from the occupancy
-// query of THIS kernel on the CURRENT device (asked every call: nothing is cached across devices) times its CU
-// count.  max_group caps it (1 = no inter-workgroup barrier at all).
-static int emd_group_size_of(const void* kernel, size_t dyn_lds, int B, int n, int max_group) {
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        return 1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, EMD_THREADS, dyn_lds) != hipSuccess || per_cu <= 0)
-        return 1;
-    const long long slots = (long long)cus * per_cu;
-    const int padded = (B + 7) / 8 * 8;
-    const int cap = max_group > 0 && max_group < EMD_MAX_GROUP ? max_group : EMD_MAX_GROUP;
-    int G = 1;
-    while (G * 2 <= cap && (long long)padded * G * 2 <= slots && G * 2 * EMD_WAVES * 4 <= n) G *= 2;
-    return G;
+// The three forward kernels, by the shapes they take: TEAM 128 <= n <= EMD_TEAM_MAX (pruned scan: the training call),
+// LOCAL n <= EMD_TILE (replicated state, full scan), STREAMING any n (state in memory, targets through LDS tiles).
+enum EmdForm { EMD_TEAM, EMD_LOCAL, EMD_STREAMING };
+static const char* const EMD_FORM_NAMES[] = {"team", "local", "streaming"};
+static const char* const EMD_KERNEL_NAMES[] = {"emd_auction_team_kernel", "emd_auction_local_kernel", "emd_auction_kernel"};
+
+static bool emd_form_takes(int form, int n) {
+    return form == EMD_TEAM ? n >= 128 && n <= EMD_TEAM_MAX : form == EMD_LOCAL ? n <= EMD_TILE : true;
 }
 
-static int emd_group_size(int B, int n, int max_group) {
-    return emd_group_size_of(reinterpret_cast<const void*>(emd_auction_kernel), 0, B, n, max_group);
+// The first form that takes n.  VPN_EMD_FORM=team|local|streaming picks a form instead where that form takes n (the
+// tests cross-check the kernels with it); results are the same bits either way.
+static EmdForm emd_form(int n) {
+    if (const char* e = getenv("VPN_EMD_FORM"))
+        for (int f = EMD_TEAM; f <= EMD_STREAMING; ++f)
+            if (strcmp(e, EMD_FORM_NAMES[f]) == 0 && emd_form_takes(f, n)) return (EmdForm)f;
+    return emd_form_takes(EMD_TEAM, n) ? EMD_TEAM : emd_form_takes(EMD_LOCAL, n) ? EMD_LOCAL : EMD_STREAMING;
 }
 
-// VPN_EMD_STREAMING=1: the streaming kernel also for one-tile problems; VPN_EMD_NOGRID=1: the unpruned replicated-state
-// kernel also for n <= 2048 (cross-checks of the three kernels in the tests)
 static bool emd_env_flag(const char* name) {
     const char* e = getenv(name);
     return e && e[0] == '1';
 }
-static bool emd_force_streaming() { return emd_env_flag("VPN_EMD_STREAMING"); }
-// The group size G is bounded by hipOccupancyMaxActiveBlocksPerMultiprocessor x #CU on every call, so the grid of a PLAIN
-// launch is resident as a whole unless something else holds the CUs (then the bounded spin gives up: NaN / -1, a loud
-// failure).  VPN_EMD_COOP_LAUNCH=1 launches cooperatively instead, which adds the runtime's own residency check -- off by
-// default since round 4: in a process that has captured a HIP graph, ONE cooperative launch makes every later dispatch of
-// the process ~50 us slower (profiles/r04_coop_launch_side_effect.txt: the C5 step 1.90 -> 2.55 ms, every kernel of it
-// +45..65 us, eager and replayed), and it costs ~40 us of host time per call.
-static bool emd_coop_launch() { return emd_env_flag("VPN_EMD_COOP_LAUNCH"); }
+
+struct EmdGroup { int G, lg; };            // workgroups per sample and its log2
+
+// Largest group size G (power of two, <= min(max_group, EMD_MAX_GROUP)) with G * 64 <= n, G dividing npad if
+// `divides_npad`, and the whole grid resident: ceil(B / 8) * 8 * G workgroups against the CU count of the current
+// device times the workgroups per CU that the occupancy query gives for THIS kernel with lds_of(G) bytes of dynamic
+// LDS (asked every call: nothing is cached across devices).  max_group = 1: no inter-workgroup barrier at all.
+template <typename LdsOf>
+static EmdGroup emd_group_size(const void* kern, LdsOf lds_of, bool divides_npad, int B, int n, int npad, int max_group) {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+        return {1, 0};
+    const long long padded = (B + 7) / 8 * 8;
+    const int cap = max_group > 0 && max_group < EMD_MAX_GROUP ? max_group : EMD_MAX_GROUP;
+    for (int G = EMD_MAX_GROUP; G > 1; G >>= 1) {
+        if (G > cap || G * EMD_WAVES * 4 > n || (divides_npad && npad % G != 0)) continue;
+        int per_cu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, EMD_THREADS, lds_of(G)) != hipSuccess || per_cu <= 0) continue;
+        if (padded * G <= (long long)cus * per_cu) return {G, __builtin_ctz(G)};
+    }
+    return {1, 0};
+}
+
+static size_t emd_lds_raised[3];          // per form: the dynamic LDS its kernel has been allowed so far
+
+template <typename T> struct emd_exactly { using type = T; };      // keeps `args` out of template argument deduction
+
+// Launch the kernel of `form`: raise its dynamic LDS limit (once per kernel, to the largest size asked so far), choose
+// grp, then launch ceil(B / 8) * 8 * grp.G workgroups with lds_of(grp.G) bytes of LDS.  `args` are the kernel's arguments
+// as variables of exactly its parameter types; grp.G (and grp.lg) are among them, so the cooperative launch's argument
+// list and the fallback see the same group size.
+// G is bounded by the occupancy query on every call, so the grid of a PLAIN launch is resident as a whole unless
+// something else holds the CUs (then the bounded spin gives up: NaN / -1, a loud failure).  VPN_EMD_COOP_LAUNCH=1
+// launches cooperatively when G > 1, which adds the runtime's own residency check (if it refuses the grid: G = 1) --
+// off by default since round 4: in a process that has captured a HIP graph, ONE cooperative launch makes every later
+// dispatch of the process ~50 us slower (profiles/r04_coop_launch_side_effect.txt: the C5 step 1.90 -> 2.55 ms, every
+// kernel of it +45..65 us, eager and replayed), and it costs ~40 us of host time per call.
+template <typename LdsOf, typename... P>
+static int emd_launch(EmdForm form, void (*kern)(P...), LdsOf lds_of, bool divides_npad, int B, int n, int npad,
+                      int max_group, EmdGroup& grp, hipStream_t s, typename emd_exactly<P>::type&... args) {
+    const void* k = reinterpret_cast<const void*>(kern);
+    if (lds_of(1) > emd_lds_raised[form]) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_of(1));
+        if (e != hipSuccess) return (int)e;
+        emd_lds_raised[form] = lds_of(1);
+    }
+    grp = emd_group_size(k, lds_of, divides_npad, B, n, npad, max_group);
+    const int padded = (B + 7) / 8 * 8;
+    if (grp.G > 1 && emd_env_flag("VPN_EMD_COOP_LAUNCH")) {
+        void* argv[] = {(void*)&args...};
+        vpn::prof_begin(EMD_KERNEL_NAMES[form], s);
+        const hipError_t e = hipLaunchCooperativeKernel(k, dim3(padded * grp.G), dim3(EMD_THREADS), argv, (unsigned)lds_of(grp.G), s);
+        vpn::prof_end(s);
+        if (e == hipSuccess) return 0;
+        (void)hipGetLastError();
+        if (e != hipErrorCooperativeLaunchTooLarge && e != hipErrorNotSupported && e != hipErrorInvalidConfiguration) return (int)e;
+        grp = {1, 0};
+    }
+    VPN_LAUNCH_AS(EMD_KERNEL_NAMES[form], kern, dim3(padded * grp.G), dim3(EMD_THREADS), (unsigned)lds_of(grp.G), s, args...);
+    VPN_LAUNCH_CHECK();
+    return 0;
+}
 
 static size_t emd_state_bytes(int B, int n) { return (size_t)B * n * EMD_WS_PLANES * sizeof(float); }
 
@@ -1639,33 +1407,13 @@ extern "C" int vpn_emd_fwd(const float* xyz1, const float* xyz2, int B, int n, f
     unsigned* counters = reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + emd_state_bytes(B, n));
     if (hipMemsetAsync(counters, 0, (size_t)2 * B * sizeof(unsigned), s) != hipSuccess) return (int)hipGetLastError();
     float* wsf = (float*)workspace;
-    if (n <= EMD_GRID_MAX && n >= 128 && !emd_force_streaming() && !emd_env_flag("VPN_EMD_NOGRID") && !emd_env_flag("VPN_EMD_GRID1")) {
-        // the training call (n = SAMPLE_NUM * VP_NUM = 2048): pruned scan, static ownership, granule exchange
-        const int npad = (n + 63) / 64 * 64;
-        const void* kern = reinterpret_cast<const void*>(emd_auction_team_kernel);
-        const int flat_lds = npad >= 1024 ? 1 : 0;               // the balanced form's lists (small clouds never need it)
+    EmdGroup grp{1, 0};
+    switch (emd_form(n)) {
+    case EMD_TEAM: {
+        // pruned scan, static ownership, granule exchange
+        int npad = (n + 63) / 64 * 64;
+        int flat_lds = npad >= 1024 ? 1 : 0;                     // the balanced form's lists (small clouds never need it)
         auto lds_of = [&](int G) { return (size_t)npad * 32 + (size_t)(npad / G) * 18 + (flat_lds ? EMD_FLAT_BYTES : 0); };
-        static size_t raised = 0;
-        if (lds_of(1) > raised) {
-            const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_of(1));
-            if (e != hipSuccess) return (int)e;
-            raised = lds_of(1);
-        }
-        // largest G (power of two, <= 16, <= max_group) whose whole grid is resident: workgroups per CU from the
-        // occupancy query of THIS kernel with THAT group size's LDS, times the CU count of the current device
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
-        const int padded = (B + 7) / 8 * 8;
-        const int cap = max_group > 0 && max_group < EMD_MAX_GROUP ? max_group : EMD_MAX_GROUP;
-        int G = 1, lgG = 0;
-        for (int cand = EMD_MAX_GROUP, lg = 4; cand > 1; cand >>= 1, --lg) {
-            if (cand > cap || cand * EMD_WAVES * 4 > n || npad % cand != 0) continue;
-            int per_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, EMD_THREADS, lds_of(cand)) != hipSuccess || per_cu <= 0) continue;
-            if ((long long)padded * cand <= (long long)cus * per_cu) { G = cand; lgG = lg; break; }
-        }
-        const unsigned lds = (unsigned)lds_of(G);
-        const bool coop = G > 1 && emd_coop_launch();
         int tnum = 1024, tmax = 16;                              // lanes the own bidders of a round are spread over; largest team
         if (const char* e = getenv("VPN_EMD_TNUM")) tnum = atoi(e) > 0 ? atoi(e) : tnum;
         if (const char* e = getenv("VPN_EMD_TMAX")) tmax = atoi(e) > 0 ? atoi(e) : tmax;
@@ -1675,75 +1423,24 @@ extern "C" int vpn_emd_fwd(const float* xyz1, const float* xyz2, int B, int n, f
         int flat_min = 1, flat_work = 0;
         if (const char* e = getenv("VPN_EMD_FLAT_MIN")) flat_min = atoi(e);
         if (const char* e = getenv("VPN_EMD_FLAT_WORK")) flat_work = atoi(e);
-        if (coop) {
-            void* args[] = {(void*)&xyz1, (void*)&xyz2, (void*)&B, (void*)&n, (void*)&npad, (void*)&G, (void*)&lgG, (void*)&eps, (void*)&iters,
-                            (void*)&dist, (void*)&assignment, (void*)&wsf, (void*)&counters, (void*)&tnum, (void*)&tmax, (void*)&flat_min, (void*)&flat_lds, (void*)&flat_work};
-            vpn::prof_begin("emd_auction_team_kernel", s);
-            const hipError_t e = hipLaunchCooperativeKernel(kern, dim3(padded * G), dim3(EMD_THREADS), args, lds, s);
-            vpn::prof_end(s);
-            if (e == hipSuccess) return 0;
-            (void)hipGetLastError();
-            if (e != hipErrorCooperativeLaunchTooLarge && e != hipErrorNotSupported && e != hipErrorInvalidConfiguration) return (int)e;
-            G = 1; lgG = 0;
-        }
-        VPN_LAUNCH(emd_auction_team_kernel, dim3(padded * G), dim3(EMD_THREADS), (unsigned)lds_of(G), s, xyz1, xyz2, B, n, npad, G, lgG, eps,
-                   iters, dist, assignment, wsf, counters, tnum, tmax, flat_min, flat_lds, flat_work);
-        VPN_LAUNCH_CHECK();
-        return 0;
+        return emd_launch(EMD_TEAM, emd_auction_team_kernel, lds_of, true, B, n, npad, max_group, grp, s, xyz1, xyz2, B, n,
+                          npad, grp.G, grp.lg, eps, iters, dist, assignment, wsf, counters, tnum, tmax, flat_min, flat_lds,
+                          flat_work);
     }
-    if (n <= EMD_TILE && !emd_force_streaming()) {
-        // one-tile problem (every training call): replicated state, one group barrier per round
+    case EMD_LOCAL: {
+        // one-tile problem: replicated state, one group barrier per round
         int npad = (n + 64 * EMD_UNROLL - 1) / (64 * EMD_UNROLL) * (64 * EMD_UNROLL);
-        const bool grid = n <= EMD_GRID_MAX && n >= 64 && !emd_env_flag("VPN_EMD_NOGRID");     // pruned Bid scan
-        const void* kern = grid ? reinterpret_cast<const void*>(emd_auction_grid_kernel)
-                                : reinterpret_cast<const void*>(emd_auction_local_kernel);
-        const size_t lds = (size_t)npad * (grid ? 12 : 7) * sizeof(float);
-        static size_t raised[2] = {0, 0};              // largest dynamic LDS size each kernel has been allowed so far
-        if (lds > raised[grid]) {
-            const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-            raised[grid] = lds;
-        }
-        int G = emd_group_size_of(kern, lds, B, n, max_group);
-        if (G > 1 && emd_coop_launch()) {
-            void* args[] = {(void*)&xyz1, (void*)&xyz2, (void*)&B, (void*)&n, (void*)&npad, (void*)&G, (void*)&eps, (void*)&iters,
-                            (void*)&dist, (void*)&assignment, (void*)&wsf, (void*)&counters};
-            vpn::prof_begin(grid ? "emd_auction_grid_kernel" : "emd_auction_local_kernel", s);
-            const hipError_t e = hipLaunchCooperativeKernel(kern, dim3((B + 7) / 8 * 8 * G), dim3(EMD_THREADS), args, (unsigned)lds, s);
-            vpn::prof_end(s);
-            if (e == hipSuccess) return 0;
-            (void)hipGetLastError();
-            if (e != hipErrorCooperativeLaunchTooLarge && e != hipErrorNotSupported && e != hipErrorInvalidConfiguration) return (int)e;
-            G = 1;
-        }
-        if (grid)
-            VPN_LAUNCH(emd_auction_grid_kernel, dim3((B + 7) / 8 * 8 * G), dim3(EMD_THREADS), lds, s, xyz1, xyz2, B, n, npad, G, eps,
-                       iters, dist, assignment, wsf, counters);
-        else
-            VPN_LAUNCH(emd_auction_local_kernel, dim3((B + 7) / 8 * 8 * G), dim3(EMD_THREADS), lds, s, xyz1, xyz2, B, n, npad, G, eps,
-                       iters, dist, assignment, wsf, counters);
-        VPN_LAUNCH_CHECK();
-        return 0;
+        auto lds_of = [&](int) { return (size_t)npad * 7 * sizeof(float); };
+        return emd_launch(EMD_LOCAL, emd_auction_local_kernel, lds_of, false, B, n, npad, max_group, grp, s, xyz1, xyz2, B,
+                          n, npad, grp.G, eps, iters, dist, assignment, wsf, counters);
     }
-    int G = emd_group_size(B, n, max_group);
-    if (G > 1 && emd_coop_launch()) {
-        // the G workgroups of a sample synchronise with each other: a COOPERATIVE launch makes the runtime check that
-        // the whole grid can be resident at once; if it says no, fall back to one workgroup per sample
-        void* args[] = {(void*)&xyz1, (void*)&xyz2, (void*)&B, (void*)&n, (void*)&G, (void*)&eps, (void*)&iters,
-                        (void*)&dist, (void*)&assignment, (void*)&wsf, (void*)&counters};
-        vpn::prof_begin("emd_auction_kernel", s);
-        const hipError_t e = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(emd_auction_kernel),
-                                                        dim3((B + 7) / 8 * 8 * G), dim3(EMD_THREADS), args, 0, s);
-        vpn::prof_end(s);
-        if (e == hipSuccess) return 0;
-        (void)hipGetLastError();
-        if (e != hipErrorCooperativeLaunchTooLarge && e != hipErrorNotSupported && e != hipErrorInvalidConfiguration) return (int)e;
-        G = 1;
+    case EMD_STREAMING:
+    default: {
+        auto lds_of = [](int) { return (size_t)0; };
+        return emd_launch(EMD_STREAMING, emd_auction_kernel, lds_of, false, B, n, 0, max_group, grp, s, xyz1, xyz2, B, n,
+                          grp.G, eps, iters, dist, assignment, wsf, counters);
     }
-    VPN_LAUNCH(emd_auction_kernel, dim3((B + 7) / 8 * 8 * G), dim3(EMD_THREADS), 0, s, xyz1, xyz2, B, n, G, eps, iters,
-               dist, assignment, wsf, counters);
-    VPN_LAUNCH_CHECK();
-    return 0;
+    }
 }
 
 extern "C" int vpn_emd_bwd(const float* xyz1, const float* xyz2, const float* grad_dist, const int32_t* assignment,

@@ -420,8 +420,11 @@ class EmdFunction(Function):
 
     @staticmethod
     def forward(ctx, xyz1, xyz2, eps, iters, max_group=None):
-        """max_group: workgroups per sample (None: VPN_EMD_GROUP or automatic; 1: no inter-workgroup barrier -- forced
-        when other streams share the GPU (VPN_CONCURRENT=1), because the group barrier needs the whole grid resident)."""
+        """max_group: cap on the workgroups per sample (None: VPN_EMD_GROUP or automatic; 1: no inter-workgroup barrier --
+        forced when other streams share the GPU (VPN_CONCURRENT=1), because the group barrier needs the whole grid
+        resident).  The library bounds the group by the occupancy query and launches plainly (VPN_EMD_COOP_LAUNCH=1: a
+        cooperative launch, which falls back to one workgroup per sample if the runtime refuses the grid); the kernel
+        follows from n (VPN_EMD_FORM=team|local|streaming overrides it).  The result is the same bits in every case."""
         B, n, _ = xyz1.size()
         assert n == xyz2.size(1)                       # emd_module.py:36-37
         assert B == xyz2.size(0)
