@@ -38,7 +38,7 @@ extern "C" {
  * step in one autograd node).  4 (round 3): raster records are 16 float4 per primitive (vpn_raster_records_size grew), tile_order is a buffer of
  * 48-byte tile entries (vpn_raster_order_size, K <= 64).  3: vpn_raster_total_fwd_fin, vpn_hotpath_chamfer_fwd, the mesh
  * entry points. */
-#define VPN_ABI_VERSION 5
+#define VPN_ABI_VERSION 6
 
 /* primitive kinds (reference: train.py:106-116 cuboids first, then spheres, cones are stubs) */
 #define VPN_SPHERE 0
@@ -414,10 +414,14 @@ int vpn_trainstep_bwd(const float* params, const int32_t* kinds, uint64_t seed, 
  * of 1024 and B is not limited to 512 (emd_module.py:38-39). */
 /* max_group: cap on the number of workgroups that cooperate on one sample (0 = automatic: as many as can be
  * resident together by hipOccupancyMaxActiveBlocksPerMultiprocessor x #CU, power of two <= 16; 1 = one workgroup per
- * sample, nothing shared between workgroups).  The workgroups of a sample wait for each other's bids: the whole grid must
- * be resident, which the occupancy bound guarantees for a plain launch on a GPU that runs nothing else at the time; the
- * wait is bounded (~0.5 s: dist = NaN, assignment = -1 for that sample rather than a hang).  Pass 1 when other streams or
- * processes share the GPU.  VPN_EMD_COOP_LAUNCH=1 in the environment launches cooperatively (the runtime then checks
+ * sample, nothing shared between workgroups).  Co-residency: the workgroups of a sample wait for each other's bids, so
+ * they must all be resident together.  The occupancy bound guarantees that for a plain launch on a GPU that runs nothing
+ * else at the time; when other processes or streams share the GPU (several ranks on one device, a long kernel of another
+ * stream) some may not be.  Their wait is bounded (~0.5 s), the sample is flagged, and every call that ran with G > 1
+ * ends with a second launch at G = 1 on the same stream that recomputes the flagged samples: the result is always the
+ * G = 1 result, with no host synchronisation (the call stays capturable in a HIP graph).  On an idle GPU that launch is one
+ * wave of workgroups that read their flag and leave.  Sharing the GPU therefore costs time (the spin, then the redo),
+ * never correctness; max_group = 1 avoids the cost where sharing is the rule.  VPN_EMD_COOP_LAUNCH=1 in the environment launches cooperatively (the runtime then checks
  * residency itself; the call falls back to 1 if it refuses) -- not the default: a cooperative launch in a process that has
  * captured a HIP graph slows every later dispatch of that process by ~50 us.  Results do not depend on any of this.
  * For 128 <= n <= 2048 the auction is one workgroup per CU (1024 threads, <= 128 VGPRs, 131 KB of LDS at n = 2048,
@@ -433,6 +437,17 @@ int vpn_trainstep_bwd(const float* params, const int32_t* kinds, uint64_t seed, 
 size_t vpn_emd_workspace(int B, int n);
 int vpn_emd_fwd(const float* xyz1, const float* xyz2, int B, int n, float eps, int iters,
                 float* dist, int32_t* assignment, void* workspace, int max_group, void* stream);
+/* vpn_emd_fwd with a test hook (vpn_emd_fwd passes 0): a sample b < 32 with bit b of test_giveup_mask set gives up at its
+ * first group barrier at once when G > 1 (no spin, no wait), as if its workgroups could not all be resident, so that
+ * the recovery above runs deterministically.  The result does not change. */
+int vpn_emd_fwd_ex(const float* xyz1, const float* xyz2, int B, int n, float eps, int iters,
+                   float* dist, int32_t* assignment, void* workspace, int max_group, void* stream,
+                   unsigned test_giveup_mask);
+/* Samples the G = 1 recovery launches have recomputed on the current device since the library was loaded.  Waits for
+ * the device (hipDeviceSynchronize): call it between steps, not inside one.  < 0: -(HIP error). */
+long long vpn_emd_recovered_samples(void);
+/* Workgroups per sample (G) of the last vpn_emd_fwd / vpn_emd_fwd_ex launch in this process (0: none yet). */
+int vpn_emd_last_group(void);
 /* grad_xyz1 [B,n,3] = 2 grad_dist (xyz1 - xyz2[assignment]) is written; xyz2 receives no gradient
  * (emd_module.py:66-70 returns zeros for it). */
 int vpn_emd_bwd(const float* xyz1, const float* xyz2, const float* grad_dist, const int32_t* assignment,

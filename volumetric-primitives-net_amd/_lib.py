@@ -9,7 +9,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('VPN_HIP_LIB') or os.path.join(_HERE, 'libvpn_hip.so')     # VPN_HIP_LIB: the sanitizer build of the tests
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 _c_f = ctypes.c_void_p      # device pointers travel as void*
 _i, _f, _u64, _sz = ctypes.c_int, ctypes.c_float, ctypes.c_uint64, ctypes.c_size_t
@@ -72,6 +72,9 @@ SIGNATURES = {
                                _f, _f, _i, _c_f, _c_f]),
     'vpn_emd_workspace': (_sz, [_i, _i]),
     'vpn_emd_fwd': (_i, [_c_f, _c_f, _i, _i, _f, _i, _c_f, _c_f, _c_f, _i, _c_f]),
+    'vpn_emd_fwd_ex': (_i, [_c_f, _c_f, _i, _i, _f, _i, _c_f, _c_f, _c_f, _i, _c_f, ctypes.c_uint]),
+    'vpn_emd_recovered_samples': (ctypes.c_longlong, []),
+    'vpn_emd_last_group': (_i, []),
     'vpn_emd_bwd': (_i, [_c_f, _c_f, _c_f, _c_f, _i, _i, _c_f, _c_f]),
 }
 

@@ -3,6 +3,11 @@ of the reference).  The operators take them as explicit arguments; these are onl
 SAMPLE_NUM = 128            # config.py:8
 CD_W1 = 1.0                 # config.py:11
 CD_W2 = 1.0                 # config.py:12
+L_VIEW_CD = 1.0             # config.py:13-17: the five loss weights of train.py:243-262
+L_CAN_CD = 0.0
+L_SIL = 0.0
+L_VP_DIV = 0.1
+L_EMD = 1.0
 MANUAL_SEED = 1234          # config.py:20
 VP_CLAMP_MIN = 0.01         # config.py:22
 VP_CLAMP_MAX = 0.8          # config.py:23

@@ -9,7 +9,8 @@
 //   the last iteration assigns every remaining point to its bid;  dist = squared distance to the assigned target.
 //
 // MI355X design: G persistent workgroups (1024 lanes = 16 waves each; G = 1..16, bounded by the occupancy query) per
-// sample run all iterations in a single launch (the reference needs 7 x iters launches).  Three kernels, by n:
+// sample run all iterations in a single launch (the reference needs 7 x iters launches); when G > 1 a second launch at
+// G = 1 redoes any sample whose workgroups could not all be resident together (emd_redo_skip).  Three kernels, by n:
 //   emd_auction_team_kernel   128 <= n <= 2048 (the training call): replicated state in LDS, pruned Bid scan over a
 //                             cell grid, bids exchanged between the workgroups by tagged granules;
 //   emd_auction_local_kernel  n <= 4096 otherwise: replicated state in LDS, full Bid scan, one group barrier per round;
@@ -71,10 +72,14 @@ __device__ inline void emd_st(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_REL
 // (emd_st / emd_ld); every wave waits for its own stores and atomics to be acknowledged (vmcnt counts stores on gfx9)
 // BEFORE the workgroup barrier; only then one lane adds to the group's counter and polls it with sc1 loads; the other
 // waves load shared state only after the second workgroup barrier.
-// Co-residency of the G workgroups is required while they spin: the host bounds G by the occupancy query so that the
-// whole grid of its plain launch is resident (VPN_EMD_COOP_LAUNCH=1: a cooperative launch, the runtime rejects a grid
-// that cannot be resident and the host falls back to G = 1).  As a last resort the spin is bounded: after ~1 s (other work holding the CUs, a partitioned device) the workgroup gives up, flags
-// the sample and the kernel writes NaN distances for it instead of hanging the GPU.
+// Co-residency of the G workgroups is required while they spin.  The host bounds G by the occupancy query, which
+// assumes an idle device: a plain launch is resident as a whole unless something else holds CUs -- another process on
+// the GPU, a long kernel of another stream (VPN_EMD_COOP_LAUNCH=1 launches cooperatively instead: the runtime rejects a
+// grid that cannot be resident and the host falls back to G = 1).  So the spin is bounded: after ~0.5 s the workgroup
+// gives up and flags the sample (counters[2b + 1]); its partners see the flag and give up too, and the kernel writes
+// NaN / -1 for the sample instead of hanging the GPU.  Whenever G > 1 the host follows the launch with a REDO launch
+// of the same kernel at G = 1 on the same stream (emd_redo_skip below): it recomputes exactly the flagged samples,
+// with no inter-workgroup barrier, so the caller always gets the G = 1 result -- the same bits.
 constexpr unsigned EMD_SPIN_LIMIT = 1u << 24;          // x s_sleep(1) = 64 cycles each: ~0.5 s at 2.1 GHz
 
 __device__ inline bool emd_group_sync(unsigned* counter, unsigned& passed, int G, int* gave_up) {
@@ -109,13 +114,44 @@ __device__ inline bool emd_group_sync(unsigned* counter, unsigned& passed, int G
     return *gave_up == 0;
 }
 
+// The first group barrier of a launch.  Test hook: a sample b < 32 with bit b of test_mask set gives up here at once
+// (flag, NaN / -1 path) -- no spin, no wait -- so the redo launch can be exercised deterministically.
+__device__ inline bool emd_first_sync(unsigned* counter, unsigned& passed, int G, int* gave_up, unsigned test_mask, int b) {
+    if (G > 1 && b < 32 && ((test_mask >> b) & 1u)) {
+        __syncthreads();
+        if (threadIdx.x == 0) { __hip_atomic_store(counter + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); *gave_up = 1; }
+        __syncthreads();
+        return false;
+    }
+    return emd_group_sync(counter, passed, G, gave_up);
+}
+
+// Samples recomputed by redo launches since the library was loaded (per device; vpn_emd_recovered_samples)
+__device__ unsigned long long emd_recovered;
+
+// Redo launch (G = 1, after a launch with G > 1 on the same stream): true for a sample whose workgroups did not give
+// up -- the workgroup leaves at once.  One uniform branch on the sample's flag; a flagged sample clears its flag (at
+// G = 1 nothing else reads it, and the team kernel's granule wait must not see it) and counts itself.
+__device__ inline bool emd_redo_skip(int redo, unsigned* counters, int b) {
+    if (!redo) return false;
+    if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(counters + 2 * b + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0)
+        return true;
+    __syncthreads();                                            // every wave has read the flag before it is cleared
+    if (threadIdx.x == 0) {
+        __hip_atomic_store(counters + 2 * b + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(&emd_recovered, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return false;
+}
+
 // grid: (ceil(B/8) * 8 * G) workgroups; the G workgroups of a sample sit on one XCD (workgroups are dealt to the
 // 8 XCDs round-robin), so its state stays in that XCD's L2.
 __global__ __launch_bounds__(EMD_THREADS) void emd_auction_kernel(const float* __restrict__ xyz1,
                                                                   const float* __restrict__ xyz2, int B, int n,
                                                                   int G, float eps, int iters,
                                                                   float* __restrict__ dist, int32_t* assignment,
-                                                                  float* wsf, unsigned* counters) {
+                                                                  float* wsf, unsigned* counters,
+                                                                  unsigned test_mask, int redo) {
     __shared__ __attribute__((aligned(16))) float tx[EMD_TILE], ty[EMD_TILE], tz[EMD_TILE], tp[EMD_TILE];
     __shared__ int wcount[EMD_WAVES];
     __shared__ int gave_up;
@@ -123,6 +159,7 @@ __global__ __launch_bounds__(EMD_THREADS) void emd_auction_kernel(const float* _
     const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
     const int b = (q / G) * 8 + xcd, g = q % G;
     if (b >= B) return;                                         // padding workgroups of a ragged batch
+    if (emd_redo_skip(redo, counters, b)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int gtid = g * EMD_THREADS + tid, gthreads = G * EMD_THREADS;
     const float* p1 = xyz1 + (size_t)b * n * 3;
@@ -143,7 +180,7 @@ __global__ __launch_bounds__(EMD_THREADS) void emd_auction_kernel(const float* _
     for (int j = gtid; j < n; j += gthreads) {                  // emd_module.py:44-50 initial state
         emd_st(assign + j, -1); emd_st(assign_inv + j, -1); emd_st(price + j, 0.0f); emd_st(top + j, 0ull);
     }
-    ok = emd_group_sync(counter, passed, G, &gave_up);
+    ok = emd_first_sync(counter, passed, G, &gave_up, test_mask, b);
 
     const int per = (n + EMD_THREADS - 1) / EMD_THREADS, j0 = min(n, tid * per), j1 = min(n, j0 + per);
     for (int it = 0; ok && it < iters; ++it) {
@@ -280,7 +317,8 @@ __global__ __launch_bounds__(EMD_THREADS) void emd_auction_local_kernel(const fl
                                                                         const float* __restrict__ xyz2, int B, int n,
                                                                         int npad, int G, float eps, int iters,
                                                                         float* __restrict__ dist, int32_t* assignment,
-                                                                        float* wsf, unsigned* counters) {
+                                                                        float* wsf, unsigned* counters,
+                                                                        unsigned test_mask, int redo) {
     extern __shared__ __attribute__((aligned(16))) float emd_lds[];      // 4 planes of npad floats + 3 arrays of npad ints
     float* tx = emd_lds; float* ty = tx + npad; float* tz = ty + npad; float* tp = tz + npad;
     int* assign_l = reinterpret_cast<int*>(tp + npad);
@@ -291,7 +329,7 @@ __global__ __launch_bounds__(EMD_THREADS) void emd_auction_local_kernel(const fl
     if (threadIdx.x == 0) gave_up = 0;
     const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
     const int b = (q / G) * 8 + xcd, g = q % G;
-    if (b >= B) return;
+    if (b >= B || emd_redo_skip(redo, counters, b)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* p1 = xyz1 + (size_t)b * n * 3;
     const float* p2 = xyz2 + (size_t)b * n * 3;
@@ -309,7 +347,7 @@ __global__ __launch_bounds__(EMD_THREADS) void emd_auction_local_kernel(const fl
         assign_l[j] = -1; inv_l[j] = -1;
     }
     for (int j = g * EMD_THREADS + tid; j < 3 * n; j += G * EMD_THREADS) emd_st(top + j, 0ull);
-    ok = emd_group_sync(counter, passed, G, &gave_up);
+    ok = emd_first_sync(counter, passed, G, &gave_up, test_mask, b);
 
     const int per = (n + EMD_THREADS - 1) / EMD_THREADS, j0 = min(n, tid * per), j1 = min(n, j0 + per);
     for (int it = 0; ok && it < iters; ++it) {
@@ -1002,7 +1040,8 @@ __global__ __launch_bounds__(EMD_THREADS, 4) void emd_auction_team_kernel(const 
                                                                           const float* __restrict__ xyz2, int B, int n,
                                                                           int npad, int G, int lgG, float eps, int iters,
                                                                           float* __restrict__ dist, int32_t* assignment,
-                                                                          float* wsf, unsigned* counters, int tnum, int tmax, int flat_min, int flat_lds, int flat_work) {
+                                                                          float* wsf, unsigned* counters, int tnum, int tmax, int flat_min, int flat_lds, int flat_work,
+                                                                          unsigned test_mask, int redo) {
     extern __shared__ __attribute__((aligned(16))) float emd_lds[];
     const int nown = npad >> lgG;                                // points this workgroup bids for (local index i >> lgG)
     float4* t4 = reinterpret_cast<float4*>(emd_lds);                                               // SORTED by cell, then index
@@ -1022,7 +1061,7 @@ __global__ __launch_bounds__(EMD_THREADS, 4) void emd_auction_team_kernel(const 
     if (threadIdx.x == 0) { gave_up = 0; emd3_flat_off = 0; emd3_flat_tpb = 1.0e9f; }
     const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
     const int b = (q / G) * 8 + xcd, g = q % G;
-    if (b >= B) return;
+    if (b >= B || emd_redo_skip(redo, counters, b)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* p1 = xyz1 + (size_t)b * n * 3;
     const float* p2 = xyz2 + (size_t)b * n * 3;
@@ -1121,7 +1160,7 @@ __global__ __launch_bounds__(EMD_THREADS, 4) void emd_auction_team_kernel(const 
         for (int j = tid; j < npad; j += EMD_THREADS) { assign_l[j] = -1; inv_l[j] = -1; top_l[j] = 0ull; }
     }
     for (int j = g * EMD_THREADS + tid; j < 2 * n; j += G * EMD_THREADS) emd_st(bids + j, 0ull);
-    bool ok = emd_group_sync(counter, passed, G, &gave_up);       // the launch's only counter barrier: granule tags start at 0
+    bool ok = emd_first_sync(counter, passed, G, &gave_up, test_mask, b);   // the launch's only counter barrier: granule tags start at 0
     // first bid of a point (no memory yet): radius that holds ~6 targets of a cloud that fills its box; doubled until two are found
     const float r_first = 1.5f * cbrtf(fmaxf(grid.cw[0] * (float)egx, 1e-30f) * fmaxf(grid.cw[1] * EG3, 1e-30f) * fmaxf(grid.cw[2] * EG3, 1e-30f)
                                        * (6.0f / (4.0f * 3.14159265f)) / (float)n);
@@ -1278,6 +1317,14 @@ __global__ __launch_bounds__(EMD_THREADS, 4) void emd_auction_team_kernel(const 
     }
 }
 
+// Zero the samples' [arrivals, gave-up flag] words before a launch.  A kernel, not hipMemsetAsync: replayed from a captured
+// HIP graph, the memset node left other values in these words from the second replay on (measured on MI355X), which
+// skipped the first group barrier and flagged samples that had not given up.
+__global__ __launch_bounds__(256) void emd_counters_reset_kernel(unsigned* counters, int words) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < words) counters[i] = 0u;
+}
+
 // NmDistanceGradKernel :284-300: grad_xyz1 = (2 g) (x1 - x2[assignment]); xyz2 gets no gradient
 __global__ __launch_bounds__(256) void emd_bwd_kernel(const float* __restrict__ xyz1, const float* __restrict__ xyz2,
                                                       const float* __restrict__ grad_dist,
@@ -1308,6 +1355,7 @@ using namespace vpn;
 enum EmdForm { EMD_TEAM, EMD_LOCAL, EMD_STREAMING };
 static const char* const EMD_FORM_NAMES[] = {"team", "local", "streaming"};
 static const char* const EMD_KERNEL_NAMES[] = {"emd_auction_team_kernel", "emd_auction_local_kernel", "emd_auction_kernel"};
+static const char* const EMD_REDO_NAMES[] = {"emd_auction_team_kernel (redo)", "emd_auction_local_kernel (redo)", "emd_auction_kernel (redo)"};
 
 static bool emd_form_takes(int form, int n) {
     return form == EMD_TEAM ? n >= 128 && n <= EMD_TEAM_MAX : form == EMD_LOCAL ? n <= EMD_TILE : true;
@@ -1350,6 +1398,7 @@ static EmdGroup emd_group_size(const void* kern, LdsOf lds_of, bool divides_npad
 }
 
 static size_t emd_lds_raised[3];          // per form: the dynamic LDS its kernel has been allowed so far
+static int emd_last_group = 0;            // G of the last main launch (vpn_emd_last_group)
 
 template <typename T> struct emd_exactly { using type = T; };      // keeps `args` out of template argument deduction
 
@@ -1358,14 +1407,17 @@ template <typename T> struct emd_exactly { using type = T; };      // keeps `arg
 // as variables of exactly its parameter types; grp.G (and grp.lg) are among them, so the cooperative launch's argument
 // list and the fallback see the same group size.
 // G is bounded by the occupancy query on every call, so the grid of a PLAIN launch is resident as a whole unless
-// something else holds the CUs (then the bounded spin gives up: NaN / -1, a loud failure).  VPN_EMD_COOP_LAUNCH=1
+// something else holds the CUs; then the bounded spin gives up, and the REDO launch that follows every launch with
+// G > 1 (same kernel, G = 1, same stream: `grp`, `test_mask` and `redo` are among `args` by reference) recomputes the
+// flagged samples -- on an idle device one wave of workgroups that read a flag and leave.  VPN_EMD_COOP_LAUNCH=1
 // launches cooperatively when G > 1, which adds the runtime's own residency check (if it refuses the grid: G = 1) --
 // off by default since round 4: in a process that has captured a HIP graph, ONE cooperative launch makes every later
 // dispatch of the process ~50 us slower (profiles/r04_coop_launch_side_effect.txt: the C5 step 1.90 -> 2.55 ms, every
 // kernel of it +45..65 us, eager and replayed), and it costs ~40 us of host time per call.
 template <typename LdsOf, typename... P>
 static int emd_launch(EmdForm form, void (*kern)(P...), LdsOf lds_of, bool divides_npad, int B, int n, int npad,
-                      int max_group, EmdGroup& grp, hipStream_t s, typename emd_exactly<P>::type&... args) {
+                      int max_group, EmdGroup& grp, unsigned& test_mask, int& redo, hipStream_t s,
+                      typename emd_exactly<P>::type&... args) {
     const void* k = reinterpret_cast<const void*>(kern);
     if (lds_of(1) > emd_lds_raised[form]) {
         const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_of(1));
@@ -1374,18 +1426,32 @@ static int emd_launch(EmdForm form, void (*kern)(P...), LdsOf lds_of, bool divid
     }
     grp = emd_group_size(k, lds_of, divides_npad, B, n, npad, max_group);
     const int padded = (B + 7) / 8 * 8;
+    bool launched = false;
+    redo = 0;
     if (grp.G > 1 && emd_env_flag("VPN_EMD_COOP_LAUNCH")) {
         void* argv[] = {(void*)&args...};
         vpn::prof_begin(EMD_KERNEL_NAMES[form], s);
         const hipError_t e = hipLaunchCooperativeKernel(k, dim3(padded * grp.G), dim3(EMD_THREADS), argv, (unsigned)lds_of(grp.G), s);
         vpn::prof_end(s);
-        if (e == hipSuccess) return 0;
-        (void)hipGetLastError();
-        if (e != hipErrorCooperativeLaunchTooLarge && e != hipErrorNotSupported && e != hipErrorInvalidConfiguration) return (int)e;
-        grp = {1, 0};
+        launched = e == hipSuccess;
+        if (!launched) {
+            (void)hipGetLastError();
+            if (e != hipErrorCooperativeLaunchTooLarge && e != hipErrorNotSupported && e != hipErrorInvalidConfiguration) return (int)e;
+            grp = {1, 0};
+        }
     }
-    VPN_LAUNCH_AS(EMD_KERNEL_NAMES[form], kern, dim3(padded * grp.G), dim3(EMD_THREADS), (unsigned)lds_of(grp.G), s, args...);
-    VPN_LAUNCH_CHECK();
+    if (!launched) {
+        VPN_LAUNCH_AS(EMD_KERNEL_NAMES[form], kern, dim3(padded * grp.G), dim3(EMD_THREADS), (unsigned)lds_of(grp.G), s, args...);
+        VPN_LAUNCH_CHECK();
+    }
+    emd_last_group = grp.G;
+    if (grp.G > 1) {                      // the redo launch: flagged samples again at G = 1, the others leave at once
+        grp = {1, 0};
+        test_mask = 0;
+        redo = 1;
+        VPN_LAUNCH_AS(EMD_REDO_NAMES[form], kern, dim3(padded), dim3(EMD_THREADS), (unsigned)lds_of(1), s, args...);
+        VPN_LAUNCH_CHECK();
+    }
     return 0;
 }
 
@@ -1396,8 +1462,8 @@ extern "C" size_t vpn_emd_workspace(int B, int n) {
     return emd_state_bytes(B, n) + ((size_t)2 * B * sizeof(unsigned) + 7) / 8 * 8;
 }
 
-extern "C" int vpn_emd_fwd(const float* xyz1, const float* xyz2, int B, int n, float eps, int iters, float* dist,
-                           int32_t* assignment, void* workspace, int max_group, void* stream) {
+extern "C" int vpn_emd_fwd_ex(const float* xyz1, const float* xyz2, int B, int n, float eps, int iters, float* dist,
+                              int32_t* assignment, void* workspace, int max_group, void* stream, unsigned test_giveup_mask) {
     if (!xyz1 || !xyz2 || !dist || !assignment || !workspace || B < 0 || n < 0 || iters < 1 || !(eps >= 0.0f))
         return VPN_E_BADARG;
     if ((long long)B * n * 3 > 0x7fffffffLL) return VPN_E_TOOBIG;
@@ -1405,9 +1471,12 @@ extern "C" int vpn_emd_fwd(const float* xyz1, const float* xyz2, int B, int n, f
     if (B == 0 || n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     unsigned* counters = reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + emd_state_bytes(B, n));
-    if (hipMemsetAsync(counters, 0, (size_t)2 * B * sizeof(unsigned), s) != hipSuccess) return (int)hipGetLastError();
+    VPN_LAUNCH(emd_counters_reset_kernel, dim3((2 * B + 255) / 256), dim3(256), 0, s, counters, 2 * B);
+    VPN_LAUNCH_CHECK();
     float* wsf = (float*)workspace;
     EmdGroup grp{1, 0};
+    unsigned test_mask = test_giveup_mask;
+    int redo = 0;
     switch (emd_form(n)) {
     case EMD_TEAM: {
         // pruned scan, static ownership, granule exchange
@@ -1423,24 +1492,38 @@ extern "C" int vpn_emd_fwd(const float* xyz1, const float* xyz2, int B, int n, f
         int flat_min = 1, flat_work = 0;
         if (const char* e = getenv("VPN_EMD_FLAT_MIN")) flat_min = atoi(e);
         if (const char* e = getenv("VPN_EMD_FLAT_WORK")) flat_work = atoi(e);
-        return emd_launch(EMD_TEAM, emd_auction_team_kernel, lds_of, true, B, n, npad, max_group, grp, s, xyz1, xyz2, B, n,
+        return emd_launch(EMD_TEAM, emd_auction_team_kernel, lds_of, true, B, n, npad, max_group, grp, test_mask, redo, s, xyz1, xyz2, B, n,
                           npad, grp.G, grp.lg, eps, iters, dist, assignment, wsf, counters, tnum, tmax, flat_min, flat_lds,
-                          flat_work);
+                          flat_work, test_mask, redo);
     }
     case EMD_LOCAL: {
         // one-tile problem: replicated state, one group barrier per round
         int npad = (n + 64 * EMD_UNROLL - 1) / (64 * EMD_UNROLL) * (64 * EMD_UNROLL);
         auto lds_of = [&](int) { return (size_t)npad * 7 * sizeof(float); };
-        return emd_launch(EMD_LOCAL, emd_auction_local_kernel, lds_of, false, B, n, npad, max_group, grp, s, xyz1, xyz2, B,
-                          n, npad, grp.G, eps, iters, dist, assignment, wsf, counters);
+        return emd_launch(EMD_LOCAL, emd_auction_local_kernel, lds_of, false, B, n, npad, max_group, grp, test_mask, redo, s, xyz1, xyz2, B,
+                          n, npad, grp.G, eps, iters, dist, assignment, wsf, counters, test_mask, redo);
     }
     case EMD_STREAMING:
     default: {
         auto lds_of = [](int) { return (size_t)0; };
-        return emd_launch(EMD_STREAMING, emd_auction_kernel, lds_of, false, B, n, 0, max_group, grp, s, xyz1, xyz2, B, n,
-                          grp.G, eps, iters, dist, assignment, wsf, counters);
+        return emd_launch(EMD_STREAMING, emd_auction_kernel, lds_of, false, B, n, 0, max_group, grp, test_mask, redo, s, xyz1, xyz2, B, n,
+                          grp.G, eps, iters, dist, assignment, wsf, counters, test_mask, redo);
     }
     }
+}
+
+extern "C" int vpn_emd_fwd(const float* xyz1, const float* xyz2, int B, int n, float eps, int iters, float* dist,
+                           int32_t* assignment, void* workspace, int max_group, void* stream) {
+    return vpn_emd_fwd_ex(xyz1, xyz2, B, n, eps, iters, dist, assignment, workspace, max_group, stream, 0u);
+}
+
+extern "C" int vpn_emd_last_group(void) { return emd_last_group; }
+
+extern "C" long long vpn_emd_recovered_samples(void) {
+    hipError_t e = hipDeviceSynchronize();
+    unsigned long long v = 0;
+    if (e == hipSuccess) e = hipMemcpyFromSymbol(&v, HIP_SYMBOL(emd_recovered), sizeof(v), 0, hipMemcpyDeviceToHost);
+    return e == hipSuccess ? (long long)v : -(long long)e;
 }
 
 extern "C" int vpn_emd_bwd(const float* xyz1, const float* xyz2, const float* grad_dist, const int32_t* assignment,

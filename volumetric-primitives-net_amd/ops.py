@@ -413,6 +413,26 @@ def chamfer_nn(p1, p2, mode='auto'):
     return d1, i1, d2, i2
 
 
+# Test hook of the auction (vpn_emd_fwd_ex): bit b set = sample b < 32 of every EMD call in this process gives up at its
+# first group barrier whenever the call runs with G > 1, so the G = 1 recovery launch redoes it.  0 in normal use.
+EMD_TEST_GIVEUP_MASK = 0
+
+
+def emd_recovered_samples():
+    """Samples the auction's G = 1 recovery launches have recomputed on the current device since the library was loaded
+    (workgroups of a sample that could not all be resident together: another process or stream held the CUs).  Waits
+    for the device: call it between steps."""
+    v = _lib.lib().vpn_emd_recovered_samples()
+    if v < 0:
+        _lib.check(int(-v))
+    return int(v)
+
+
+def emd_last_group():
+    """Workgroups per sample (G) of the last auction launch in this process (0: none yet)."""
+    return int(_lib.lib().vpn_emd_last_group())
+
+
 class EmdFunction(Function):
     """emdFunction (modules/loss/emd/emd_module.py:29-70) on vpn_emd_fwd / vpn_emd_bwd: auction
     approximation of the Earth Mover's Distance.  Returns (dist [B,n] squared distance to the assigned
@@ -421,10 +441,13 @@ class EmdFunction(Function):
     @staticmethod
     def forward(ctx, xyz1, xyz2, eps, iters, max_group=None):
         """max_group: cap on the workgroups per sample (None: VPN_EMD_GROUP or automatic; 1: no inter-workgroup barrier --
-        forced when other streams share the GPU (VPN_CONCURRENT=1), because the group barrier needs the whole grid
-        resident).  The library bounds the group by the occupancy query and launches plainly (VPN_EMD_COOP_LAUNCH=1: a
-        cooperative launch, which falls back to one workgroup per sample if the runtime refuses the grid); the kernel
-        follows from n (VPN_EMD_FORM=team|local|streaming overrides it).  The result is the same bits in every case."""
+        what VPN_CONCURRENT=1 picks, since there other streams of this process share the GPU by design).  The library
+        bounds the group by the occupancy query of an idle GPU and launches plainly (VPN_EMD_COOP_LAUNCH=1: a cooperative
+        launch, which falls back to one workgroup per sample if the runtime refuses the grid).  When another process or
+        stream keeps some of a sample's workgroups from being resident, their bounded wait gives up and the launch at
+        G = 1 that follows every G > 1 launch recomputes the sample (emd_recovered_samples() counts them): sharing the
+        GPU costs time, not correctness.  The kernel follows from n (VPN_EMD_FORM=team|local|streaming overrides it).
+        The result is the same bits in every case."""
         B, n, _ = xyz1.size()
         assert n == xyz2.size(1)                       # emd_module.py:36-37
         assert B == xyz2.size(0)
@@ -435,8 +458,8 @@ class EmdFunction(Function):
         ws = torch.empty((max(1, _lib.lib().vpn_emd_workspace(B, n) // 4),), dtype=torch.float32, device=dev)
         if max_group is None:
             max_group = 1 if CONCURRENT_BRANCHES else int(os.environ.get('VPN_EMD_GROUP', '0'))
-        _lib.call('vpn_emd_fwd', _lib.ptr(xyz1), _lib.ptr(xyz2), B, n, float(eps), int(iters), _lib.ptr(dist),
-                  _lib.ptr(assignment), _lib.ptr(ws), int(max_group), _lib.stream())
+        _lib.call('vpn_emd_fwd_ex', _lib.ptr(xyz1), _lib.ptr(xyz2), B, n, float(eps), int(iters), _lib.ptr(dist),
+                  _lib.ptr(assignment), _lib.ptr(ws), int(max_group), _lib.stream(), EMD_TEST_GIVEUP_MASK)
         ctx.save_for_backward(xyz1, xyz2, assignment)
         ctx.mark_non_differentiable(assignment)
         return dist, assignment
@@ -853,8 +876,9 @@ class TrainStepLossFunction(Function):
                 side = _side_stream(dev)
                 side.wait_stream(main)
                 es = ctypes.c_void_p(side.cuda_stream)
-            _lib.call('vpn_emd_fwd', _lib.ptr(points), _lib.ptr(gt_view), B, N, float(eps), int(iters), _lib.ptr(emd_dist),
-                      _lib.ptr(emd_assign), _lib.ptr(ews), 1 if CONCURRENT_BRANCHES else int(os.environ.get('VPN_EMD_GROUP', '0')), es)
+            _lib.call('vpn_emd_fwd_ex', _lib.ptr(points), _lib.ptr(gt_view), B, N, float(eps), int(iters), _lib.ptr(emd_dist),
+                      _lib.ptr(emd_assign), _lib.ptr(ews), 1 if CONCURRENT_BRANCHES else int(os.environ.get('VPN_EMD_GROUP', '0')), es,
+                      EMD_TEST_GIVEUP_MASK)
         ntile = ((Wr + 15) // 16) * ((Hr + 15) // 16)
         use_order = render and TILE_ORDER and K <= 64 and ntile <= 16384 and K * 84 + (K + 2) * 4 + ntile <= 24576
         order = None
