@@ -692,10 +692,16 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
 // One launch converts both clouds of a Chamfer call.  1-D grid of B * (j0.ysplit + j1.ysplit) workgroups, decoded
 // such that sample b runs on XCD b / (B/8) — where the filter kernel will read what is written here (its own remap).
-__global__ __launch_bounds__(CFEAT_THREADS) void chamfer_feat_kernel(const FeatJob j0, const FeatJob j1, int B) {
+// Grid: [the Morton-cell order of j0's samples: ord workgroups, when j0.perm] + B * (j0.ysplit + j1.ysplit) slices.
+__global__ __launch_bounds__(CFEAT_THREADS) void chamfer_feat_kernel(const FeatJob j0, const FeatJob j1, int B, int ord) {
     __shared__ float red[CFEAT_THREADS / 64];
     int b, sy;
-    feat_decode(blockIdx.x, B, b, sy);
+    if ((int)blockIdx.x < ord) {
+        feat_decode(blockIdx.x, ord, b, sy);
+        if (b < B) feat_order_wg(j0, b);
+        return;
+    }
+    feat_decode((int)blockIdx.x - ord, B, b, sy);
     const bool other = sy >= j0.ysplit;
     feat_slice(other ? j1 : j0, b, sy - (other ? j0.ysplit : 0), red);
 }
@@ -1053,6 +1059,8 @@ struct ScanJob {          // one direction of a Chamfer call
     int Nq, Nt, Ntp, gx, G;                       // G = gx * B workgroups
     float* out_dist; int32_t* out_idx;
     float* wgsum;                                 // [B][gx]: sum of the minima of each workgroup's queries (fixed order)
+    const int32_t* qperm;                         // [B][pad32(Nq)]: the order the queries are visited in (null: natural)
+    const float* tboxes;                          // fp16 filter: box per 256-target tile (vpn_chamfer_feat.h), null: no skipping
 };
 
 // Both directions of a Chamfer call in ONE launch: workgroups [0, j0.G) run job 0, the rest job 1.  Launched
@@ -1098,6 +1106,8 @@ __global__ __launch_bounds__(cm_block<PREC>(), PREC == 1 ? 5 : CM_WAVES_PER_EU) 
     float* __restrict__ out_dist = other ? j1.out_dist : j0.out_dist;
     int32_t* __restrict__ out_idx = other ? j1.out_idx : j0.out_idx;
     float* __restrict__ wgsum = other ? j1.wgsum : j0.wgsum;
+    const int32_t* __restrict__ qperm = PREC == 2 ? (other ? j1.qperm : j0.qperm) : nullptr;   // the fp16 filter only
+    const float* __restrict__ tboxes = PREC == 2 ? (other ? j1.tboxes : j0.tboxes) : nullptr;
     // Workgroups are dealt round-robin over the 8 XCDs (L2 is per XCD), so the id inside the job is remapped such
     // that all workgroups of a sample land on ONE XCD and stream its target rows out of that XCD's L2 (speed only:
     // any placement is correct; j0.G is a multiple of 8 whenever B is, so id & 7 is still the XCD).
@@ -1110,7 +1120,9 @@ __global__ __launch_bounds__(cm_block<PREC>(), PREC == 1 ? 5 : CM_WAVES_PER_EU) 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, jq = lane & 31, half = lane >> 5;
     const float* qb = qpts + (size_t)b * Nq * 3;
     const int qi = (bx * (cm_block<PREC>() / 64) + wave) * 32 + jq;
-    const int qc = min(qi, Nq - 1);
+    // the query this lane serves, as an index of the caller's cloud (the order only groups queries into waves; the
+    // clamp keeps a stale permutation from turning into a wild access)
+    const int qc = qperm ? min(max(qperm[(size_t)b * ((Nq + 63) & ~63) + min(qi, Nq - 1)], 0), Nq - 1) : min(qi, Nq - 1);
     const F3 a3 = ld3(qb + qc * 3);
     const float ax = a3.x, ay = a3.y, az = a3.z;
     // B operand (K x N): lane supplies B[k = lane/32][n = lane%32]
@@ -1203,6 +1215,19 @@ __global__ __launch_bounds__(cm_block<PREC>(), PREC == 1 ? 5 : CM_WAVES_PER_EU) 
         const float mAB = min32(accA, accB);                                                   \
         CM_UPDATE_C(mAB, J)                                                                    \
     }
+        // Tile skipping: U = best / S^2 + skipc bounds from above the exact d2 of the target that holds this
+        // lane's filtered best, with the tie width and every rounding on top; a tile whose box lies farther than U from
+        // the query holds no target that can win or tie, nor any that would move the winner cell or lower V2.  skipc is
+        // +inf (never skip) outside the fp16 filter's domain and for non-finite queries; NaN anywhere compares false.
+        float skipc = __builtin_inff();
+        const float* __restrict__ tbox = tboxes ? tboxes + (size_t)b * (Ntp >> 5) * CFEAT_BOXF : nullptr;
+        if (tbox) {
+            const float nb0 = __uint_as_float(wave_max_bits(lane < CFEAT_SLOTS ? nmax[b * CFEAT_SLOTS + lane] : 0u));
+            const float na0 = ax * ax + ay * ay + az * az;
+            const float r = sqrt_up(na0) + sqrt_up(nb0), r2 = r * r;   // >= (|a| + |b|)^2 for every target b
+            const float E0 = CM_EPS_F16 * r2 * (1.0f + 1.0e-6f) + 5.9604644775390625e-08f * 1.7320509f * r;
+            if (nb0 <= CM_DOMAIN16 && na0 <= CM_DOMAIN16) skipc = (na0 + E0) + (3.0e-5f * r2 + 1.0e-30f);
+        }
         Pre pre = fetch(0);
         stash(0, pre);
         __syncthreads();
@@ -1210,6 +1235,20 @@ __global__ __launch_bounds__(cm_block<PREC>(), PREC == 1 ? 5 : CM_WAVES_PER_EU) 
         for (int t0 = 0; t0 < Ntp; t0 += CM_TILE16, buf ^= 1) {
             const bool more = t0 + CM_TILE16 < Ntp;
             if (more) pre = fetch(t0 + CM_TILE16);     // in flight during the MFMA loop, stored to LDS after it
+            bool scan = true;
+            if (tbox) {                                // wave-uniform box: scalar loads
+                const float4 bl = *reinterpret_cast<const float4*>(tbox + (t0 >> 8) * CFEAT_BOXF);
+                const float2 bh = *reinterpret_cast<const float2*>(tbox + (t0 >> 8) * CFEAT_BOXF + 4);
+                const float dx = fmaxf(fmaxf(bl.x - ax, ax - bl.w), 0.0f);
+                const float dy = fmaxf(fmaxf(bl.y - ay, ay - bh.x), 0.0f);
+                const float dz = fmaxf(fmaxf(bl.z - az, az - bh.y), 0.0f);
+                const float L = ((dx * dx + dy * dy) + dz * dz) * (1.0f - 1.0e-6f);
+                scan = __ballot(!(L > __builtin_fmaf(best, CM_INV_S16SQ, skipc))) != 0ull;
+#ifdef VPN_CHAMFER_DEBUG
+                if (!scan && lane == 0) atomicAdd(&g_dbg[3], 1ull);   // skipped (wave, tile) pairs
+#endif
+            }
+            if (scan) {
             const int nblk = min(CM_TILE16, Ntp - t0) >> 5;          // 2, 4, 6 or 8 (Ntp is a multiple of 64)
             const unsigned char* T = &tileH[buf][jq * CM_ROWB + half * 16];
             const float before = best;
@@ -1225,6 +1264,7 @@ __global__ __launch_bounds__(cm_block<PREC>(), PREC == 1 ? 5 : CM_WAVES_PER_EU) 
                 }
             }
             blk = best < before ? t0 + (blkc << 6) : blk;            // the tile improved this lane's minimum
+            }
             if (more) stash(buf ^ 1, pre);
             __syncthreads();
         }
@@ -1495,11 +1535,11 @@ __global__ __launch_bounds__(cm_block<PREC>(), PREC == 1 ? 5 : CM_WAVES_PER_EU) 
     int pos = -1;                                                   // (s_cnt was zeroed before the tile loop, whose barriers order it)
     if (half == 0 && qi < Nq) {
         if (!ambiguous) {
-            out_dist[(size_t)b * Nq + qi] = s;
-            out_idx[(size_t)b * Nq + qi] = idx;
+            out_dist[(size_t)b * Nq + qc] = s;
+            out_idx[(size_t)b * Nq + qc] = idx;
         } else {
             pos = atomicAdd(&s_cnt, 1);
-            s_qd[pos] = make_float4(ax, ay, az, s); s_qi[pos] = make_int2(qi, idx);
+            s_qd[pos] = make_float4(ax, ay, az, s); s_qi[pos] = make_int2(qc, idx);
 #ifdef VPN_CHAMFER_DEBUG
             atomicAdd(&g_dbg[6], 1ull);
 #endif
@@ -1901,19 +1941,25 @@ static int mfma_both(const float* p1, const float* p2, int B, int N, int M, floa
     const MfmaWs w2 = mfma_carve(ws, B, M, N);                            // p2 = targets of direction 1
     const MfmaWs w1 = mfma_carve(ws + mfma_ws_floats(B, M, N), B, N, M);  // p1 = targets of direction 2
     auto split = [](int Ntp) { return feat_split(Ntp); };
-    const FeatJob f2{p2, M, w2.Ntp, split(w2.Ntp), w2.F, w2.nmax, fp32_filter ? nullptr : w2.H, prec == 2};
-    const FeatJob f1{p1, N, w1.Ntp, split(w1.Ntp), w1.F, w1.nmax, fp32_filter ? nullptr : w1.H, prec == 2};
+    // fp16 filter: direction 2 (queries p2) visits p2 in Morton-cell order and skips p1's tiles (vpn_chamfer_feat.h)
+    const bool skip = prec == 2 && N >= CSKIP_MIN_TARGETS;
+    const FeatJob f2{p2, M, w2.Ntp, split(w2.Ntp), w2.F, w2.nmax, fp32_filter ? nullptr : w2.H, prec == 2, nullptr,
+                     skip ? w2.perm : nullptr};
+    const FeatJob f1{p1, N, w1.Ntp, split(w1.Ntp), w1.F, w1.nmax, fp32_filter ? nullptr : w1.H, prec == 2,
+                     skip ? w1.boxes : nullptr, nullptr};
     hipError_t e = hipSuccess;
     if (!features_ready) {      // mode 7: written by vpn_hotpath_sample_fwd into the same workspace, earlier on this stream
-        VPN_LAUNCH(chamfer_feat_kernel, dim3(B * (f2.ysplit + f1.ysplit)), dim3(CFEAT_THREADS), 0, s, f2, f1, B);
+        const int ord = skip ? (B + 7) & ~7 : 0;
+        VPN_LAUNCH(chamfer_feat_kernel, dim3(ord + B * (f2.ysplit + f1.ysplit)), dim3(CFEAT_THREADS), 0, s, f2, f1, B, ord);
         e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
     }
     {
         const int qpw = prec == 2 ? 32 * CM_WAVES16 : 128;          // queries per workgroup
         const int gx1 = (N + qpw - 1) / qpw, gx2 = (M + qpw - 1) / qpw;
-        const ScanJob s1{p1, w2.F, w2.H, w2.nmax, N, M, w2.Ntp, gx1, gx1 * B, d1, i1, w2.wgsum};     // p1 against p2
-        const ScanJob s2{p2, w1.F, w1.H, w1.nmax, M, N, w1.Ntp, gx2, gx2 * B, d2, i2, w1.wgsum};     // p2 against p1
+        const ScanJob s1{p1, w2.F, w2.H, w2.nmax, N, M, w2.Ntp, gx1, gx1 * B, d1, i1, w2.wgsum, nullptr, nullptr};  // p1 against p2
+        const ScanJob s2{p2, w1.F, w1.H, w1.nmax, M, N, w1.Ntp, gx2, gx2 * B, d2, i2, w1.wgsum,                     // p2 against p1
+                         f2.perm, f1.tboxes};
         const bool long_first = (long long)N > (long long)M;       // direction 2 scans the N targets: more work per workgroup
         const ScanJob& ja = long_first ? s2 : s1;
         const ScanJob& jb = long_first ? s1 : s2;
@@ -1943,8 +1989,9 @@ int chamfer_feat_jobs(void* workspace, size_t workspace_bytes, int B, int N, int
     float* ws = (float*)workspace;
     const MfmaWs w2 = mfma_carve(ws, B, M, N);
     const MfmaWs w1 = mfma_carve(ws + mfma_ws_floats(B, M, N), B, N, M);
-    *job2 = FeatJob{p2, M, w2.Ntp, feat_split(w2.Ntp), w2.F, w2.nmax, w2.H, 1};
-    *job1 = FeatJob{p1, N, w1.Ntp, feat_split(w1.Ntp), w1.F, w1.nmax, w1.H, 1};
+    const bool skip = N >= CSKIP_MIN_TARGETS;                                                          // as mfma_both(prec 2)
+    *job2 = FeatJob{p2, M, w2.Ntp, feat_split(w2.Ntp), w2.F, w2.nmax, w2.H, 1, nullptr, skip ? w2.perm : nullptr};
+    *job1 = FeatJob{p1, N, w1.Ntp, feat_split(w1.Ntp), w1.F, w1.nmax, w1.H, 1, skip ? w1.boxes : nullptr, nullptr};
     return 0;
 }
 

@@ -157,7 +157,11 @@ __device__ inline void sample_wg(PrimLds& P, float* red, int b, int k,
     if (feat) {
         // the last primitive's workgroup also writes the padding rows [N, Np) of the sample (fewer than 64)
         if (k == K - 1) for (int j = K * n + (int)threadIdx.x; j < feat->Np; j += SAMP_BLOCK) feat_point(*feat, b, j, 0.f, 0.f, 0.f);
+        if (feat->tboxes) __threadfence_block();                    // the planes, for the tile boxes behind the barrier
         feat_finish_slice(*feat, b, k, nv, red);
+        // the boxes of the scan's 256-row tiles that lie inside this primitive's rows (all of them when n is a multiple
+        // of 256, as at C3); a tile shared with the next primitive gets the box of all space
+        feat_tile_boxes(*feat, b, k * n, k == K - 1 ? feat->Np : (k + 1) * n);
     }
 }
 
@@ -173,6 +177,7 @@ __global__ __launch_bounds__(SAMP_BLOCK) void sample_fwd_kernel(
 // record workgroups at the head of sample_feat_fwd_kernel's grid: a multiple of 8, so that the sampler workgroups behind
 // them keep their XCD (feat_decode)
 __host__ __device__ inline int rec_workgroups(int BK) { return ((BK + SAMP_BLOCK - 1) / SAMP_BLOCK + 7) & ~7; }
+__host__ __device__ inline int ord_workgroups(int B) { return (B + 7) & ~7; }
 
 // Forward launch of the training step with the Chamfer features inside: 1-D grid of B * K workgroups decoded like the
 // feature kernel's (sample b on XCD b / (B/8)): workgroup (b, k) samples primitive k (also the slot of its max norm:
@@ -205,10 +210,19 @@ __global__ __launch_bounds__(SAMP_BLOCK) void sample_feat_fwd_kernel(
         }
         return;
     }
+    // then the Morton-cell order of each sample's ground-truth cloud (the query order of the scan's direction 2): one
+    // workgroup per sample, a multiple of 8 of them so that the sampler workgroups behind keep their XCD
+    const int nord = gt.perm ? ord_workgroups(B) : 0;
+    if ((int)blockIdx.x < nrec + nord) {
+        int ob, oy;
+        feat_decode((int)blockIdx.x - nrec, nord, ob, oy);
+        if (ob < B) feat_order_wg(gt, ob);
+        return;
+    }
     RasterPrep rq = rp;
     rq.rec = nullptr;                                  // the sampler workgroups keep the counters and the seed only
     int b, sy;
-    feat_decode((int)blockIdx.x - nrec, B, b, sy);
+    feat_decode((int)blockIdx.x - nrec - nord, B, b, sy);
     __shared__ float red_gt[SAMP_BLOCK / 64];
     sample_wg(P, red, b, sy, params, kinds, u, seed, sample_base, K, n, points, rq, &pred, &gt, red_gt);
 }
@@ -855,7 +869,7 @@ extern "C" int vpn_hotpath_sample_fwd(const float* params, const int32_t* kinds,
     if (rc) return rc;
     pred.ysplit = K;                      // one slice (and one max-norm slot) per primitive
     gt.ysplit = K;                        // ... and the same workgroups share the ground-truth cloud
-    const unsigned nrec = (unsigned)rec_workgroups(B * K);
+    const unsigned nrec = (unsigned)rec_workgroups(B * K) + (gt.perm ? (unsigned)ord_workgroups(B) : 0u);
     VPN_LAUNCH(sample_feat_fwd_kernel, dim3((unsigned)B * (unsigned)K + nrec), dim3(SAMP_BLOCK), 0, (hipStream_t)stream,
                params, kinds, u, seed, seed_dev, sample_base, B, K, n, points, rp, pred, gt);
     VPN_LAUNCH_CHECK();

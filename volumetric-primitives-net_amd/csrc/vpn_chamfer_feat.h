@@ -81,6 +81,8 @@ struct FeatJob {          // one cloud: slices [0, ysplit) of a sample's workgro
     const float* pts; int N, Np, ysplit;
     float* F; unsigned int* nmax; unsigned short* H;
     int rows16;           // rows as 32-byte fp16 pieces (PREC 2) instead of 48-byte bf16 pieces (PREC 1)
+    float* tboxes;        // fp16 filter, cloud in the TARGET role of the skipping scan: a box per 256-row tile (or null)
+    int32_t* perm;        // fp16 filter, cloud in the QUERY role of that scan: its points in Morton-cell order (or null)
 };
 
 // workgroup id -> (sample, slice): sample b runs on XCD b / (B/8), where the filter kernel reads what is written
@@ -128,6 +130,172 @@ __device__ inline void feat_finish_slice(const FeatJob& J, int b, int by, float 
     }
 }
 
+template <bool MAX>
+__device__ inline float feat_wave_minmax(float v) {   // any finite or infinite values; the result is wave-uniform
+#define VPN_FDPP(v, ctrl, rmask) \
+    __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), ctrl, rmask, 0xf, false))
+#define VPN_FOP(a, b) (MAX ? fmaxf(a, b) : fminf(a, b))
+    v = VPN_FOP(v, VPN_FDPP(v, 0x111, 0xf)); v = VPN_FOP(v, VPN_FDPP(v, 0x112, 0xf));
+    v = VPN_FOP(v, VPN_FDPP(v, 0x114, 0xf)); v = VPN_FOP(v, VPN_FDPP(v, 0x118, 0xf));
+    v = VPN_FOP(v, VPN_FDPP(v, 0x142, 0xa)); v = VPN_FOP(v, VPN_FDPP(v, 0x143, 0xc));
+#undef VPN_FOP
+#undef VPN_FDPP
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+
+// ---- Tile skipping of the fp16 scan (chamfer.hip, direction 2 of a Chamfer call).  The scan's LDS tiles are 256
+// consecutive target rows; a wave skips a tile when every one of its 32 queries provably has a nearer target already
+// (DESIGN 4.1).  That needs (a) a box per target tile and (b) waves of queries that lie close together, so the query
+// cloud is visited in Morton-cell order (a permutation; the features themselves stay in the original order).
+constexpr int CFEAT_TILE = 256;          // rows per tile box (= CM_TILE16 of the scan)
+constexpr int CFEAT_BOXF = 8;            // floats per box: lo xyz, hi xyz, 2 unused
+// the skipping scan is used when direction 2 has at least this many targets (the sampled cloud): measured, at 2048 targets
+// (8 tiles, the C5 step's clouds) the ordering workgroups cost more than the skipped tiles save
+constexpr int CSKIP_MIN_TARGETS = 4096;
+constexpr int CORD_MAX = 2048;           // largest cloud one workgroup orders (8 cells per lane in registers); larger
+                                         // clouds keep their natural order
+
+// box entry of tile t of sample b of a cloud with Np padded rows (the workspace carves Np / 32 entries per sample)
+__device__ inline float* feat_tile_box(float* boxes, int Np, int b, int t) {
+    return boxes + ((size_t)b * (Np >> 5) + t) * CFEAT_BOXF;
+}
+
+// The boxes of the tiles that meet the rows [rlo, rhi) of sample b, whose planes this workgroup has written (the caller
+// orders those writes before this call with a fence and a barrier).  A tile that lies entirely inside [rlo, rhi) gets
+// the exact box of its points (padding rows excluded; a tile of padding only gets the empty box +inf / -inf); a tile
+// the workgroup shares with another gets the box of all space (never skipped) -- every writer of it writes those same
+// bits.  One wave per tile.
+__device__ inline void feat_tile_boxes(const FeatJob& J, int b, int rlo, int rhi) {
+    if (!J.tboxes || rlo >= rhi) return;
+    const float* f = J.F + (size_t)b * 4 * J.Np;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float inf = __builtin_inff();
+    for (int t = rlo / CFEAT_TILE + wave; t * CFEAT_TILE < rhi; t += CFEAT_THREADS / 64) {
+        const int r0 = t * CFEAT_TILE, r1 = min(r0 + CFEAT_TILE, J.Np);
+        float lo[3] = {-inf, -inf, -inf}, hi[3] = {inf, inf, inf};
+        if (r0 >= rlo && r1 <= rhi) {                               // uniform per wave
+            lo[0] = lo[1] = lo[2] = inf; hi[0] = hi[1] = hi[2] = -inf;
+            const int rn = min(r1, J.N);
+            for (int r = r0 + lane; r < rn; r += 64) {
+                const float x = f[r], y = f[J.Np + r], z = f[2 * J.Np + r];
+                lo[0] = fminf(lo[0], x); hi[0] = fmaxf(hi[0], x);
+                lo[1] = fminf(lo[1], y); hi[1] = fmaxf(hi[1], y);
+                lo[2] = fminf(lo[2], z); hi[2] = fmaxf(hi[2], z);
+            }
+#pragma unroll
+            for (int a = 0; a < 3; ++a) { lo[a] = feat_wave_minmax<false>(lo[a]); hi[a] = feat_wave_minmax<true>(hi[a]); }
+        }
+        if (lane == 0) {
+            float4* o = reinterpret_cast<float4*>(feat_tile_box(J.tboxes, J.Np, b, t));
+            o[0] = make_float4(lo[0], lo[1], lo[2], hi[0]);
+            o[1] = make_float4(hi[1], hi[2], 0.f, 0.f);
+        }
+    }
+}
+
+// The query order of sample b of the cloud J.pts: J.perm[b][s] = the point visited s-th.  A stable counting sort by the
+// 4 x 4 x 4 Morton cell of the sample's bounding box (deterministic: the order inside a cell is the original one), by one
+// workgroup of CFEAT_THREADS lanes.  Lane l of wave w holds the cells of the points w * 64 + l + 256 j (j < CORD_PER),
+// i.e. lane l of every chunk c = w + 4 j of 64 consecutive points: the rank of a point among the chunk's points of its
+// cell comes from six ballots, a table [chunk][cell] of counts in LDS turns into the output positions.  Clouds above
+// CORD_MAX points keep their natural order.  Rows past N are not written (the scan never uses them).
+__device__ inline void feat_order_wg(const FeatJob& J, int b) {
+    constexpr int CORD_PER = CORD_MAX / CFEAT_THREADS;
+    __shared__ unsigned short cnt[CORD_MAX / 64][64];
+    __shared__ float bred[6][CFEAT_THREADS / 64];
+    __shared__ int cbase[64];
+    const int N = J.N, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* p = J.pts + (size_t)b * N * 3;
+    int32_t* po = J.perm + (size_t)b * J.Np;
+    if (N > CORD_MAX) {
+        for (int i = tid; i < N; i += CFEAT_THREADS) po[i] = i;
+        return;
+    }
+    const float inf = __builtin_inff();
+    float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
+#pragma unroll 2
+    for (int j = 0; j < CORD_PER; ++j) {                            // (unrolled little: the sampler's register budget)
+        const F3 v = ld3(p + min(tid + j * CFEAT_THREADS, N - 1) * 3);     // a repeated point changes no box
+        lo[0] = fminf(lo[0], v.x); hi[0] = fmaxf(hi[0], v.x);
+        lo[1] = fminf(lo[1], v.y); hi[1] = fmaxf(hi[1], v.y);
+        lo[2] = fminf(lo[2], v.z); hi[2] = fmaxf(hi[2], v.z);
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float l = feat_wave_minmax<false>(lo[a]), h = feat_wave_minmax<true>(hi[a]);
+        if (lane == 0) { bred[a][wave] = l; bred[3 + a][wave] = h; }
+    }
+    const int nch = (N + 63) >> 6;
+    for (int e = tid; e < nch * 64; e += CFEAT_THREADS) cnt[e >> 6][e & 63] = 0;
+    __syncthreads();
+    float o3[3], sc[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float l = bred[a][0], h = bred[3 + a][0];
+        for (int w = 1; w < CFEAT_THREADS / 64; ++w) { l = fminf(l, bred[a][w]); h = fmaxf(h, bred[3 + a][w]); }
+        o3[a] = l;
+        sc[a] = h > l ? 4.0f / (h - l) : 0.0f;                      // non-finite boxes give cell 0 (the order is only speed)
+    }
+    static_assert(CORD_PER * 6 <= 64, "the cells of a lane's points are packed into 64 bits");
+    unsigned long long keys = 0;                                    // cell of point j in bits [6 j, 6 j + 6)
+#pragma unroll 2
+    for (int j = 0; j < CORD_PER; ++j) {                            // the points again (L2 hits)
+        const F3 v = ld3(p + min(tid + j * CFEAT_THREADS, N - 1) * 3);
+        const float c[3] = {v.x, v.y, v.z};
+        unsigned k = 0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const unsigned ca = (unsigned)(int)fminf(fmaxf((c[a] - o3[a]) * sc[a], 0.0f), 3.0f);   // NaN -> 0
+            k |= ((ca & 1u) << a) | ((ca >> 1) << (a + 3));
+        }
+        keys |= (unsigned long long)k << (6 * j);
+    }
+    // rank of lane among the chunk's lanes of the same cell, and how many there are
+    auto rank_of = [&](unsigned k, bool ok, int& rank, int& count) {
+        unsigned long long eq = __ballot(ok);
+#pragma unroll
+        for (int bit = 0; bit < 6; ++bit) {
+            const bool s = (k >> bit) & 1u;
+            const unsigned long long m = __ballot(s);
+            eq &= s ? m : ~m;
+        }
+        rank = __popcll(eq & ((1ull << lane) - 1ull));
+        count = __popcll(eq);
+    };
+#pragma unroll 2
+    for (int j = 0; j < CORD_PER; ++j) {                            // pass 1: counts per (chunk, cell)
+        const int c = wave + j * (CFEAT_THREADS / 64);
+        if (c >= nch) break;                                        // uniform per wave
+        const bool ok = tid + j * CFEAT_THREADS < N;
+        const unsigned k = (unsigned)(keys >> (6 * j)) & 63u;
+        int rank, count;
+        rank_of(k, ok, rank, count);
+        if (ok && rank == 0) cnt[c][k] = (unsigned short)count;
+    }
+    __syncthreads();
+    if (tid < 64) {                                                 // per cell: exclusive prefix over the chunks
+        int s = 0;
+#pragma unroll 8
+        for (int c = 0; c < nch; ++c) { const int t = cnt[c][tid]; cnt[c][tid] = (unsigned short)s; s += t; }
+        int inc = s;                                                // ... and over the cells
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const int t2 = __shfl_up(inc, o, 64); if (lane >= o) inc += t2; }
+        cbase[tid] = inc - s;
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int j = 0; j < CORD_PER; ++j) {                            // pass 2: positions
+        const int c = wave + j * (CFEAT_THREADS / 64);
+        if (c >= nch) break;
+        const int i = tid + j * CFEAT_THREADS;
+        const bool ok = i < N;
+        const unsigned k = (unsigned)(keys >> (6 * j)) & 63u;
+        int rank, count;
+        rank_of(k, ok, rank, count);
+        if (ok) po[cbase[k] + cnt[c][k] + rank] = i;
+    }
+}
+
 // slice `by` of sample b of the cloud J.pts (AoS xyz): one workgroup of CFEAT_THREADS lanes
 __device__ inline void feat_slice(const FeatJob& J, int b, int by, float* red) {
     const float* pb = J.pts + (size_t)b * J.N * 3;
@@ -149,7 +317,9 @@ __device__ inline void feat_slice(const FeatJob& J, int b, int by, float* red) {
             nv = fmaxf(nv, feat_point(J, b, j, xs[u], ys[u], zs[u]));
         }
     }
+    if (J.tboxes) __threadfence_block();                            // the planes, for the tile boxes behind the barrier
     feat_finish_slice(J, b, by, nv, red);
+    feat_tile_boxes(J, b, jlo, jhi);
 }
 
 // The same slice by the lanes [first, CFEAT_THREADS) of a workgroup and WITHOUT its barrier: the caller has one coming
