@@ -1,0 +1,99 @@
+"""The refinement step of the reference's train_gcn.py (:119-138) on the drop-in surface, with synthetic inputs.
+
+    python examples/train_gcn_step.py [--steps 5] [--batch 8]
+
+VPNetOneRes (a ResNet-18 with MLP heads) is out of scope and torchvision is absent, so a stand-in
+produces what train_gcn.py:126 takes from it: 16 sphere primitives (volumes, rotates, translates) and the ResNet-18
+feature maps of a 128 x 128 image (64@32², 128@16², 256@8², 512@4²) plus a 512-wide global feature.  The rest is the
+reference's step:
+
+    get_vp_meshes / compose_vp_meshes  train_gcn.py:68-88   Meshing.sphere_meshing, Meshing.compose_meshes  (16 x 128 = 2048)
+    gcn(predict_meshes, rgbs, ...)     train_gcn.py:129-130 GCNModel                                        (vpn_gcn_*)
+    cd_loss + emd_loss                 train_gcn.py:132-135 ChamferDistanceLoss + sqrt(EMD dist).mean()
+    Adam(lr, betas=(0.9, 0.99), weight_decay)               train_gcn.py:100-101
+"""
+import argparse
+import os
+import sys
+
+import torch
+import torch.nn as nn
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import vpn_amd  # noqa: E402
+from vpn_amd.modules.network import GCNModel  # noqa: E402
+
+VP_NUM = 16
+
+
+class StandInVPN(nn.Module):
+    """rgbs [B,3,128,128] -> (volumes, rotates, translates) as K lists of (B,3|4|3), perceptual maps, global [B,512]."""
+
+    def __init__(self):
+        super().__init__()
+        self.levels = nn.ModuleList([nn.Conv2d(3, c, 1) for c in (64, 128, 256, 512)])
+        self.head = nn.Linear(512, VP_NUM * 10)
+
+    def forward(self, rgbs):
+        maps = [conv(nn.functional.adaptive_avg_pool2d(rgbs, s)) for conv, s in zip(self.levels, (32, 16, 8, 4))]
+        g = maps[-1].mean((2, 3))
+        p = torch.sigmoid(self.head(g)).view(-1, VP_NUM, 10)
+        volumes = [p[:, k, 0:3] * 0.2 + 0.05 for k in range(VP_NUM)]
+        rotates = [p[:, k, 3:7] for k in range(VP_NUM)]
+        translates = [(p[:, k, 7:10] - 0.5) * 0.8 for k in range(VP_NUM)]
+        return volumes, rotates, translates, maps, g
+
+
+def get_vp_meshes(volumes, rotates, translates):
+    batch_vp_meshes = [[] for _ in range(volumes[0].size(0))]
+    for i in range(VP_NUM):
+        meshes = vpn_amd.Meshing.sphere_meshing(volumes[i], rotates[i], translates[i])
+        for b in range(volumes[0].size(0)):
+            batch_vp_meshes[b].append(meshes[b])
+    return batch_vp_meshes
+
+
+def compose_vp_meshes(batch_vp_meshes):
+    return [vpn_amd.Meshing.compose_meshes(m) for m in batch_vp_meshes]
+
+
+def calculate_emd_loss(predict_points, gt_points):
+    dist, _assignment = vpn_amd.EarthMoverDistanceLoss()(predict_points, gt_points, 0.005, 50)
+    return torch.sqrt(dist).mean()
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--steps', type=int, default=5)
+    ap.add_argument('--batch', type=int, default=8)
+    ap.add_argument('--lr', type=float, default=1e-5)
+    args = ap.parse_args(argv)
+    dev = torch.device('cuda')
+    torch.manual_seed(1234)
+    vpn = StandInVPN().to(dev).eval()
+    gcn = GCNModel().to(dev)
+    optimizer = torch.optim.Adam(params=gcn.parameters(), lr=args.lr, betas=(0.9, 0.99), weight_decay=1e-6)
+    cd_loss_func = vpn_amd.ChamferDistanceLoss()
+    B = args.batch
+    losses = []
+    for step in range(args.steps):
+        rgbs = torch.zeros(B, 3, 128, 128, device=dev)
+        rgbs[:, :, 24:104, 16:112] = torch.rand(B, 3, 80, 96, device=dev)
+        points = (torch.rand(B, VP_NUM * 128, 3, device=dev) - 0.5) * 0.8
+        with torch.no_grad():
+            volumes, rotates, translates, perceptual_features, global_features = vpn(rgbs)
+        predict_meshes = compose_vp_meshes(get_vp_meshes(volumes, rotates, translates))
+        predict_vertices = gcn(predict_meshes, rgbs, perceptual_features, global_features)
+        cd_loss = cd_loss_func(predict_vertices, points)
+        emd_loss = calculate_emd_loss(predict_vertices, points)
+        total_loss = cd_loss + emd_loss
+        optimizer.zero_grad()
+        total_loss.backward()
+        optimizer.step()
+        losses.append((float(cd_loss), float(emd_loss)))
+        print('step %d  CD Loss = %.6f, EMD Loss = %.6f' % (step, losses[-1][0], losses[-1][1]), flush=True)
+    return losses
+
+
+if __name__ == '__main__':
+    main()

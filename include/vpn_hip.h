@@ -34,11 +34,12 @@
 extern "C" {
 #endif
 
-/* 5 (round 4): vpn_vpdiv_fwd, vpn_camera_matrix, vpn_trainstep_finalize, vpn_trainstep_bwd (the reference's whole training
+/* 7: the GCN refinement stage (vpn_gcn_*).  6: vpn_emd_fwd_ex, vpn_emd_recovered_samples, vpn_emd_last_group.
+ * 5 (round 4): vpn_vpdiv_fwd, vpn_camera_matrix, vpn_trainstep_finalize, vpn_trainstep_bwd (the reference's whole training
  * step in one autograd node).  4 (round 3): raster records are 16 float4 per primitive (vpn_raster_records_size grew), tile_order is a buffer of
  * 48-byte tile entries (vpn_raster_order_size, K <= 64).  3: vpn_raster_total_fwd_fin, vpn_hotpath_chamfer_fwd, the mesh
  * entry points. */
-#define VPN_ABI_VERSION 6
+#define VPN_ABI_VERSION 7
 
 /* primitive kinds (reference: train.py:106-116 cuboids first, then spheres, cones are stubs) */
 #define VPN_SPHERE 0
@@ -452,6 +453,47 @@ int vpn_emd_last_group(void);
  * (emd_module.py:66-70 returns zeros for it). */
 int vpn_emd_bwd(const float* xyz1, const float* xyz2, const float* grad_dist, const int32_t* assignment,
                 int B, int n, float* grad_xyz1, void* stream);
+
+/* ---- the GCN refinement stage (modules/network/gcn.py, GCNModel; train_gcn.py / test_gcn.py)
+ * vpn_gcn_aggregate: out [B,N,C] = A x [B,N,C] + bias [C] (bias may be NULL), then max(., 0) when relu != 0, where A is a
+ *   CSR matrix over the N vertices (row_ptr [N+1], col / w [nnz]; the GCN uses the symmetric A = D^-1/2 (A_mesh + I)
+ *   D^-1/2 of PyG's gcn_norm).  mask != NULL ([B,N,C]): x[j] counts only where mask[j] > 0 (the backward of a ReLU'd
+ *   layer: dx = A (g * [y > 0]) for symmetric A).  Fixed summation order (CSR order), no atomics.
+ * vpn_gcn_colsum: out [S,C] = sum_{r < R} in[(s R + r) ld + off + c] (* [mask > 0], mask indexed like in, may be NULL) in
+ *   a fixed order; workspace of vpn_gcn_colsum_workspace(S, R, C) bytes.
+ * vpn_gcn_bounds: get_bound_of_images (gcn.py:90-133) of img [B,C,H,W] -> bounds [B,4] in [-1,1], bit-exact: mask =
+ *   sum_c img > 0.03 (channels added in order); b0 = min{i >= 1 : column i occupied} else 0, b1 = max{j : column j
+ *   occupied} else W, rows alike; b / W * 2 - 1, b / H * 2 - 1 in fp32.
+ * vpn_gcn_input_fwd: conv1's input out [B,N,venc + sum C_l + G] = [encoding | pooled | global] (gcn.py:36-42) of verts
+ *   [B,N,3]: venc = 0 (none), 3 (the vertices) or 39 (positional encoding [x, sin x, cos x, sin 2x, ..., cos 32x],
+ *   gcn.py:73-82); pooled = bilinear samples (align_corners, zero padding, as grid_sample) of the L <= 4 NCHW maps f_l
+ *   [B,C_l,H_l,W_l] at the grid of gcn.py:141-153 (per-sample min / max of z and y, bounds [B,4]); global [B,G] repeated
+ *   (G may be 0).  Writes ext [B,4] (zmin, zmax, ymin, ymax), ext_idx [B,4] (their first vertex), grid [B,N,2] and the
+ *   NHWC copy of the maps in maps_ws (vpn_gcn_maps_workspace bytes); the backward reads all four.  With L = 0 bounds,
+ *   ext, ext_idx, grid and maps_ws may be NULL.  zmax == zmin or ymax == ymin divides by zero, as the reference does.
+ * vpn_gcn_input_bwd: from grad [B,N,ctot]: grad_verts [B,N,3] (NULL: skipped) through the encoding, the grid and the
+ *   min / max (to the first arg-extreme vertex), and the map gradients gf_l [B,C_l,H_l,W_l] (all NULL: skipped), summed
+ *   per pixel over the vertices sorted by bilinear cell: deterministic, no atomics; N <= 8192 then.  The gradient of the
+ *   global block is a column sum (vpn_gcn_colsum).  workspace: vpn_gcn_input_bwd_workspace bytes. */
+int vpn_gcn_aggregate(const float* x, const int32_t* row_ptr, const int32_t* col, const float* w, const float* bias,
+                      const float* mask, int B, int N, int C, int relu, float* out, void* stream);
+size_t vpn_gcn_colsum_workspace(int S, int R, int C);
+int vpn_gcn_colsum(const float* in, const float* mask, int S, int R, int ld, int off, int C, void* workspace, float* out,
+                   void* stream);
+int vpn_gcn_bounds(const float* img, int B, int C, int H, int W, float* bounds, void* stream);
+size_t vpn_gcn_maps_workspace(int B, int L, int C0, int H0, int W0, int C1, int H1, int W1, int C2, int H2, int W2,
+                              int C3, int H3, int W3);
+int vpn_gcn_input_fwd(const float* verts, const float* bounds, const float* global_features, int B, int N, int G,
+                      int venc, int L, const float* f0, const float* f1, const float* f2, const float* f3, int C0,
+                      int H0, int W0, int C1, int H1, int W1, int C2, int H2, int W2, int C3, int H3, int W3,
+                      float* ext, int32_t* ext_idx, float* grid, void* maps_ws, float* out, void* stream);
+size_t vpn_gcn_input_bwd_workspace(int B, int N, int L, int C0, int H0, int W0, int C1, int H1, int W1, int C2, int H2,
+                                   int W2, int C3, int H3, int W3);
+int vpn_gcn_input_bwd(const float* grad, const float* verts, const float* bounds, int B, int N, int G, int venc, int L,
+                      int C0, int H0, int W0, int C1, int H1, int W1, int C2, int H2, int W2, int C3, int H3, int W3,
+                      const float* ext, const int32_t* ext_idx, const float* grid, const void* maps_ws,
+                      void* workspace, float* grad_verts, float* gf0, float* gf1, float* gf2, float* gf3,
+                      void* stream);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,6 @@ from .loss import ChamferDistanceLoss, EarthMoverDistanceLoss, SilhouetteLoss, V
 from .render import VertexRenderer
 from .transform import (transform_points, rotate_points, translate_points, view_to_obj_points,
                         obj_to_view_points, rotate_points_forward_x_axis)
-from .network import pack_head_outputs, split_primitives
+from .network import pack_head_outputs, split_primitives, GCNModel, GCNConv
 from .meshing import Meshing, TriangleMesh, load_obj
 from .dataset import parse_split_csv, parse_rendering_metadata, split_rgba

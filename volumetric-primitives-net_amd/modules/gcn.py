@@ -1,0 +1,138 @@
+"""GCNModel of the reference (modules/network/gcn.py): the VPN + GCN refinement stage of train_gcn.py / test_gcn.py.
+
+torch_geometric and kaolin are absent, so their two pieces are restated here: GCNConv (PyG's default: self loops,
+symmetric normalisation, bias) and the unique mesh edges of `compute_adjacency_info`.  The dense GEMMs (x Theta and the
+fc stack) stay torch.matmul / nn.Linear; everything around them runs on the HIP kernels of csrc/gcn.hip:
+graph aggregation (+ bias, + ReLU), image bounds, positional encoding, perceptual feature pooling and their backward.
+
+Degenerate clouds (zmax == zmin or ymax == ymin within a sample) divide by zero in the reference's grid; they do here
+as well and are not supported."""
+import math
+
+import torch
+import torch.nn as nn
+
+from ..ops import GcnAggregateFunction, GcnInputFunction, gcn_bounds, gcn_edges, gcn_edge_index, gcn_graph
+
+
+class GCNConv(nn.Module):
+    """PyG's GCNConv(in_channels, out_channels) with its defaults (add_self_loops, normalize, bias, no cached edge
+    weights): forward(x [B,N,in], graph) = A_hat (x Theta) + b, A_hat = D^-1/2 (A + I) D^-1/2 (ops.gcn_normalized_adjacency).
+    Glorot-uniform Theta, zero bias, as PyG initialises them.
+
+    Parameters: `weight` (in, out) and `bias` (out,), the PyG 1.x layout, which state_dict() saves.  load_state_dict also
+    takes the PyG >= 2 layout, `lin.weight` (out, in) + `bias`, and transposes it."""
+
+    def __init__(self, in_channels, out_channels):
+        super().__init__()
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.weight = nn.Parameter(torch.empty(in_channels, out_channels))
+        self.bias = nn.Parameter(torch.empty(out_channels))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        a = math.sqrt(6.0 / (self.in_channels + self.out_channels))          # torch_geometric.nn.inits.glorot
+        with torch.no_grad():
+            self.weight.uniform_(-a, a)
+            self.bias.zero_()
+
+    def forward(self, x, graph, relu=False):
+        """x [B,N,in] -> [B,N,out]; relu=True applies the ReLU that follows the layer in GCNModel (fused)."""
+        return GcnAggregateFunction.apply(torch.matmul(x, self.weight), self.bias, graph.row_ptr, graph.col, graph.w, relu)
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        lin = prefix + 'lin.weight'
+        if lin in state_dict and prefix + 'weight' not in state_dict:
+            state_dict[prefix + 'weight'] = state_dict.pop(lin).t().contiguous()
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                                      error_msgs)
+
+    def extra_repr(self):
+        return '%d, %d' % (self.in_channels, self.out_channels)
+
+
+def to_pyg2_state_dict(state_dict):
+    """A GCNModel / GCNConv state dict in the PyG >= 2 layout (`convK.lin.weight` (out, in)); the inverse of what
+    load_state_dict does with such a dict."""
+    out = {}
+    for k, v in state_dict.items():
+        if k.endswith('.weight') and k.split('.')[-2].startswith('conv') and v.dim() == 2:
+            out[k[:-len('weight')] + 'lin.weight'] = v.t().contiguous()
+        else:
+            out[k] = v
+    return out
+
+
+class GCNModel(nn.Module):
+    """gcn.py:7-58: same constructor, forward, layers (conv1..conv6, fc) and output
+    predict_vertices [B,N,3] = vertices + 0.1 * fc(conv stack).  The graph of meshes[0]'s faces is built once per face
+    topology (ops.gcn_graph) and the image bounds are computed on the device: a step makes no host synchronisation."""
+
+    def __init__(self, n_dim=3, img_feature_dim=960 + 512, v_num=2048, use_position_encoding=True):
+        super().__init__()
+        conv = GCNConv
+        self.use_position_encoding = use_position_encoding
+        self.relu = nn.ReLU()
+        n_dim = n_dim + n_dim * 12 if use_position_encoding else n_dim
+        self.venc = n_dim
+        self.conv1 = conv(n_dim + img_feature_dim, 512)
+        self.conv2 = conv(512, 512)
+        self.conv3 = conv(512, 512)
+        self.conv4 = conv(512, 512)
+        self.conv5 = conv(512, 64)
+        self.conv6 = conv(64, 3)
+        self.fc = nn.Sequential(
+            nn.Linear(v_num * 3, 1024),
+            nn.Linear(1024, 1024),
+            nn.Linear(1024, v_num * 3),
+            nn.Tanh()
+        )
+
+    def forward(self, meshes: list, rgbs: torch.Tensor, perceptual_features: list, global_features: torch.Tensor = None):
+        batch_vertices = self.get_batch_vertices(meshes)                                  # (B, N, 3)
+        graph = gcn_graph(meshes[0].faces, batch_vertices.size(1), batch_vertices.device)
+        if self.venc not in (0, 3, 39):
+            raise ValueError('GCNModel: the vertex encoding has %d channels; the kernels take 3 (n_dim = 3)' % self.venc)
+        bounds = gcn_bounds(rgbs)
+        x = GcnInputFunction.apply(batch_vertices, bounds, global_features, self.venc, *perceptual_features)
+        x = self.conv1(x, graph)
+        x = self.conv2(x, graph, relu=True)
+        x = self.conv3(x, graph)
+        x = self.conv4(x, graph, relu=True)
+        x = self.conv5(x, graph)
+        x = self.conv6(x, graph, relu=True)
+        x = x.reshape(x.size(0), -1)
+        deformations = self.fc(x).view(x.size(0), -1, 3) * 0.1
+        return batch_vertices + deformations
+
+    @staticmethod
+    def get_edge_indices(mesh):
+        """(2, 2E) int64 edge index of the unique undirected edges of mesh.faces, both directions, laid out as
+        gcn.py:63-67 lays them out (column 2m = (a_m, b_m), 2m + 1 = (b_m, a_m), edges sorted by (a, b), a < b)."""
+        return gcn_edge_index(gcn_edges(mesh.faces)).to(mesh.faces.device)
+
+    @staticmethod
+    def get_batch_vertices(meshes: list):
+        return torch.cat([mesh.vertices[None] for mesh in meshes])
+
+    @staticmethod
+    def positional_encoding(x: torch.Tensor):
+        """[x, sin(x), cos(x), sin(2x), cos(2x), ..., sin(32x), cos(32x)] along the last axis (gcn.py:73-82), x [..., 3]."""
+        flat = x.reshape(1, -1, 3)
+        return GcnInputFunction.apply(flat, None, None, 39).reshape(*x.shape[:-1], 39)
+
+    @classmethod
+    def get_local_features(cls, vertices: torch.Tensor, rgbs: torch.Tensor, perceptual_features: list):
+        bounds = cls.get_bound_of_images(rgbs)
+        return cls.perceptual_feature_pooling(perceptual_features, vertices, bounds)
+
+    @staticmethod
+    def get_bound_of_images(imgs: torch.Tensor):
+        assert imgs.ndimension() == 4
+        return gcn_bounds(imgs)
+
+    @staticmethod
+    def perceptual_feature_pooling(perceptual_features: list, points: torch.Tensor, bounds: torch.Tensor):
+        """(B, N, sum C_l): bilinear samples (align_corners=True, zero padding) of the maps at the grid of gcn.py:141-153."""
+        assert points.ndimension() == 3 and bounds.ndimension() == 2
+        return GcnInputFunction.apply(points, bounds, None, 0, *perceptual_features)

@@ -190,7 +190,7 @@ class Meshing:
     def mesh_primitives(cls, params, kinds):
         """All K primitives of all B samples in one launch: params (B,K,10), kinds list ->
         vertices (B, P_total, 3) (differentiable) and the faces (F_total, 3) of the composed mesh."""
-        from ..ops import kinds_host
+        from ..ops import kinds_host, faces_fingerprint, faces_remember
         kinds = tuple(int(k) for k in (kinds_host(kinds) if isinstance(kinds, torch.Tensor) and kinds.is_cuda else
                                        (kinds.tolist() if isinstance(kinds, torch.Tensor) else kinds)))
         dev = params.device
@@ -204,7 +204,10 @@ class Meshing:
                 v, f = tpl[k]
                 faces.append(f + offsets[-1])                   # meshing.py:38-39
                 offsets.append(offsets[-1] + v.shape[0])
-            cls._layouts[key] = (torch.tensor(offsets, dtype=torch.int32, device=dev), torch.cat(faces), offsets[-1])
+            composed = torch.cat(faces)
+            # content key of the composed faces, hashed once here so that no later user pays a device read for it
+            faces_remember(composed, faces_fingerprint(composed.cpu()))
+            cls._layouts[key] = (torch.tensor(offsets, dtype=torch.int32, device=dev), composed, offsets[-1])
         off, faces, ptot = cls._layouts[key]
         verts = MeshFunction.apply(params, kinds_tensor(kinds, dev), off,
                                    tpl[SPHERE][0] if SPHERE in tpl else None, tpl[CUBOID][0] if CUBOID in tpl else None, ptot)
@@ -246,7 +249,21 @@ class Meshing:
             from ..ops import kinds_host
             kinds = [k for p in packs for k in kinds_host(p.kinds)]          # host tuples: no device round trip per mesh
             prims = PrimitivePack(torch.cat([p.params for p in packs], 1), kinds)
-        return TriangleMesh.from_tensors(vertices=torch.cat(vertices), faces=torch.cat(faces), primitives=prims)
+        faces_all = torch.cat(faces)
+        # the composed faces' content key follows from the parts' keys when those are known (no device read): the GCN's
+        # graph cache (ops.gcn_graph) then finds a re-composed mesh every step without a host synchronisation
+        from ..ops import faces_fingerprint_known, faces_remember
+        parts, n = [], 0
+        for m in meshes:
+            fp = faces_fingerprint_known(m.faces)
+            if fp is None:
+                parts = None
+                break
+            parts.append((fp, n))
+            n += m.vertices.size(0)
+        if parts is not None:
+            faces_remember(faces_all, ('composed', tuple(parts)))
+        return TriangleMesh.from_tensors(vertices=torch.cat(vertices), faces=faces_all, primitives=prims)
 
     @staticmethod
     def check_parameters(v: torch.Tensor, q: torch.Tensor, t: torch.Tensor):

@@ -1,10 +1,12 @@
 """The one piece of modules/network of the reference that sits on the hot path: the post-processing of the three
 head outputs (vpnet_one_resnet.py:34-41, :67-85; identical in vpnet_two_resnet.py and sdnet.py).  The networks
-themselves (ResNet-18 trunk, MLP heads) are out of scope."""
+themselves (ResNet-18 trunk, MLP heads) are out of scope.  GCNModel (gcn.py, the refinement stage of
+train_gcn.py / test_gcn.py) is re-exported from modules/gcn.py, so that `from modules.network import GCNModel` resolves."""
 import torch
 
 from .. import config
 from ..ops import HeadPackFunction
+from .gcn import GCNModel, GCNConv  # noqa: F401
 
 
 def pack_head_outputs(volumes: torch.Tensor, rotates: torch.Tensor, translates: torch.Tensor,

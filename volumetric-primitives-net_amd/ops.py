@@ -200,6 +200,15 @@ def faces_fingerprint(faces):
     return fp
 
 
+def faces_fingerprint_known(faces):
+    """The content key of a face tensor if it is already known (remembered for this object and version), else None;
+    never reads the device."""
+    hit = _FACES_FP.get(id(faces))
+    if hit is not None and hit[0]() is faces and hit[1] == faces._version:
+        return hit[2]
+    return None
+
+
 def faces_remember(faces, fp):
     key = id(faces)
     _FACES_FP[key] = (weakref.ref(faces, lambda _r, key=key: _FACES_FP.pop(key, None)), faces._version, fp)
@@ -970,3 +979,186 @@ class TrainStepLossFunction(Function):
                   (w_can * cd_w1 / (N * B)) if cn else 0.0, (w_can * cd_w2 / (Mc * B)) if cn else 0.0, Mc if cn else 0,
                   p(grad_params), _lib.stream())
         return (grad_params,) + (None,) * 20
+
+
+# ---- the GCN refinement stage (modules/network/gcn.py of the reference; modules/gcn.py here)
+
+class GcnGraph:
+    """The normalised mesh adjacency of PyG's GCNConv in CSR form, on one device: row_ptr [N+1] int32, col [nnz] int32,
+    w [nnz] fp32 (see gcn_normalized_adjacency), plus the (2, 2E) int64 edge index it was built from."""
+
+    def __init__(self, row_ptr, col, w, n, edge_index):
+        self.row_ptr, self.col, self.w, self.n, self.edge_index = row_ptr, col, w, n, edge_index
+
+
+def gcn_edges(faces):
+    """Unique undirected edges (E, 2) int64 (host) of a triangle list, each as (min, max), sorted lexicographically."""
+    f = faces.detach().cpu().long().reshape(-1, 3)
+    e = torch.cat([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]])
+    e = torch.stack([e.min(1)[0], e.max(1)[0]], 1)
+    e = e[e[:, 0] != e[:, 1]]
+    return torch.unique(e, dim=0)
+
+
+def gcn_edge_index(edges):
+    """(E, 2) -> (2, 2E) with both directions, as gcn.py:63-67 builds it: `torch.cat([edges, edges.flip(1)]).view(2, -1)`
+    reinterprets memory, so row 0 is edges.flatten() and row 1 is edges.flip(1).flatten(): column 2m is (a_m, b_m) and
+    column 2m + 1 is (b_m, a_m)."""
+    return torch.cat([edges, edges.flip(1)]).view(2, -1)
+
+
+def gcn_normalized_adjacency(edges, n):
+    """CSR of A_hat = D^-1/2 (A + I) D^-1/2 over n vertices, PyG GCNConv's default `gcn_norm` (Kipf & Welling, ICLR 2017,
+    eq. 2): A_ij = 1 for every undirected edge (both directions), self loops added with weight 1, the degree counted with
+    the self loop (deg_i = 1 + number of neighbours), no edge weights, fp32 deg^-1/2 and fp32 products
+    w_ij = deg_i^-1/2 * deg_j^-1/2.  Entries of a row are sorted by column (the self loop among them).  Host tensors:
+    (row_ptr [n+1] int32, col [nnz] int32, w [nnz] fp32)."""
+    e = edges.long()
+    loops = torch.arange(n, dtype=torch.long)
+    src = torch.cat([e[:, 0], e[:, 1], loops])
+    dst = torch.cat([e[:, 1], e[:, 0], loops])
+    deg = torch.zeros(n, dtype=torch.float32).index_add_(0, dst, torch.ones(dst.numel(), dtype=torch.float32))
+    dis = deg.pow(-0.5)
+    order = torch.argsort(dst * n + src)
+    row, col = dst[order], src[order]
+    w = dis[row] * dis[col]
+    row_ptr = torch.zeros(n + 1, dtype=torch.long)
+    row_ptr[1:] = torch.cumsum(torch.bincount(row, minlength=n), 0)
+    return row_ptr.int(), col.int(), w.float()
+
+
+_GCN_GRAPHS = {}
+
+
+def gcn_graph(faces, n, device):
+    """The GcnGraph of a face topology over n vertices on `device`, built on the host once per (face content, n, device)
+    (keyed by ops.faces_fingerprint, like the face cache): a repeated step does no host work and no synchronisation."""
+    key = (faces_fingerprint(faces), int(n), str(torch.device(device)))
+    hit = _GCN_GRAPHS.get(key)
+    if hit is None:
+        if len(_GCN_GRAPHS) > 64:
+            _GCN_GRAPHS.clear()
+        edges = gcn_edges(faces)
+        if edges.numel() and int(edges.max()) >= n:
+            raise ValueError('faces index vertex %d of a %d-vertex mesh' % (int(edges.max()), n))
+        rp, col, w = gcn_normalized_adjacency(edges, int(n))
+        hit = GcnGraph(rp.to(device), col.to(device), w.to(device), int(n), gcn_edge_index(edges).to(device))
+        _GCN_GRAPHS[key] = hit
+    return hit
+
+
+def _colsum(x, mask, S, R, ld, off, C):
+    ws = torch.empty((_lib.lib().vpn_gcn_colsum_workspace(S, R, C) // 4,), dtype=torch.float32, device=x.device)
+    out = torch.empty((S, C), dtype=torch.float32, device=x.device)
+    _lib.call('vpn_gcn_colsum', _lib.ptr(x), _lib.ptr(mask), S, R, ld, off, C, _lib.ptr(ws), _lib.ptr(out), _lib.stream())
+    return out
+
+
+class GcnAggregateFunction(Function):
+    """y [B,N,C] = A_hat h [B,N,C] + bias [C] (ReLU'd when relu): the propagation of GCNConv over a GcnGraph.  Backward:
+    A_hat is symmetric, so dh = A_hat (g * [y > 0]) by the same gather; dbias = sum over (b, i) in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, h, bias, row_ptr, col, w, relu=False):
+        h = _f32c(h)
+        B, N, C = h.shape
+        assert row_ptr.numel() == N + 1, 'graph has %d vertices, features %d' % (row_ptr.numel() - 1, N)
+        b = _f32c(bias) if bias is not None else None
+        y = torch.empty_like(h)
+        _lib.call('vpn_gcn_aggregate', _lib.ptr(h), _lib.ptr(row_ptr), _lib.ptr(col), _lib.ptr(w), _lib.ptr(b), None, B, N, C,
+                  int(bool(relu)), _lib.ptr(y), _lib.stream())
+        ctx.save_for_backward(row_ptr, col, w, y if relu else None)
+        ctx.meta = (B, N, C, bias is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        row_ptr, col, w, y = ctx.saved_tensors
+        B, N, C, has_bias = ctx.meta
+        g = _f32c(g)
+        gh = gb = None
+        if ctx.needs_input_grad[0]:
+            gh = torch.empty_like(g)
+            _lib.call('vpn_gcn_aggregate', _lib.ptr(g), _lib.ptr(row_ptr), _lib.ptr(col), _lib.ptr(w), None, _lib.ptr(y),
+                      B, N, C, 0, _lib.ptr(gh), _lib.stream())
+        if has_bias and ctx.needs_input_grad[1]:
+            gb = _colsum(g, y, 1, B * N, C, 0, C).reshape(C)
+        return gh, gb, None, None, None, None
+
+
+def gcn_bounds(rgbs):
+    """get_bound_of_images (gcn.py:90-133) on the device: rgbs [B,C,H,W] -> bounds [B,4] fp32, bit-exact, no host sync.
+    Not differentiable (the reference's bounds are integers written into a fresh tensor)."""
+    img = _f32c(rgbs.detach())
+    assert img.dim() == 4
+    B, C, H, W = img.shape
+    out = torch.empty((B, 4), dtype=torch.float32, device=img.device)
+    _lib.call('vpn_gcn_bounds', _lib.ptr(img), B, C, H, W, _lib.ptr(out), _lib.stream())
+    return out
+
+
+def _gcn_dims(maps):
+    dims = []
+    for m in maps:
+        dims += [int(m.shape[1]), int(m.shape[2]), int(m.shape[3])]
+    return dims + [0] * (12 - len(dims))
+
+
+class GcnInputFunction(Function):
+    """conv1's input [B,N,venc + sum C_l + G] = [encoding | pooled | global] (gcn.py:36-42) in one pass, no torch.cat:
+    venc = 39 (positional encoding, gcn.py:73-82), 3 (the vertices) or 0; pooled = perceptual_feature_pooling
+    (gcn.py:135-164) of the L <= 4 NCHW maps at the grid given by bounds [B,4] and the per-sample z / y extents of
+    verts [B,N,3]; global_features [B,G] (or None) repeated over the vertices.  Differentiable w.r.t. verts (through
+    the encoding, the grid and the min / max), the maps and the global features."""
+
+    @staticmethod
+    def forward(ctx, verts, bounds, global_features, venc, *maps):
+        verts = _f32c(verts)
+        B, N, _ = verts.shape
+        L = len(maps)
+        assert L <= 4 and verts.shape[2] == 3
+        maps = tuple(_f32c(m) for m in maps)
+        for m in maps:
+            assert m.dim() == 4 and m.shape[0] == B, m.shape
+        gf = _f32c(global_features) if global_features is not None else None
+        G = int(gf.shape[1]) if gf is not None else 0
+        dev = verts.device
+        dims = _gcn_dims(maps)
+        ctot = int(venc) + sum(int(m.shape[1]) for m in maps) + G
+        out = torch.empty((B, N, ctot), dtype=torch.float32, device=dev)
+        ext = ext_idx = grid = mws = None
+        if L:
+            bounds = _f32c(bounds)
+            ext = torch.empty((B, 4), dtype=torch.float32, device=dev)
+            ext_idx = torch.empty((B, 4), dtype=torch.int32, device=dev)
+            grid = torch.empty((B, N, 2), dtype=torch.float32, device=dev)
+            mws = torch.empty((_lib.lib().vpn_gcn_maps_workspace(B, L, *dims) // 4,), dtype=torch.float32, device=dev)
+        fp = [_lib.ptr(maps[l]) if l < L else None for l in range(4)]
+        _lib.call('vpn_gcn_input_fwd', _lib.ptr(verts), _lib.ptr(bounds) if L else None, _lib.ptr(gf), B, N, G, int(venc), L,
+                  *fp, *dims, _lib.ptr(ext), _lib.ptr(ext_idx), _lib.ptr(grid), _lib.ptr(mws), _lib.ptr(out), _lib.stream())
+        ctx.save_for_backward(verts, bounds if L else None, ext, ext_idx, grid, mws)
+        ctx.meta = (B, N, G, int(venc), L, dims, [tuple(m.shape) for m in maps])
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        verts, bounds, ext, ext_idx, grid, mws = ctx.saved_tensors
+        B, N, G, venc, L, dims, shapes = ctx.meta
+        g = _f32c(g)
+        dev = g.device
+        need_v = ctx.needs_input_grad[0]
+        need_m = any(ctx.needs_input_grad[4:4 + L])
+        gv = torch.empty((B, N, 3), dtype=torch.float32, device=dev) if need_v else None
+        gm = [torch.empty(s, dtype=torch.float32, device=dev) for s in shapes] if need_m else []
+        if need_v or need_m:
+            ws = torch.empty((max(_lib.lib().vpn_gcn_input_bwd_workspace(B, N, L, *dims), 4) // 4,), dtype=torch.float32,
+                             device=dev)
+            fp = [_lib.ptr(gm[l]) if l < len(gm) else None for l in range(4)]
+            _lib.call('vpn_gcn_input_bwd', _lib.ptr(g), _lib.ptr(verts), _lib.ptr(bounds), B, N, G, venc, L, *dims,
+                      _lib.ptr(ext), _lib.ptr(ext_idx), _lib.ptr(grid), _lib.ptr(mws), _lib.ptr(ws), _lib.ptr(gv), *fp,
+                      _lib.stream())
+        gg = None
+        if G and ctx.needs_input_grad[2]:
+            ctot = g.shape[2]
+            gg = _colsum(g, None, B, N, ctot, ctot - G, G)
+        return (gv, None, gg, None) + (tuple(gm) if need_m else (None,) * L)
