@@ -7,13 +7,17 @@ Workloads (config.workload):
   c3 (default, the headline): BASELINE configs[2]: B=64 per GPU, K=32 sphere primitives, 256x256, n=256 points per
      primitive (N=8192) vs M=2048 GT points.  With --global-batch G the batch is split G/N per rank (BASELINE
      configs[3] = C4: G=256, strong scaling) instead of 64 per rank (weak scaling).
-  c2: BASELINE configs[1]: K=16, 128x128 silhouette+depth, B=32, raster fwd/bwd only.  The default
-     run also measures it and reports it under the key "c2" next to the C3 headline.
+  c2: BASELINE configs[1]: K=16, 128x128 silhouette+depth, B=32, raster fwd/bwd only.  A --full run
+     of c3 also measures it and reports it under the key "c2" next to the C3 headline.
 
     python bench.py [--gpus N --steps K --warmup W] [--workload c2] [--global-batch 256] [--collective allreduce]
     python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR     # also writes the last timed step's outputs
+    python bench.py --full ...                                           # the headline and everything measured next to it
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline`.
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run sets up, warms up, times the steps, writes
+--dump-outputs and prints the headline (metric, value, unit, ms_per_step, dtype, config, ...).  Everything else -- hipEvent
+windows, steady state, per-kernel times and rooflines, the multi-rank `dist` record, the CPU baseline and the parity
+legs against the oracle, the C2 / C5 / EMD / primitive-kind side workloads -- runs only with --full.
 """
 import argparse
 import json
@@ -116,9 +120,9 @@ def traffic_of(name, pmc):
     return int((k['FETCH_SIZE'] * mul + k['WRITE_SIZE']) * 1024)
 
 
-def raster_only(vpn_amd, _lib, dev, B, K, H, steps, warmup, windows, pmc_key, use_graph=True):
+def raster_only(vpn_amd, _lib, dev, B, K, H, steps, warmup, windows, pmc_key, use_graph=True, full=True):
     """C2: vpn_raster_loss_fwd + vpn_raster_loss_bwd alone (render, L1 silhouette + L1 depth, gradient to (v,q,t)),
-    HIP-graph replay, hipEvent timing; per-kernel times from the library's launch profiler."""
+    HIP-graph replay, hipEvent timing; with `full`, per-kernel times from the library's launch profiler and rooflines."""
     W = H
     kinds = vpn_amd.kinds_tensor([vpn_amd.SPHERE] * K, dev)
     params, _ = synth_inputs(B, K, 8, 1234, dev)
@@ -155,6 +159,12 @@ def raster_only(vpn_amd, _lib, dev, B, K, H, steps, warmup, windows, pmc_key, us
         run()
     torch.cuda.synchronize()
     ev = event_windows(run, steps, windows)
+    ms = ev['median']
+    res = {'workload': 'C2: B=%d, K=%d sphere primitives, %dx%d silhouette+depth, raster fwd+bwd only '
+                       '(vpn_raster_total_fwd/bwd: render + L1(sil) + L1(depth) + gradient to (v,q,t))' % (B, K, H, W),
+           'images_per_s': round(B / ms * 1e3, 1), 'ms_per_step': round(ms, 5), 'timing': ev}
+    if not full:
+        return res
     ksteps = 20
     with _lib.KernelProfile() as kp:
         for _ in range(ksteps):
@@ -173,12 +183,9 @@ def raster_only(vpn_amd, _lib, dev, B, K, H, steps, warmup, windows, pmc_key, us
                       'hbm': {'bound': 'hbm', 'achieved': round(gbs, 2), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                               'frac': round(gbs / HBM_PEAK_GBS, 5), 'traffic': traffic_of(name, pmc)},
                       'executed_work': valu_issue_roofline(name, pmc, us)}
-    ms = ev['median']
-    return {'workload': 'C2: B=%d, K=%d sphere primitives, %dx%d silhouette+depth, raster fwd+bwd only '
-                        '(vpn_raster_total_fwd/bwd: render + L1(sil) + L1(depth) + gradient to (v,q,t))' % (B, K, H, W),
-            'images_per_s': round(B / ms * 1e3, 1), 'ms_per_step': round(ms, 5), 'timing': ev,
-            'algorithmic_bytes_per_image': (fwd_b + bwd_b) // B, 'kernel_us': kernel_us, 'roofline': roof,
-            'pmc_source': os.path.relpath(PMC_FILE, ROOT) if pmc else None}
+    res.update({'algorithmic_bytes_per_image': (fwd_b + bwd_b) // B, 'kernel_us': kernel_us, 'roofline': roof,
+                'pmc_source': os.path.relpath(PMC_FILE, ROOT) if pmc else None})
+    return res
 
 
 def c5_inputs(vpn_amd, B, K, n, H, dev, gt_mode='uniform'):
@@ -222,11 +229,13 @@ C5_WEIGHTS = (1.0, 0.0, 1.0, 0.1, 1.0)      # L_VIEW_CD, L_CAN_CD, L_SIL, L_VP_D
 # silhouette term is evaluated here with weight 1; L_CAN_CD = 0 is the reference's value: that Chamfer is computed and weighted 0)
 
 
-def train_step_block(vpn_amd, _lib, dev, B, K, n, H, steps, warmup, windows, form, with_oracle, gt_mode='uniform', use_graph=True):
+def train_step_block(vpn_amd, _lib, dev, B, K, n, H, steps, warmup, windows, form, with_oracle, gt_mode='uniform', use_graph=True,
+                     full=True):
     """The step train.py:243-262 runs: sampler -> view-centred Chamfer + object-centred Chamfer through view_to_obj_points
     + silhouette loss + VP-diversity loss + EMD (eps 0.005, 50 rounds) -> weighted total -> backward to d/d(v,q,t).
     form 'modules': the drop-in module surface called the way train.py calls it (one autograd node per reference call);
-    form 'fused': one autograd node, no ATen kernel inside the step (TrainStepLossFunction)."""
+    form 'fused': one autograd node, no ATen kernel inside the step (TrainStepLossFunction).
+    With `full`, the losses come from a run under the library's launch profiler (`kernel_us`); without, from one step."""
     params, kinds, gt_view, gt_canon, gt_sil, dists, elevs, azims, angles = c5_inputs(vpn_amd, B, K, n, H, dev, gt_mode)
     params.requires_grad_(True)
     w = C5_WEIGHTS
@@ -284,10 +293,13 @@ def train_step_block(vpn_amd, _lib, dev, B, K, n, H, steps, warmup, windows, for
     torch.cuda.synchronize()
     ev = event_windows(run, steps, windows)
     ksteps = 10
-    with _lib.KernelProfile() as kp:
-        for i in range(ksteps):
-            out = compute(i)
-    kern = kp.summary()
+    if full:
+        with _lib.KernelProfile() as kp:
+            for i in range(ksteps):
+                out = compute(i)
+        kern = kp.summary()
+    else:
+        out = compute(0)
     ms = ev['median']
     res.update({'workload': 'train.py:243-262 step: B=%d, K=%d spheres, n=%d pts/prim (N=M=%d), %dx%d, weights (view_cd, can_cd, sil, '
                             'vp_div, emd) = %s, EMD eps=0.005 iters=50; %s' % (B, K, n, K * n, H, H, (w,),
@@ -295,9 +307,10 @@ def train_step_block(vpn_amd, _lib, dev, B, K, n, H, steps, warmup, windows, for
                              'surface': 'GT cloud on the surfaces of a target primitive set, predicted primitives = the target perturbed by 10 % (a partly converged run)'}[gt_mode]),
                 'ms_per_step': round(ms, 5), 'images_per_s': round(B / ms * 1e3, 1), 'timing': ev,
                 'losses': dict(zip(('view_cd', 'obj_cd', 'sil', 'vp_div', 'emd', 'total'), [float(x) for x in out])),
-                'finite_grad': bool(torch.isfinite(params.grad).all()),
-                'kernel_us': {k: {'calls_per_step': round(v[0] / ksteps, 2), 'avg_us': round(v[1] * 1e3, 2)} for k, v in kern.items()},
-                'kernel_us_sum_per_step': round(sum(v[0] * v[1] for v in kern.values()) / ksteps * 1e3, 1)})
+                'finite_grad': bool(torch.isfinite(params.grad).all())})
+    if full:
+        res.update({'kernel_us': {k: {'calls_per_step': round(v[0] / ksteps, 2), 'avg_us': round(v[1] * 1e3, 2)} for k, v in kern.items()},
+                    'kernel_us_sum_per_step': round(sum(v[0] * v[1] for v in kern.values()) / ksteps * 1e3, 1)})
     if with_oracle:
         res['parity_vs_oracle'] = c5_parity(vpn_amd, params.detach(), kinds, gt_view, gt_canon, gt_sil, dists, elevs, azims, angles, K, n, H, w)
     return res, (params, kinds, gt_view, gt_canon, gt_sil, dists, elevs, azims, angles)
@@ -365,12 +378,16 @@ def main():
     ap.add_argument('--collective', choices=['allreduce', 'allgather'], default='allreduce',
                     help='the one gradient exchange per step when N>1 (north_star: RCCL all-reduce)')
     ap.add_argument('--windows', type=int, default=5, help='hipEvent windows of --steps replays each (median reported)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also measure and check everything reported next to it (hipEvent windows, '
+                         'steady state, per-kernel times and rooflines, CPU baseline, parity with the oracle, side workloads)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline and the oracle parity legs')
     ap.add_argument('--c5-form', choices=['modules', 'fused', 'both'], default='both')
     ap.add_argument('--c5-gt', choices=['uniform', 'surface'], default='uniform', help='GT cloud of the c5 workload (see c5_inputs)')
-    ap.add_argument('--no-c5', action='store_true', help='skip the C5 train-step measurement of the default run')
-    ap.add_argument('--no-c2', action='store_true', help='skip the C2 raster-only measurement of the default run')
-    ap.add_argument('--no-extras', action='store_true', help='skip C2, EMD and the CPU baseline (profiling runs)')
+    ap.add_argument('--no-c5', action='store_true', help='--full: skip the C5 train-step measurement')
+    ap.add_argument('--no-c2', action='store_true', help='--full: skip the C2 raster-only measurement')
+    ap.add_argument('--no-extras', action='store_true', help='--full: skip C2, C5, EMD, the primitive-kind variants and the CPU '
+                                                             'baseline (profiling runs)')
     ap.add_argument('--no-graph', action='store_true', help='launch every step eagerly instead of replaying a HIP graph')
     ap.add_argument('--dist-selftest', action='store_true',
                     help='run the multi-rank code path (RCCL group, gradient collective) even with one rank')
@@ -421,17 +438,18 @@ def main():
     if args.workload == 'c2':
         B = args.batch or 32
         res = raster_only(vpn_amd, _lib, dev, B, args.prims or 16, args.size or 128, args.steps, args.warmup,
-                          args.windows, 'c2', not args.no_graph)
+                          args.windows, 'c2', not args.no_graph, args.full)
         if rank == 0:
-            domk = max(res['roofline'], key=lambda k: res['roofline'][k]['avg_launch_us'])
-            dom = res['roofline'][domk]
             out = {'metric': 'raster fwd+bwd images/sec (BASELINE config C2)', 'value': res['images_per_s'],
                    'unit': 'images/s', 'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup,
                    'ms_per_step': res['ms_per_step'], 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
                    'dtype': 'f32', 'data': 'synthetic', 'launch': 'eager' if args.no_graph else 'hip-graph replay',
-                   'config': {'workload': res['workload'], 'global_batch': B, 'parallelism': 'dp1'},
-                   'roofline': dict(dom.get('hbm', {}), kernel=domk, executed_work=dom.get('executed_work')),
-                   'c2': res}
+                   'config': {'workload': res['workload'], 'global_batch': B, 'parallelism': 'dp1'}}
+            if args.full:
+                domk = max(res['roofline'], key=lambda k: res['roofline'][k]['avg_launch_us'])
+                dom = res['roofline'][domk]
+                out['roofline'] = dict(dom.get('hbm', {}), kernel=domk, executed_work=dom.get('executed_work'))
+            out['c2'] = res
             print(json.dumps(out), flush=True)
         if multi:
             dist.destroy_process_group()
@@ -440,8 +458,8 @@ def main():
     if args.workload == 'c5':
         forms = [args.c5_form] if args.c5_form != 'both' else ['modules', 'fused']
         res = {f: train_step_block(vpn_amd, _lib, dev, args.batch or 64, args.prims or 64, args.points if args.points != 256 else 32,
-                                   args.size or 256, args.steps, args.warmup, args.windows, f, f == 'fused' and not args.no_cpu_baseline,
-                                   args.c5_gt, not args.no_graph)[0]
+                                   args.size or 256, args.steps, args.warmup, args.windows, f,
+                                   args.full and f == 'fused' and not args.no_cpu_baseline, args.c5_gt, not args.no_graph, args.full)[0]
                for f in forms}
         if rank == 0:
             best = min(res.values(), key=lambda r: r['ms_per_step'])
@@ -573,6 +591,40 @@ def main():
         dt = float(tmax)
     ms_per_step = dt / args.steps * 1e3
     value = Bg * args.steps / dt
+    is_c3 = (B, K, n, M, H) == (64, 32, 256, 2048, 256)
+
+    def headline(seed_after):
+        """The contract's line: all a plain run prints (rank 0); --full adds what it measures after the timed region."""
+        coll = 'none'
+        if multi:
+            nbytes = (Bg * K * 10 + 1) * 4 if args.collective == 'allreduce' else (B * K * 10 + 4) * 4
+            coll = '%s %s, %d B per rank per step' % ('REHEARSAL over gloo, all ranks on one GPU:' if args.rehearse else 'rccl', 'all-reduce (sum) of the global gradient buffer'
+                                                       if args.collective == 'allreduce' else 'all-gather', nbytes)
+        if args.global_batch:
+            name = 'C4' if (Bg, K, n, M, H) == (256, 32, 256, 2048, 256) else 'custom strong-scaling shape'
+        else:
+            name = 'C3' if is_c3 else 'custom shape'
+        return {
+            'metric': 'render+Chamfer fwd+bwd images/sec', 'value': round(value, 1), 'unit': 'images/s',
+            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 4),
+            'higher_is_better': True, 'scaling': scaling, 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+            'launch': 'hip-graph replay' if use_graph else 'eager',
+            'config': {'workload': '%s: B=%d/GPU (global %d), K=%d %s, %dx%d silhouette+depth, n=%d pts/prim '
+                                   '(N=%d) vs M=%d GT points, Chamfer+L1 fwd+bwd'
+                                   % (name if args.kinds == 'spheres' else name + ' variant', B, Bg, K,
+                                      {'spheres': 'sphere primitives', 'cuboids': 'cuboid primitives',
+                                       'mixed': 'primitives (%d cuboids then %d spheres)' % (K // 2, K - K // 2)}[args.kinds],
+                                      H, W, n, K * n, M),
+                       'global_batch': Bg, 'parallelism': 'dp%d' % world, 'collective': coll,
+                       'sampling': 'fresh Philox draws every step (device step counter, %d steps drawn)' % (seed_after - 1234)},
+        }
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(int(seed_buf.item()))), flush=True)
+        if multi:
+            dist.destroy_process_group()
+        return
     probe('after timed region')
     # ---- the same steps again under a HIP event pair on the launch stream: median of `windows` windows
     ev = event_windows(run_step, args.steps, args.windows)
@@ -660,7 +712,6 @@ def main():
         'chamfer_bwd_lds_kernel': B * (12 * (N + M) + 8 * (N + M) + 12 * N),
         'sample_chamfer_bwd_kernel': B * (12 * (N + M) + 8 * (N + M) + 80 * K),
     }
-    is_c3 = (B, K, n, M, H) == (64, 32, 256, 2048, 256)
     pmc = load_pmc('c3') if is_c3 else {}
     pair_flops = 8.0 * B * N * M                      # 8 flop per point pair (3 sub, 3 mul, 2 add  ==  K=4 MAC on the matrix pipe)
     dom = max((k for k in kern if k in alg_bytes), key=lambda k: kern[k][0] * kern[k][1])
@@ -756,32 +807,12 @@ def main():
         c2 = guarded(raster_only, vpn_amd, _lib, dev, 32, 16, 128, args.steps, args.warmup, args.windows, 'c2')
 
     if rank == 0:
-        coll = 'none'
-        if multi:
-            nbytes = (Bg * K * 10 + 1) * 4 if args.collective == 'allreduce' else (B * K * 10 + 4) * 4
-            coll = '%s %s, %d B per rank per step' % ('REHEARSAL over gloo, all ranks on one GPU:' if args.rehearse else 'rccl', 'all-reduce (sum) of the global gradient buffer'
-                                                       if args.collective == 'allreduce' else 'all-gather', nbytes)
-        if args.global_batch:
-            name = 'C4' if (Bg, K, n, M, H) == (256, 32, 256, 2048, 256) else 'custom strong-scaling shape'
-        else:
-            name = 'C3' if is_c3 else 'custom shape'
-        out = {
-            'metric': 'render+Chamfer fwd+bwd images/sec', 'value': round(value, 1), 'unit': 'images/s',
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 4),
-            'higher_is_better': True, 'scaling': scaling, 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-            'launch': 'hip-graph replay' if use_graph else 'eager',
-            'config': {'workload': '%s: B=%d/GPU (global %d), K=%d %s, %dx%d silhouette+depth, n=%d pts/prim '
-                                   '(N=%d) vs M=%d GT points, Chamfer+L1 fwd+bwd'
-                                   % (name if args.kinds == 'spheres' else name + ' variant', B, Bg, K,
-                                      {'spheres': 'sphere primitives', 'cuboids': 'cuboid primitives',
-                                       'mixed': 'primitives (%d cuboids then %d spheres)' % (K // 2, K - K // 2)}[args.kinds],
-                                      H, W, n, N, M),
-                       'global_batch': Bg, 'parallelism': 'dp%d' % world, 'collective': coll,
-                       'sampling': 'fresh Philox draws every step (device step counter, %d steps drawn)' % (seed_after - 1234)},
+        out = headline(seed_after)
+        out.update({
             'hip_event_ms_per_step': {k: (round(v, 5) if isinstance(v, float) else v) for k, v in ev.items()},
             'steady_state': steady,
             'roofline': roofline, 'raster_roofline': raster_roof, 'kernel_us': kernel_us, 'entry_us': entry_us,
-        }
+        })
         assert 0.0 < roofline['frac'] <= 1.0, 'roofline.frac must be a fraction: %r' % (roofline,)
         if dist_info is not None:
             out['dist'] = dist_info

@@ -1,6 +1,6 @@
 """Collect the rocprofv3 passes of tools/profile_all.sh into the files bench.py and the judge read:
 
-    python tools/pmc_collect.py <tag> [gpurun_out]      ->  profiles/<tag>_pmc.json        {workload: {kernel: {counter: mean per dispatch}}}
+    python tools/pmc_collect.py <tag> <out dir>         ->  profiles/<tag>_pmc.json        {workload: {kernel: {counter: mean per dispatch}}}
                                                             profiles/<tag>_<wl>_pmc.txt    the same as text
                                                             profiles/<tag>_<wl>_kernel_stats.{csv,txt}  rocprofv3 --stats summary
 
@@ -42,7 +42,7 @@ for wl in ('c3', 'c2', 'c5'):
     if not acc:
         continue
     ker = {}
-    lines = ['# rocprofv3 --kernel-trace --pmc <counters> -- python3 bench.py --steps 10 --warmup 3 --no-extras --no-graph '
+    lines = ['# rocprofv3 --kernel-trace --pmc <counters> -- python3 bench.py --full --steps 10 --warmup 3 --no-extras --no-graph '
              '--workload %s  (separate passes, tools/profile_all.sh; mean per dispatch)' % wl]
     for k, c in sorted(acc.items()):
         if not k.startswith(('chamfer', 'raster', 'sample', 'loss_', 'emd_', 'vpdiv', 'trainstep', 'camera')):
@@ -59,7 +59,7 @@ for wl in ('c3', 'c2', 'c5'):
     if st:
         shutil.copy(st[0], os.path.join(ROOT, 'profiles', '%s_%s_kernel_stats.csv' % (tag, wl)))
         with open(os.path.join(ROOT, 'profiles', '%s_%s_kernel_stats.txt' % (tag, wl)), 'w') as fh:
-            fh.write('# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 10 --warmup 3 --no-extras --no-graph --workload %s\n' % wl)
+            fh.write('# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 10 --warmup 3 --no-extras --no-graph --workload %s\n' % wl)
             for r in list(csv.DictReader(open(st[0])))[:16]:
                 fh.write('%-72s calls=%-5s avg_us=%9.2f min=%9.2f max=%9.2f pct=%s\n' % (
                     r['Name'][:72], r['Calls'], float(r['AverageNs']) / 1e3, float(r['MinNs']) / 1e3,

@@ -1,15 +1,16 @@
 #!/bin/bash
-# usage: tools/profile_all.sh <tag>    (GPU box, repo root)
+# usage: tools/profile_all.sh <tag> <out dir>    (GPU box)
 # One kernel-trace + stats pass and the PMC passes (separate runs, --kernel-trace only beside --pmc) of bench.py for
-# the C3 headline workload, the C2 raster-only workload and the C5 training step (fused node).  Output: gpurun_out/<tag>_{c3,c2}_{stats,pmcN}/ ;
-# tools/pmc_collect.py turns them into profiles/<tag>_pmc.json + text summaries.
+# the C3 headline workload, the C2 raster-only workload and the C5 training step (fused node).  Output: <out dir>/<tag>_{c3,c2,c5}_{stats,pmcN}/ ;
+# tools/pmc_collect.py <tag> <out dir> turns them into profiles/<tag>_pmc.json + text summaries.
 tag=$1
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
+out=$(mkdir -p "$2" && cd "$2" && pwd)
 cd /tmp && export TMPDIR=/tmp
 run() {   # name, bench args..., then `--` and rocprof args
   local name=$1; shift
   local bargs=(); while [ "$1" != "--" ]; do bargs+=("$1"); shift; done; shift
-  rocprofv3 "$@" --output-format csv -d $R/gpurun_out/${tag}_$name -- python3 $R/bench.py --steps 10 --warmup 3 --no-extras --no-graph "${bargs[@]}" > $R/gpurun_out/${tag}_$name.log 2>&1
+  rocprofv3 "$@" --output-format csv -d $out/${tag}_$name -- python3 $R/bench.py --full --steps 10 --warmup 3 --no-extras --no-graph "${bargs[@]}" > $out/${tag}_$name.log 2>&1
   echo "${tag}_$name rc=$?"
 }
 for wl in c3 c2 c5; do
