@@ -87,6 +87,20 @@ def make_batch(B, K, sample_num, size, dev, seed=0):
     return feats, gt_points, gt_sil, dists, elevs, azims, torch.zeros(B, device=dev), kinds
 
 
+def augment_batch(batch, which, it):
+    """train.py:232-237 on the HIP augmentation stage, in the reference's order.  The stand-in network reads features, not
+    pixels, so the mixed rgbs (here: the silhouette repeated over three channels) have no consumer; the mix-up moves the
+    points only -- re-meshing and re-rendering them (the rest of point_mixup_data) is host-side mesh processing."""
+    feats, gt_points, gt_sil, dists, elevs, azims, angles, kinds = batch
+    if 'rotate' in which:
+        gt_points = vpn_amd.rotate_points_forward_x_axis(gt_points, angles)
+    if 'cutmix' in which:
+        _, gt_sil, gt_points = vpn_amd.cut_mix_data(gt_sil.expand(-1, 3, -1, -1), gt_sil, gt_points, seed=2000 + it)
+    if 'mixup' in which:
+        gt_points = vpn_amd.mixup_points(gt_points)
+    return feats, gt_points, gt_sil, dists, elevs, azims, angles, kinds
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=20)
@@ -95,7 +109,10 @@ def main():
     ap.add_argument('--sample-num', type=int, default=128)   # config.py:8
     ap.add_argument('--size', type=int, default=128)         # config.py:49
     ap.add_argument('--fused', action='store_true', help='the whole loss as one autograd node (TrainStepLossFunction)')
+    ap.add_argument('--augment', default='', help='comma-separated subset of rotate,cutmix,mixup (config.py AUGMENT_3D; default: none)')
     args = ap.parse_args()
+    augment = [a for a in args.augment.split(',') if a]
+    assert set(augment) <= {'rotate', 'cutmix', 'mixup'}, augment
     losses = training_losses_fused if args.fused else training_losses
     dev = torch.device('cuda')
     torch.manual_seed(1234)
@@ -105,7 +122,8 @@ def main():
     weights = (1.0, 1.0, 1.0, 0.1, 1.0)
     for it in range(args.steps):
         opt.zero_grad()
-        total, parts = losses(net, *batch, args.sample_num, weights, seed=1000 + it)
+        total, parts = losses(net, *(augment_batch(batch, augment, it) if augment else batch), args.sample_num, weights,
+                              seed=1000 + it)
         total.backward()
         opt.step()
         print('step %3d  total %.5f  ' % (it, float(total.detach())) + '  '.join('%s %.5f' % (k, float(v.detach())) for k, v in parts.items()),

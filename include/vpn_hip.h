@@ -34,12 +34,12 @@
 extern "C" {
 #endif
 
-/* 7: the GCN refinement stage (vpn_gcn_*).  6: vpn_emd_fwd_ex, vpn_emd_recovered_samples, vpn_emd_last_group.
+/* 8: the batch augmentation stage (vpn_cutmix_*, vpn_mixup_*).  7: the GCN refinement stage (vpn_gcn_*).  6: vpn_emd_fwd_ex, vpn_emd_recovered_samples, vpn_emd_last_group.
  * 5 (round 4): vpn_vpdiv_fwd, vpn_camera_matrix, vpn_trainstep_finalize, vpn_trainstep_bwd (the reference's whole training
  * step in one autograd node).  4 (round 3): raster records are 16 float4 per primitive (vpn_raster_records_size grew), tile_order is a buffer of
  * 48-byte tile entries (vpn_raster_order_size, K <= 64).  3: vpn_raster_total_fwd_fin, vpn_hotpath_chamfer_fwd, the mesh
  * entry points. */
-#define VPN_ABI_VERSION 7
+#define VPN_ABI_VERSION 8
 
 /* primitive kinds (reference: train.py:106-116 cuboids first, then spheres, cones are stubs) */
 #define VPN_SPHERE 0
@@ -54,6 +54,8 @@ extern "C" {
 #define VPN_PARAM_STRIDE 10
 /* largest K the raster / sampler stage in LDS */
 #define VPN_MAX_PRIMS 1024
+/* largest cloud vpn_cutmix_points takes: the 2 N candidate keys of a sample live in one workgroup's LDS */
+#define VPN_CUTMIX_MAX_POINTS 8192
 
 int vpn_abi_version(void);
 /* static description of a code returned by any entry point below */
@@ -494,6 +496,40 @@ int vpn_gcn_input_bwd(const float* grad, const float* verts, const float* bounds
                       const float* ext, const int32_t* ext_idx, const float* grid, const void* maps_ws,
                       void* workspace, float* grad_verts, float* gf0, float* gf1, float* gf2, float* gf3,
                       void* stream);
+
+/* ---- the batch augmentation stage (train.py:232-237): CutMix and the point mix-up.  Outputs are data: no backward.
+ * vpn_cutmix_points: cut_mix_batch_points + adjust_point_num (modules/augmentation/cutmix.py:24-50).  points [B,N,3];
+ *   indices [B] = the partner of each sample (NULL: every sample is its own partner; a value outside [0,B) is read as
+ *   the sample itself); the cut is cut_per_sample[b] when that pointer is not NULL, else `cut`.  The 2 N candidates of
+ *   sample b are numbered 0..N-1 (its own points) and N..2N-1 (its partner's); the eligible list is the reference's
+ *   cat([own[z >= cut], partner[z < cut]]) (cutmix.py:32) in that order.  out [B,n_out,3], src [B,n_out], count [B]:
+ *     count == n_out: the eligible list in order;
+ *     count >  n_out: n_out distinct members, every n_out-subset equally likely (randperm(count)[:n_out], :46), in the
+ *                     order of the draw;
+ *     0 < count < n_out: n_out independent uniform draws (randint(0, count, (n_out,)), :49);
+ *     count == 0: src[b,i] = i mod N, the sample's own points.  THE ONE DEVIATION: the reference raises here (randint(0, 0):
+ *                 "from >= to"), which needs a host synchronisation; count[b] = 0 tells the caller instead.
+ *   out[b,i] is candidate src[b,i] bit for bit.  The reference passes n_out = N; adjust_point_num alone is B = 1,
+ *   indices = NULL, cut = -inf.  Draws are Philox4x32-10 words keyed on (seed, sample_base + b, slot) as the sampler's
+ *   are, so a shard of a batch draws what the whole batch would.  One workgroup per sample, vpn_cutmix_points_lds(N)
+ *   bytes of LDS; N > VPN_CUTMIX_MAX_POINTS is VPN_E_TOOBIG before anything is launched (vpn_cutmix_points_lds: 0).
+ * vpn_cutmix_images: cutmix.py:17-18 for two images in one launch: out[b,c,y,x] = x < cut_index ? img[b,c,y,x] :
+ *   img[indices[b],c,y,x] for img_a [B,Ca,H,W] and img_b [B,Cb,H,W] (Cb = 0: img_b / out_b unused), 0 <= cut_index <= W.
+ *   Out of place: out_* must not overlap img_*.  16-byte accesses when W % 4 == 0 and the four pointers are 16-byte
+ *   aligned, element-wise otherwise.
+ * vpn_mixup_gather: out [B,n,3] = points[indices[b]] (point_mixup.py:32-33, for the whole batch).
+ * vpn_mixup_lerp: out[b,i] = wa * points[b,i] + wb * partner[b, assignment[b,i]] (point_mixup.py:36-37), each product and
+ *   the sum rounded by itself; assignment [B,n] is vpn_emd_fwd's (points vs partner); an entry outside [0,n) leaves the
+ *   point where it is. */
+size_t vpn_cutmix_points_lds(int N);
+int vpn_cutmix_points(const float* points, const int32_t* indices, const float* cut_per_sample, float cut, uint64_t seed,
+                      uint64_t sample_base, int B, int N, int n_out, float* out, int32_t* src, int32_t* count,
+                      void* stream);
+int vpn_cutmix_images(const float* img_a, const float* img_b, const int32_t* indices, int B, int Ca, int Cb, int H, int W,
+                      int cut_index, float* out_a, float* out_b, void* stream);
+int vpn_mixup_gather(const float* points, const int32_t* indices, int B, int n, float* out, void* stream);
+int vpn_mixup_lerp(const float* points, const float* partner, const int32_t* assignment, int B, int n, float wa, float wb,
+                   float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,5 +11,6 @@ from .ops import (SPHERE, CUBOID, SampleFunction, TransformFunction, ChamferFunc
 from .primitives import PrimitivePack, pack_primitives, kinds_from_counts
 from .modules import (Sampling, ChamferDistanceLoss, EarthMoverDistanceLoss, SilhouetteLoss, VPDiverseLoss, VertexRenderer,
                       transform_points, rotate_points, translate_points, view_to_obj_points,
-                      obj_to_view_points, rotate_points_forward_x_axis, pack_head_outputs, split_primitives, Meshing, TriangleMesh, load_obj)
+                      obj_to_view_points, rotate_points_forward_x_axis, pack_head_outputs, split_primitives, Meshing, TriangleMesh, load_obj,
+                      cut_mix_data, cut_mix_batch_points, adjust_point_num, mixup_points)
 from . import modules

@@ -9,7 +9,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('VPN_HIP_LIB') or os.path.join(_HERE, 'libvpn_hip.so')     # VPN_HIP_LIB: the sanitizer build of the tests
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 _c_f = ctypes.c_void_p      # device pointers travel as void*
 _i, _f, _u64, _sz = ctypes.c_int, ctypes.c_float, ctypes.c_uint64, ctypes.c_size_t
@@ -84,6 +84,11 @@ SIGNATURES = {
     'vpn_gcn_input_fwd': (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _i, _i] + [_c_f] * 4 + [_i] * 12 + [_c_f] * 6),
     'vpn_gcn_input_bwd_workspace': (_sz, [_i, _i, _i] + [_i] * 12),
     'vpn_gcn_input_bwd': (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _i, _i] + [_i] * 12 + [_c_f] * 11),
+    'vpn_cutmix_points_lds': (_sz, [_i]),
+    'vpn_cutmix_points': (_i, [_c_f, _c_f, _c_f, _f, _u64, _u64, _i, _i, _i, _c_f, _c_f, _c_f, _c_f]),
+    'vpn_cutmix_images': (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _i, _i, _i, _c_f, _c_f, _c_f]),
+    'vpn_mixup_gather': (_i, [_c_f, _c_f, _i, _i, _c_f, _c_f]),
+    'vpn_mixup_lerp': (_i, [_c_f, _c_f, _c_f, _i, _i, _f, _f, _c_f, _c_f]),
 }
 
 _lib = None

@@ -8,3 +8,5 @@ from .transform import (transform_points, rotate_points, translate_points, view_
 from .network import pack_head_outputs, split_primitives, GCNModel, GCNConv
 from .meshing import Meshing, TriangleMesh, load_obj
 from .dataset import parse_split_csv, parse_rendering_metadata, split_rgba
+from . import augmentation
+from .augmentation import cut_mix_data, cut_mix_batch_points, adjust_point_num, mixup_points

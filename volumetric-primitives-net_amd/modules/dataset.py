@@ -1,7 +1,7 @@
 """The on-disk formats either side of the hot path (row f4; modules/dataset/dataset.py of the reference): which
 models belong to which split, the camera of every rendering, and how an RGBA rendering becomes the network input
 and the GT silhouette.  Host-side text / tensor handling only — the dataset class itself (file discovery,
-augmentation, kaolin mesh sampling) is out of scope."""
+kaolin mesh sampling) is out of scope; the device-side augmentations are in modules/augmentation.py."""
 import torch
 
 DIST_SCALE = 1.754                       # dataset.py:147: the stored camera distance is scaled by this factor

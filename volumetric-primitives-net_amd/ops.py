@@ -1162,3 +1162,89 @@ class GcnInputFunction(Function):
             ctot = g.shape[2]
             gg = _colsum(g, None, B, N, ctot, ctot - G, G)
         return (gv, None, gg, None) + (tuple(gm) if need_m else (None,) * L)
+
+
+# ---- the batch augmentation stage (csrc/augment.hip).  Plain functions: the augmented tensors are data, nothing here is
+# differentiable and no output requires grad.
+
+def _augment_is_data(*tensors):
+    for t in tensors:
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise RuntimeError('augmentation arguments are dataset values here (train.py:232-237); gradients with respect '
+                               'to them are not implemented')
+
+
+def partner_indices(indices, B, device):
+    """The partner of each sample as the contiguous int32 device tensor the kernels read.  A host tensor or list is
+    checked against [0, B) here and uploaded from pinned memory without blocking (no synchronisation); a device tensor
+    is converted at most (the kernels read an entry outside [0, B) as the sample itself)."""
+    if isinstance(indices, torch.Tensor) and indices.is_cuda:
+        assert indices.numel() == B
+        return indices.reshape(B).to(torch.int32).contiguous()
+    host = torch.as_tensor(indices).reshape(-1).to(torch.int32)
+    if host.numel() != B or (B and (int(host.min()) < 0 or int(host.max()) >= B)):
+        raise ValueError('indices must name %d partners in [0, %d)' % (B, B))
+    return host.pin_memory().to(device, non_blocking=True)
+
+
+def cutmix_points(points, indices, cut, seed, sample_base=0, n_out=None):
+    """vpn_cutmix_points: points [B,N,3], indices [B] int32 on the device (None: each sample with itself), cut a float or
+    a [B] fp32 device tensor -> (out [B,n_out,3], src [B,n_out] int32, count [B] int32); n_out defaults to N."""
+    _augment_is_data(points, cut)
+    points = _f32c(points.detach())
+    B, N, _ = points.shape
+    n_out = N if n_out is None else int(n_out)
+    dev = points.device
+    cut_t = None
+    if isinstance(cut, torch.Tensor):
+        cut_t = _f32c(cut.detach()).reshape(-1)
+        assert cut_t.numel() == B
+        cut = 0.0
+    out = torch.empty((B, n_out, 3), dtype=torch.float32, device=dev)
+    src = torch.empty((B, n_out), dtype=torch.int32, device=dev)
+    count = torch.empty((B,), dtype=torch.int32, device=dev)
+    _lib.call('vpn_cutmix_points', _lib.ptr(points), _lib.ptr(indices), _lib.ptr(cut_t), float(cut),
+              int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_base), B, N, n_out, _lib.ptr(out), _lib.ptr(src), _lib.ptr(count),
+              _lib.stream())
+    return out, src, count
+
+
+def cutmix_images(rgbs, silhouettes, indices, cut_index):
+    """vpn_cutmix_images: both images in one launch, out of place (silhouettes may be None)."""
+    _augment_is_data(rgbs, silhouettes)
+    rgbs = _f32c(rgbs.detach())
+    B, Ca, H, W = rgbs.shape
+    out_a = torch.empty_like(rgbs)
+    Cb, out_b = 0, None
+    if silhouettes is not None:
+        silhouettes = _f32c(silhouettes.detach())
+        assert silhouettes.size(0) == B and silhouettes.shape[2:] == rgbs.shape[2:]
+        Cb = silhouettes.size(1)
+        out_b = torch.empty_like(silhouettes)
+    _lib.call('vpn_cutmix_images', _lib.ptr(rgbs), _lib.ptr(silhouettes), _lib.ptr(indices), B, Ca, Cb, H, W, int(cut_index),
+              _lib.ptr(out_a), _lib.ptr(out_b), _lib.stream())
+    return out_a, out_b
+
+
+def mixup_points(points, indices, ratio, eps=0.005, iters=100, max_group=None):
+    """point_mixup.py:24-40 for the whole batch: gather of the partner clouds, ONE auction over the B pairs, the
+    interpolation through its assignment -> (mixed [B,n,3], dist [B,n], assignment [B,n] int32)."""
+    _augment_is_data(points)
+    points = _f32c(points.detach())
+    B, n, _ = points.shape
+    dev = points.device
+    partner = torch.empty_like(points)
+    _lib.call('vpn_mixup_gather', _lib.ptr(points), _lib.ptr(indices), B, n, _lib.ptr(partner), _lib.stream())
+    dist = torch.empty((B, n), dtype=torch.float32, device=dev)
+    assignment = torch.empty((B, n), dtype=torch.int32, device=dev)
+    ws = torch.empty((max(1, _lib.lib().vpn_emd_workspace(B, n) // 4),), dtype=torch.float32, device=dev)
+    if max_group is None:
+        max_group = 1 if CONCURRENT_BRANCHES else int(os.environ.get('VPN_EMD_GROUP', '0'))
+    _lib.call('vpn_emd_fwd_ex', _lib.ptr(points), _lib.ptr(partner), B, n, float(eps), int(iters), _lib.ptr(dist),
+              _lib.ptr(assignment), _lib.ptr(ws), int(max_group), _lib.stream(), EMD_TEST_GIVEUP_MASK)
+    ratio = float(ratio)
+    mixed = torch.empty_like(points)
+    # (1 - r) and r as torch rounds the two Python doubles of point_mixup.py:36 to fp32
+    _lib.call('vpn_mixup_lerp', _lib.ptr(points), _lib.ptr(partner), _lib.ptr(assignment), B, n, 1.0 - ratio, ratio,
+              _lib.ptr(mixed), _lib.stream())
+    return mixed, dist, assignment
