@@ -168,8 +168,10 @@ class KernelProfile:
 
 
 def call(name, *args):
-    """Invoke entry point `name`, raise on a non-zero return code."""
+    """Invoke entry point `name`, raise on a non-zero return code.  A tensor argument travels as its device pointer
+    (ptr(): GPU only, contiguous); None, numbers and ctypes values (the stream, pointers the caller built) pass as they are."""
     fn = getattr(lib(), name)
+    args = [ptr(a) if isinstance(a, torch.Tensor) else a for a in args]
     if _timer is None:
         check(fn(*args))
         return

@@ -6,6 +6,7 @@ backward needs; backward returns one gradient per tensor input and None for the 
 Unlike it, a non-zero return code raises."""
 import ctypes
 import os
+import weakref
 
 import torch
 from torch.autograd import Function
@@ -23,7 +24,22 @@ def _f32c(t):
     return t.contiguous().float()          # emd_module.py:41-42 does the same to its inputs
 
 
-import weakref
+def _workspace(query, *dims, dev, dtype=torch.float32, floor=0):
+    """Uninitialised buffer of the size in bytes that the library's `query`(*dims) reports, as `dtype` elements and at least
+    `floor` of them (an empty tensor has a null pointer).  Like _nn_outputs, torch.empty alone: the hot path is captured
+    into HIP graphs and stays free of host synchronisation and of ATen kernels."""
+    nbytes = getattr(_lib.lib(), query)(*dims)
+    return torch.empty((max(floor, nbytes // dtype.itemsize),), dtype=dtype, device=dev)
+
+
+def _nn_outputs(B, N, M, dev):
+    """(dist1 [B,N], idx1 [B,N] int32, dist2 [B,M], idx2 [B,M] int32): the outputs of a nearest-neighbour scan."""
+    d1 = torch.empty((B, N), dtype=torch.float32, device=dev)
+    d2 = torch.empty((B, M), dtype=torch.float32, device=dev)
+    i1 = torch.empty((B, N), dtype=torch.int32, device=dev)
+    i2 = torch.empty((B, M), dtype=torch.int32, device=dev)
+    return d1, i1, d2, i2
+
 
 # Host copies of device kind tensors: id(tensor) -> (weak reference to it, the version counter it had then, the kinds as a
 # tuple).  The entry dies with its tensor (weakref callback) and a hit also requires the reference to be the same object, so
@@ -104,8 +120,7 @@ class SampleFunction(Function):
             u = _f32c(u)
             assert u.shape == (B, K, n, 3)
         points = torch.empty((B, K * n, 3), dtype=torch.float32, device=params.device)
-        _lib.call('vpn_sample_fwd', _lib.ptr(params), _lib.ptr(kinds), _lib.ptr(u), int(seed), None, int(sample_base),
-                                    B, K, n, _lib.ptr(points), _lib.stream())
+        _lib.call('vpn_sample_fwd', params, kinds, u, int(seed), None, int(sample_base), B, K, n, points, _lib.stream())
         ctx.save_for_backward(params, kinds, u if u is not None else torch.empty(0, device=params.device))
         ctx.has_u = u is not None
         ctx.meta = (int(seed), int(sample_base), B, K, n)
@@ -117,8 +132,8 @@ class SampleFunction(Function):
         seed, base, B, K, n = ctx.meta
         grad_points = _f32c(grad_points)
         grad_params = torch.empty_like(params)
-        _lib.call('vpn_sample_bwd', _lib.ptr(params), _lib.ptr(kinds), _lib.ptr(u) if ctx.has_u else None, seed, None,
-                                    base, B, K, n, _lib.ptr(grad_points), _lib.ptr(grad_params), _lib.stream())
+        _lib.call('vpn_sample_bwd', params, kinds, u if ctx.has_u else None, seed, None, base, B, K, n, grad_points,
+                  grad_params, _lib.stream())
         return grad_params, None, None, None, None, None
 
 
@@ -131,8 +146,7 @@ class TransformFunction(Function):
         t = _f32c(t) if t is not None else None
         B, N, _ = points.shape
         out = torch.empty_like(points)
-        _lib.call('vpn_transform_fwd', _lib.ptr(points), _lib.ptr(q), _lib.ptr(t), B, N, _lib.ptr(out),
-                                       _lib.stream())
+        _lib.call('vpn_transform_fwd', points, q, t, B, N, out, _lib.stream())
         ctx.save_for_backward(points, q)
         ctx.has_t = t is not None
         return out
@@ -146,8 +160,7 @@ class TransformFunction(Function):
         gp = torch.empty_like(points) if need_p else None
         gq = torch.empty_like(q) if need_q else None
         gt = torch.empty((B, 3), dtype=torch.float32, device=points.device) if need_t else None
-        _lib.call('vpn_transform_bwd', _lib.ptr(points), _lib.ptr(q), _lib.ptr(grad_out), B, N, _lib.ptr(gp),
-                                       _lib.ptr(gq), _lib.ptr(gt), _lib.stream())
+        _lib.call('vpn_transform_bwd', points, q, grad_out, B, N, gp, gq, gt, _lib.stream())
         return gp, gq, gt
 
 
@@ -163,8 +176,7 @@ class MeshFunction(Function):
         ts = _f32c(tpl_sphere) if tpl_sphere is not None else None
         tc = _f32c(tpl_cuboid) if tpl_cuboid is not None else None
         verts = torch.empty((B, int(ptot), 3), dtype=torch.float32, device=params.device)
-        _lib.call('vpn_mesh_fwd', _lib.ptr(params), _lib.ptr(kinds), _lib.ptr(offsets), _lib.ptr(ts), _lib.ptr(tc), B, K,
-                  int(ptot), _lib.ptr(verts), _lib.stream())
+        _lib.call('vpn_mesh_fwd', params, kinds, offsets, ts, tc, B, K, int(ptot), verts, _lib.stream())
         ctx.save_for_backward(params, kinds, offsets, *(x for x in (ts, tc) if x is not None))
         ctx.which = (ts is not None, tc is not None, int(ptot))
         return verts
@@ -178,8 +190,7 @@ class MeshFunction(Function):
         B, K, _ = params.shape
         g = _f32c(grad_verts)
         gp = torch.empty_like(params)
-        _lib.call('vpn_mesh_bwd', _lib.ptr(params), _lib.ptr(kinds), _lib.ptr(offsets), _lib.ptr(ts), _lib.ptr(tc), B, K, ptot,
-                  _lib.ptr(g), _lib.ptr(gp), _lib.stream())
+        _lib.call('vpn_mesh_bwd', params, kinds, offsets, ts, tc, B, K, ptot, g, gp, _lib.stream())
         return gp, None, None, None, None, None
 
 
@@ -240,10 +251,9 @@ class MeshRasterFunction(Function):
         F = faces.shape[0]
         assert faces.dtype == torch.int32 and faces.is_cuda and faces.is_contiguous() and cam.shape == (B, 3)
         dev = verts.device
-        ws = torch.empty((_lib.lib().vpn_mesh_raster_workspace(B, P) // 4,), dtype=torch.float32, device=dev)
+        ws = _workspace('vpn_mesh_raster_workspace', B, P, dev=dev)
         alpha = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-        _lib.call('vpn_mesh_raster_fwd', _lib.ptr(verts), _lib.ptr(faces), _lib.ptr(cam), B, P, F, H, W, float(sigma),
-                  _lib.ptr(ws), _lib.ptr(alpha), _lib.stream())
+        _lib.call('vpn_mesh_raster_fwd', verts, faces, cam, B, P, F, H, W, float(sigma), ws, alpha, _lib.stream())
         ctx.save_for_backward(verts, faces, cam, ws, alpha)
         ctx.meta = (B, P, F, H, W, float(sigma))
         return alpha
@@ -254,8 +264,7 @@ class MeshRasterFunction(Function):
         B, P, F, H, W, sigma = ctx.meta
         g = _f32c(grad_alpha)
         gv = torch.empty_like(verts)
-        _lib.call('vpn_mesh_raster_bwd', _lib.ptr(verts), _lib.ptr(faces), _lib.ptr(cam), B, P, F, H, W, sigma, _lib.ptr(ws),
-                  _lib.ptr(alpha), _lib.ptr(g), _lib.ptr(gv), _lib.stream())
+        _lib.call('vpn_mesh_raster_bwd', verts, faces, cam, B, P, F, H, W, sigma, ws, alpha, g, gv, _lib.stream())
         return gv, None, None, None, None, None
 
 
@@ -277,8 +286,8 @@ class MeshSampleFunction(Function):
         points = torch.empty((B, n, 3), dtype=torch.float32, device=dev)
         fidx = torch.empty((B, n), dtype=torch.int32, device=dev)
         bary = torch.empty((B, n, 3), dtype=torch.float32, device=dev)
-        _lib.call('vpn_mesh_sample_fwd', _lib.ptr(verts), _lib.ptr(faces), _lib.ptr(u), int(seed), int(mesh_base), B, P, F, int(n),
-                  _lib.ptr(cdf), _lib.ptr(points), _lib.ptr(fidx), _lib.ptr(bary), _lib.stream())
+        _lib.call('vpn_mesh_sample_fwd', verts, faces, u, int(seed), int(mesh_base), B, P, F, int(n), cdf, points, fidx, bary,
+                  _lib.stream())
         ctx.save_for_backward(faces, fidx, bary)
         ctx.meta = (B, P, F, int(n))
         ctx.mark_non_differentiable(fidx)
@@ -290,8 +299,7 @@ class MeshSampleFunction(Function):
         B, P, F, n = ctx.meta
         g = _f32c(grad_points)
         gv = torch.empty((B, P, 3), dtype=torch.float32, device=g.device)
-        _lib.call('vpn_mesh_sample_bwd', _lib.ptr(faces), _lib.ptr(fidx), _lib.ptr(bary), _lib.ptr(g), B, P, F, n, _lib.ptr(gv),
-                  _lib.stream())
+        _lib.call('vpn_mesh_sample_bwd', faces, fidx, bary, g, B, P, F, n, gv, _lib.stream())
         return gv, None, None, None, None, None
 
 
@@ -309,9 +317,8 @@ class HeadPackFunction(Function):
         r = [float(x) for x in restrict]
         assert len(r) == 3
         params = torch.empty((B, K, PARAM_STRIDE), dtype=torch.float32, device=volumes.device)
-        _lib.call('vpn_head_pack_fwd', _lib.ptr(volumes), _lib.ptr(rotates), _lib.ptr(translates), B, K,
-                  int(bool(is_sigmoid)), float(clamp_min), float(clamp_max), r[0], r[1], r[2], _lib.ptr(params),
-                  _lib.stream())
+        _lib.call('vpn_head_pack_fwd', volumes, rotates, translates, B, K, int(bool(is_sigmoid)), float(clamp_min),
+                  float(clamp_max), r[0], r[1], r[2], params, _lib.stream())
         ctx.save_for_backward(volumes, rotates, translates)
         ctx.cfg = (B, K, int(bool(is_sigmoid)), float(clamp_min), float(clamp_max), r)
         return params
@@ -324,8 +331,8 @@ class HeadPackFunction(Function):
         gv = torch.empty_like(volumes) if ctx.needs_input_grad[0] else None
         gq = torch.empty_like(rotates) if ctx.needs_input_grad[1] else None
         gt = torch.empty_like(translates) if ctx.needs_input_grad[2] else None
-        _lib.call('vpn_head_pack_bwd', _lib.ptr(volumes), _lib.ptr(rotates), _lib.ptr(translates), _lib.ptr(g), B, K, sig,
-                  cmin, cmax, r[0], r[1], r[2], _lib.ptr(gv), _lib.ptr(gq), _lib.ptr(gt), _lib.stream())
+        _lib.call('vpn_head_pack_bwd', volumes, rotates, translates, g, B, K, sig, cmin, cmax, r[0], r[1], r[2], gv, gq, gt,
+                  _lib.stream())
         return gv, gq, gt, None, None, None, None
 
 
@@ -343,8 +350,8 @@ class CameraTransformFunction(Function):
             if c.numel() != B:
                 raise ValueError('camera arguments must hold one value per sample')
         out = torch.empty_like(points)
-        _lib.call('vpn_camera_transform_fwd', _lib.ptr(points), _lib.ptr(cam[0]), _lib.ptr(cam[1]), _lib.ptr(cam[2]),
-                  _lib.ptr(ang), B, N, int(bool(to_object)), _lib.ptr(out), _lib.stream())
+        _lib.call('vpn_camera_transform_fwd', points, cam[0], cam[1], cam[2], ang, B, N, int(bool(to_object)), out,
+                  _lib.stream())
         ctx.save_for_backward(*cam, *([ang] if ang is not None else []))
         ctx.to_object = int(bool(to_object))
         return out
@@ -357,8 +364,7 @@ class CameraTransformFunction(Function):
         g = _f32c(grad_out)
         B, N, _ = g.shape
         gp = torch.empty_like(g)
-        _lib.call('vpn_camera_transform_bwd', _lib.ptr(g), _lib.ptr(d), _lib.ptr(e), _lib.ptr(a), _lib.ptr(ang), B, N,
-                  ctx.to_object, _lib.ptr(gp), _lib.stream())
+        _lib.call('vpn_camera_transform_bwd', g, d, e, a, ang, B, N, ctx.to_object, gp, _lib.stream())
         return gp, None, None, None, None, None
 
 
@@ -372,16 +378,12 @@ class ChamferFunction(Function):
         B, N, _ = p1.shape
         M = p2.shape[1]
         dev = p1.device
-        d1 = torch.empty((B, N), dtype=torch.float32, device=dev)
-        d2 = torch.empty((B, M), dtype=torch.float32, device=dev)
-        i1 = torch.empty((B, N), dtype=torch.int32, device=dev)
-        i2 = torch.empty((B, M), dtype=torch.int32, device=dev)
+        d1, i1, d2, i2 = _nn_outputs(B, N, M, dev)
         loss_b = torch.empty((B,), dtype=torch.float32, device=dev)
         s = _lib.stream()
-        ws = torch.empty((_lib.lib().vpn_chamfer_workspace(B, N, M) // 4,), dtype=torch.float32, device=dev)
-        _lib.call('vpn_chamfer_fwd_ws', _lib.ptr(p1), _lib.ptr(p2), B, N, M, _lib.ptr(d1), _lib.ptr(i1), _lib.ptr(d2),
-                  _lib.ptr(i2), _lib.ptr(ws), ws.numel() * 4, 0, s)
-        _lib.call('vpn_chamfer_loss', _lib.ptr(d1), _lib.ptr(d2), B, N, M, float(w1), float(w2), _lib.ptr(loss_b), s)
+        ws = _workspace('vpn_chamfer_workspace', B, N, M, dev=dev)
+        _lib.call('vpn_chamfer_fwd_ws', p1, p2, B, N, M, d1, i1, d2, i2, ws, ws.numel() * 4, 0, s)
+        _lib.call('vpn_chamfer_loss', d1, d2, B, N, M, float(w1), float(w2), loss_b, s)
         ctx.save_for_backward(p1, p2, d1, i1, d2, i2)
         ctx.w = (float(w1), float(w2))
         return loss_b
@@ -394,9 +396,7 @@ class ChamferFunction(Function):
         g = _f32c(grad_loss_b)
         g1 = torch.empty_like(p1) if ctx.needs_input_grad[0] else None
         g2 = torch.empty_like(p2) if ctx.needs_input_grad[1] else None
-        _lib.call('vpn_chamfer_bwd', _lib.ptr(p1), _lib.ptr(p2), _lib.ptr(d1), _lib.ptr(i1), _lib.ptr(d2),
-                                     _lib.ptr(i2), _lib.ptr(g), B, N, M, ctx.w[0], ctx.w[1], _lib.ptr(g1),
-                                     _lib.ptr(g2), _lib.stream())
+        _lib.call('vpn_chamfer_bwd', p1, p2, d1, i1, d2, i2, g, B, N, M, ctx.w[0], ctx.w[1], g1, g2, _lib.stream())
         return g1, g2, None, None
 
 
@@ -405,26 +405,36 @@ CHAMFER_MODES = {'auto': 0, 'brute': 1, 'pruned': 2, 'mfma': 3, 'mfma32': 4, 'so
 
 def chamfer_nn(p1, p2, mode='auto'):
     """Nearest-neighbour distances and indices in both directions (no autograd):
-    (dist1 [B,N], idx1 [B,N] int32, dist2 [B,M], idx2 [B,M] int32).  mode: 'auto' | 'brute' | 'pruned'
-    (same results bit for bit; 'pruned' Morton-sorts the clouds and skips far target chunks, 'mfma' / 'mfma32'
-    filter on the bf16 / fp32 matrix instructions and finish exactly)."""
+    (dist1 [B,N], idx1 [B,N] int32, dist2 [B,M], idx2 [B,M] int32).  mode, one of CHAMFER_MODES (same results bit for
+    bit; the numbered modes of vpn_chamfer_fwd_ws in include/vpn_hip.h):
+        'auto'    'mfma16' for large clouds, else 'brute'
+        'brute'   brute force
+        'pruned'  box-pruned: the clouds Morton-sorted per call, target chunks farther than the current best skipped
+        'mfma'    matrix-pipe filter on bf16 MFMA (coordinates split exactly into three bf16 pieces), finished exactly
+        'mfma32'  the same filter on fp32-input MFMA
+        'sorted'  'mfma' over Morton-sorted clouds with per-block boxes: target blocks that cannot hold a nearer point skipped
+        'mfma16'  the filter with one fp16 MFMA per 32x32 block (coordinates scaled and split into two fp16 pieces)"""
     p1, p2 = _f32c(p1.detach()), _f32c(p2.detach())
     B, N, _ = p1.shape
     M = p2.shape[1]
     dev = p1.device
-    d1 = torch.empty((B, N), dtype=torch.float32, device=dev)
-    d2 = torch.empty((B, M), dtype=torch.float32, device=dev)
-    i1 = torch.empty((B, N), dtype=torch.int32, device=dev)
-    i2 = torch.empty((B, M), dtype=torch.int32, device=dev)
-    ws = torch.empty((_lib.lib().vpn_chamfer_workspace(B, N, M) // 4,), dtype=torch.float32, device=dev)
-    _lib.call('vpn_chamfer_fwd_ws', _lib.ptr(p1), _lib.ptr(p2), B, N, M, _lib.ptr(d1), _lib.ptr(i1), _lib.ptr(d2),
-              _lib.ptr(i2), _lib.ptr(ws), ws.numel() * 4, CHAMFER_MODES[mode], _lib.stream())
+    d1, i1, d2, i2 = _nn_outputs(B, N, M, dev)
+    ws = _workspace('vpn_chamfer_workspace', B, N, M, dev=dev)
+    _lib.call('vpn_chamfer_fwd_ws', p1, p2, B, N, M, d1, i1, d2, i2, ws, ws.numel() * 4, CHAMFER_MODES[mode], _lib.stream())
     return d1, i1, d2, i2
 
 
 # Test hook of the auction (vpn_emd_fwd_ex): bit b set = sample b < 32 of every EMD call in this process gives up at its
 # first group barrier whenever the call runs with G > 1, so the G = 1 recovery launch redoes it.  0 in normal use.
 EMD_TEST_GIVEUP_MASK = 0
+
+
+def _emd_group(max_group):
+    """The auction's cap on the workgroups per sample (see EmdFunction.forward): `max_group`, or for None 1 under
+    VPN_CONCURRENT=1 and else what the environment asks for (0, the default: automatic)."""
+    if max_group is None:
+        return 1 if CONCURRENT_BRANCHES else int(os.environ.get('VPN_EMD_GROUP', '0'))
+    return int(max_group)
 
 
 def emd_recovered_samples():
@@ -449,7 +459,7 @@ class EmdFunction(Function):
 
     @staticmethod
     def forward(ctx, xyz1, xyz2, eps, iters, max_group=None):
-        """max_group: cap on the workgroups per sample (None: VPN_EMD_GROUP or automatic; 1: no inter-workgroup barrier --
+        """max_group: cap on the workgroups per sample (None: _emd_group's default; 1: no inter-workgroup barrier --
         what VPN_CONCURRENT=1 picks, since there other streams of this process share the GPU by design).  The library
         bounds the group by the occupancy query of an idle GPU and launches plainly (VPN_EMD_COOP_LAUNCH=1: a cooperative
         launch, which falls back to one workgroup per sample if the runtime refuses the grid).  When another process or
@@ -464,11 +474,9 @@ class EmdFunction(Function):
         dev = xyz1.device
         dist = torch.empty((B, n), dtype=torch.float32, device=dev)
         assignment = torch.empty((B, n), dtype=torch.int32, device=dev)
-        ws = torch.empty((max(1, _lib.lib().vpn_emd_workspace(B, n) // 4),), dtype=torch.float32, device=dev)
-        if max_group is None:
-            max_group = 1 if CONCURRENT_BRANCHES else int(os.environ.get('VPN_EMD_GROUP', '0'))
-        _lib.call('vpn_emd_fwd_ex', _lib.ptr(xyz1), _lib.ptr(xyz2), B, n, float(eps), int(iters), _lib.ptr(dist),
-                  _lib.ptr(assignment), _lib.ptr(ws), int(max_group), _lib.stream(), EMD_TEST_GIVEUP_MASK)
+        ws = _workspace('vpn_emd_workspace', B, n, dev=dev, floor=1)
+        _lib.call('vpn_emd_fwd_ex', xyz1, xyz2, B, n, float(eps), int(iters), dist, assignment, ws, _emd_group(max_group),
+                  _lib.stream(), EMD_TEST_GIVEUP_MASK)
         ctx.save_for_backward(xyz1, xyz2, assignment)
         ctx.mark_non_differentiable(assignment)
         return dist, assignment
@@ -479,8 +487,7 @@ class EmdFunction(Function):
         B, n, _ = xyz1.shape
         g = _f32c(graddist)
         g1 = torch.empty_like(xyz1)
-        _lib.call('vpn_emd_bwd', _lib.ptr(xyz1), _lib.ptr(xyz2), _lib.ptr(g), _lib.ptr(assignment), B, n,
-                  _lib.ptr(g1), _lib.stream())
+        _lib.call('vpn_emd_bwd', xyz1, xyz2, g, assignment, B, n, g1, _lib.stream())
         g2 = torch.zeros_like(xyz2) if ctx.needs_input_grad[1] else None     # emd_module.py:67
         return g1, g2, None, None, None
 
@@ -499,10 +506,9 @@ class RasterFunction(Function):
         alpha = torch.empty((B, H, W), dtype=torch.float32, device=dev)
         depth = torch.empty((B, H, W), dtype=torch.float32, device=dev)
         aux = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
-        rec = torch.empty((_lib.lib().vpn_raster_records_size(B, K, H, W) // 4,), dtype=torch.float32, device=dev)
-        _lib.call('vpn_raster_fwd', _lib.ptr(params), _lib.ptr(kinds), _lib.ptr(cam), B, K, H, W,
-                  float(sigma), float(gamma), float(z_far), _lib.ptr(alpha), _lib.ptr(depth), _lib.ptr(aux),
-                  _lib.ptr(rec), _lib.stream())
+        rec = _workspace('vpn_raster_records_size', B, K, H, W, dev=dev)
+        _lib.call('vpn_raster_fwd', params, kinds, cam, B, K, H, W, float(sigma), float(gamma), float(z_far), alpha, depth, aux,
+                  rec, _lib.stream())
         ctx.save_for_backward(params, kinds, cam, aux, rec)
         ctx.meta = (B, K, H, W, float(sigma), float(gamma), float(z_far))
         return alpha, depth
@@ -513,11 +519,10 @@ class RasterFunction(Function):
         B, K, H, W, sigma, gamma, z_far = ctx.meta
         ga = _f32c(grad_alpha) if grad_alpha is not None else None
         gd = _f32c(grad_depth) if grad_depth is not None else None
-        ws = torch.empty((_lib.lib().vpn_raster_bwd_workspace(B, K, H, W) // 4,), dtype=torch.float32, device=params.device)
+        ws = _workspace('vpn_raster_bwd_workspace', B, K, H, W, dev=params.device)
         grad_params = torch.empty_like(params)
-        _lib.call('vpn_raster_bwd', _lib.ptr(params), _lib.ptr(kinds), _lib.ptr(cam), B, K, H, W, sigma, gamma,
-                  z_far, _lib.ptr(aux), _lib.ptr(rec), _lib.ptr(ga), _lib.ptr(gd), _lib.ptr(ws),
-                  _lib.ptr(grad_params), _lib.stream())
+        _lib.call('vpn_raster_bwd', params, kinds, cam, B, K, H, W, sigma, gamma, z_far, aux, rec, ga, gd, ws, grad_params,
+                  _lib.stream())
         return grad_params, None, None, None, None, None, None, None
 
 
@@ -537,14 +542,12 @@ class RasterLossFunction(Function):
         if gt_depth is not None:
             gt_depth = _f32c(gt_depth).reshape(B, H, W)
         dev = params.device
-        L = _lib.lib()
         aux = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
-        rec = torch.empty((L.vpn_raster_records_size(B, K, H, W) // 4,), dtype=torch.float32, device=dev)
-        lws = torch.empty((L.vpn_raster_loss_workspace(B, H, W) // 4,), dtype=torch.float32, device=dev)
+        rec = _workspace('vpn_raster_records_size', B, K, H, W, dev=dev)
+        lws = _workspace('vpn_raster_loss_workspace', B, H, W, dev=dev)
         losses = torch.empty((4,), dtype=torch.float32, device=dev)
-        _lib.call('vpn_raster_loss_fwd', _lib.ptr(params), _lib.ptr(kinds), _lib.ptr(cam), B, K, H, W, float(sigma),
-                  float(gamma), float(z_far), _lib.ptr(gt_sil), _lib.ptr(gt_depth), int(bool(sil_mse)), _lib.ptr(aux),
-                  _lib.ptr(rec), _lib.ptr(lws), _lib.ptr(losses), _lib.stream())
+        _lib.call('vpn_raster_loss_fwd', params, kinds, cam, B, K, H, W, float(sigma), float(gamma), float(z_far), gt_sil,
+                  gt_depth, int(bool(sil_mse)), aux, rec, lws, losses, _lib.stream())
         losses = losses[:2]
         empty = torch.empty(0, device=dev)
         ctx.save_for_backward(params, kinds, cam, aux, rec, gt_sil if gt_sil is not None else empty,
@@ -558,13 +561,10 @@ class RasterLossFunction(Function):
         params, kinds, cam, aux, rec, gt_sil, gt_depth = ctx.saved_tensors
         B, K, H, W, sigma, gamma, z_far, sil_mse, has_sil, has_depth = ctx.meta
         g = _f32c(grad_losses)
-        ws = torch.empty((_lib.lib().vpn_raster_bwd_workspace(B, K, H, W) // 4,), dtype=torch.float32,
-                         device=params.device)
+        ws = _workspace('vpn_raster_bwd_workspace', B, K, H, W, dev=params.device)
         grad_params = torch.empty_like(params)
-        _lib.call('vpn_raster_loss_bwd', _lib.ptr(params), _lib.ptr(kinds), _lib.ptr(cam), B, K, H, W, sigma, gamma,
-                  z_far, _lib.ptr(aux), _lib.ptr(rec), _lib.ptr(gt_sil) if has_sil else None,
-                  _lib.ptr(gt_depth) if has_depth else None, sil_mse, _lib.ptr(g), _lib.ptr(ws),
-                  _lib.ptr(grad_params), 0, _lib.stream())
+        _lib.call('vpn_raster_loss_bwd', params, kinds, cam, B, K, H, W, sigma, gamma, z_far, aux, rec,
+                  gt_sil if has_sil else None, gt_depth if has_depth else None, sil_mse, g, ws, grad_params, 0, _lib.stream())
         return (grad_params,) + (None,) * 10
 
 
@@ -583,17 +583,15 @@ class RasterTotalFunction(Function):
         gt_sil = _f32c(gt_sil).reshape(B, H, W) if gt_sil is not None else None
         gt_depth = _f32c(gt_depth).reshape(B, H, W) if gt_depth is not None else None
         dev = params.device
-        L = _lib.lib()
         s = _lib.stream()
-        rec = torch.empty((L.vpn_raster_records_size(B, K, H, W) // 4,), dtype=torch.float32, device=dev)
-        lws = torch.empty((L.vpn_raster_loss_workspace(B, H, W) // 4,), dtype=torch.float32, device=dev)
-        ws = torch.empty((L.vpn_raster_bwd_workspace(B, K, H, W) // 4,), dtype=torch.float32, device=dev)
+        rec = _workspace('vpn_raster_records_size', B, K, H, W, dev=dev)
+        lws = _workspace('vpn_raster_loss_workspace', B, H, W, dev=dev)
+        ws = _workspace('vpn_raster_bwd_workspace', B, K, H, W, dev=dev)
         losses = torch.empty((4,), dtype=torch.float32, device=dev)
         # render, image losses, gradient partials and the loss finalisation: one launch after the record launch
-        _lib.call('vpn_raster_total_fwd_fin', _lib.ptr(params), _lib.ptr(kinds), _lib.ptr(cam), B, K, H, W, float(sigma),
-                  float(gamma), float(z_far), _lib.ptr(gt_sil), _lib.ptr(gt_depth), int(bool(sil_mse)), float(w_sil),
-                  float(w_dep), _lib.ptr(rec), _lib.ptr(lws), _lib.ptr(ws), 0, None, 0, 0, 0, 0.0, 0.0, 0.0,
-                  _lib.ptr(losses), None, None, None, s)
+        _lib.call('vpn_raster_total_fwd_fin', params, kinds, cam, B, K, H, W, float(sigma), float(gamma), float(z_far), gt_sil,
+                  gt_depth, int(bool(sil_mse)), float(w_sil), float(w_dep), rec, lws, ws, 0, None, 0, 0, 0, 0.0, 0.0, 0.0,
+                  losses, None, None, None, s)
         ctx.save_for_backward(params, cam, rec, ws)
         ctx.meta = (B, K, H, W)
         sil, dep, tot, _ = losses.unbind(0)
@@ -609,8 +607,7 @@ class RasterTotalFunction(Function):
             return (None,) * 13
         g = _f32c(grad_total).reshape(1)
         grad_params = torch.empty_like(params)
-        _lib.call('vpn_raster_total_bwd', _lib.ptr(params), _lib.ptr(cam), B, K, H, W, _lib.ptr(rec), _lib.ptr(ws),
-                  _lib.ptr(g), _lib.ptr(grad_params), 0, _lib.stream())
+        _lib.call('vpn_raster_total_bwd', params, cam, B, K, H, W, rec, ws, g, grad_params, 0, _lib.stream())
         return (grad_params,) + (None,) * 12
 
 
@@ -641,6 +638,63 @@ def _grad_pattern(B, w_cd, dev):
     return _PATTERNS[key]
 
 
+def _tile_rider_fits(K, H, W):
+    """Whether the Chamfer scan's launch can carry the rider that tests the raster's 16 x 16 pixel tiles (R_TW, R_TH) against
+    the K primitives and sorts them by weight.  Restates the check of vpn_hotpath_chamfer_fwd in csrc/chamfer.hip, which
+    answers VPN_E_TOOBIG otherwise: K <= R_ORDER_MAX_PRIMS, tiles <= R_ORDER_MAX_TILES and raster_order_scratch(K, tiles)
+    (csrc/vpn_raster_common.h: K * (R_CULL * 16 + 4) + (K + 2) * 4 + tiles bytes) within the scan's 2 * CM_TILE16 * CM_ROWB bytes
+    of LDS.  TILE_ORDER = False (VPN_TILE_ORDER=0) turns the rider off."""
+    ntile = ((W + 15) // 16) * ((H + 15) // 16)
+    return TILE_ORDER and K <= 64 and ntile <= 16384 and K * 84 + (K + 2) * 4 + ntile <= 24576
+
+
+def _hotpath_sample(params, kinds, cam, gt_points, n, seed_host, seed_dev, sample_base, Hr, Wr, sigma, features, s):
+    """First launch of the one-stream hot path: the sampler, which also writes the raster records of the same primitives for
+    an Hr x Wr image and, when `features`, the features of both clouds that the Chamfer scan's matrix-pipe filter (mode 7)
+    reads from its workspace.  It keeps the seed it used at loss workspace + 8 bytes for the backward launch.  Returns
+    (points [B,K*n,3], records, loss workspace, raster backward workspace, Chamfer workspace)."""
+    B, K, _ = params.shape
+    N, M = K * n, gt_points.shape[1]
+    dev = params.device
+    rec = _workspace('vpn_raster_records_size', B, K, Hr, Wr, dev=dev)
+    lws = _workspace('vpn_raster_loss_workspace', B, Hr, Wr, dev=dev)
+    rws = _workspace('vpn_raster_bwd_workspace', B, K, Hr, Wr, dev=dev)
+    points = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
+    cws = _workspace('vpn_chamfer_workspace', B, N, M, dev=dev)
+    _lib.call('vpn_hotpath_sample_fwd', params, kinds, None, seed_host, seed_dev, int(sample_base), B, K, n, points, cam, Hr, Wr,
+              float(sigma), rec, lws, gt_points, M, cws if features else None, cws.numel() * 4, s)
+    return points, rec, lws, rws, cws
+
+
+def _hotpath_scan(points, gt_points, cws, mode, rider, rec, K, Hr, Wr, s):
+    """The Chamfer scan of the hot path in `mode` of vpn_chamfer_fwd_ws.  With `rider` (see _tile_rider_fits) the launch also
+    prepares the raster's tiles in its tail: one entry per tile wave -- which tile (heaviest first), which primitives it
+    sees, which quadrants each of them reaches -- instead of every tile wave finding that out for itself.  Returns
+    (dist1, idx1, dist2, idx2, the tile entries or None)."""
+    B, N, _ = points.shape
+    M = gt_points.shape[1]
+    d1, i1, d2, i2 = _nn_outputs(B, N, M, points.device)
+    order = None
+    if rider:
+        order = _workspace('vpn_raster_order_size', B, Hr, Wr, dev=points.device, dtype=torch.int64)    # 48-byte tile entries
+        _lib.call('vpn_hotpath_chamfer_fwd', points, gt_points, B, N, M, d1, i1, d2, i2, cws, cws.numel() * 4, mode, rec, K, Hr, Wr,
+                  order, s)
+    else:
+        _lib.call('vpn_chamfer_fwd_ws', points, gt_points, B, N, M, d1, i1, d2, i2, cws, cws.numel() * 4, mode, s)
+    return d1, i1, d2, i2, order
+
+
+def _hotpath_raster_fin(params, kinds, cam, gt_sil, gt_depth, H, W, sigma, gamma, z_far, sil_mse, w_sil, w_depth, rec, lws, rws,
+                        cws, N, M, cd_w1, cd_w2, w_cd, losses, step_counter, order, s):
+    """Last forward launch of the hot path: the raster's forward+backward pass and the loss finalisation (image losses,
+    per-sample Chamfer terms from the mode-7 scan's per-workgroup sums in `cws`, total -> losses [4]; `step_counter`, the
+    device seed, is advanced by one unless None) in ONE launch.  `order`: the scan rider's tile entries, or None."""
+    B, K, _ = params.shape
+    _lib.call('vpn_raster_total_fwd_fin', params, kinds, cam, B, K, H, W, float(sigma), float(gamma), float(z_far), gt_sil,
+              gt_depth, sil_mse, float(w_sil), float(w_depth), rec, lws, rws, 1, cws, cws.numel() * 4, N, M, cd_w1, cd_w2,
+              float(w_cd), losses, None, step_counter, order, s)
+
+
 class HotPathLossFunction(Function):
     """One training-step loss of the reference's hot path in a single autograd node (train.py:243-262):
         total = w_cd * ChamferDistanceLoss(sample(params), gt_points; cd_w1, cd_w2) + w_sil * SilhouetteLoss
@@ -664,89 +718,57 @@ class HotPathLossFunction(Function):
         dev = params.device
         kinds = kinds_tensor(kinds, dev)
         assert kinds.numel() == K and cam.shape == (B, 3) and gt_points.shape[0] == B
-        L = _lib.lib()
         s = _lib.stream()
         seed_host, seed_dev = _seed_args(seed)
         cd_w1, cd_w2, sil_mse = float(cd_w1), float(cd_w2), int(bool(sil_mse))
         gt_sil = _f32c(gt_sil).reshape(B, H, W) if gt_sil is not None else None
         gt_depth = _f32c(gt_depth).reshape(B, H, W) if gt_depth is not None else None
-        rec = torch.empty((L.vpn_raster_records_size(B, K, H, W) // 4,), dtype=torch.float32, device=dev)
-        lws = torch.empty((L.vpn_raster_loss_workspace(B, H, W) // 4,), dtype=torch.float32, device=dev)
-        rws = torch.empty((L.vpn_raster_bwd_workspace(B, K, H, W) // 4,), dtype=torch.float32, device=dev)
         losses = torch.empty((4,), dtype=torch.float32, device=dev)
-
-        def raster_branch(stream, records_ready):
-            _lib.call('vpn_raster_total_fwd', _lib.ptr(params), _lib.ptr(kinds), _lib.ptr(cam), B, K, H, W, float(sigma),
-                      float(gamma), float(z_far), _lib.ptr(gt_sil), _lib.ptr(gt_depth), sil_mse, float(w_sil),
-                      float(w_depth), _lib.ptr(rec), _lib.ptr(lws), _lib.ptr(rws), records_ready, stream)
-
         if advance_seed and seed_dev is None:
             raise ValueError('advance_seed needs a device seed (a CUDA int64 tensor of one element)')
 
-        main = torch.cuda.current_stream()
-        # optionally the raster branch (independent of the sampler + Chamfer branch until the finalisation) runs on a
-        # side stream; fork / join is captured into HIP graphs as such
+        def raster_alone(rec, lws, rws, records_ready, stream):     # the forms whose finalisation is a launch of its own
+            _lib.call('vpn_raster_total_fwd', params, kinds, cam, B, K, H, W, float(sigma), float(gamma), float(z_far), gt_sil,
+                      gt_depth, sil_mse, float(w_sil), float(w_depth), rec, lws, rws, records_ready, stream)
+
         side = _side_stream(dev) if CONCURRENT_BRANCHES else None
-        if side is not None:
+        # fused: the Chamfer scan is the matrix-pipe filter on features that the sampler's launch wrote (mode 7)
+        fused = side is None and bool(_lib.lib().vpn_hotpath_fused_features(B, K, n, M))
+        if side is None:
+            points, rec, lws, rws, cws = _hotpath_sample(params, kinds, cam, gt_points, n, seed_host, seed_dev, sample_base, H, W,
+                                                         sigma, fused, s)
+            d1, i1, d2, i2, order = _hotpath_scan(points, gt_points, cws, 7 if fused else 0, fused and _tile_rider_fits(K, H, W),
+                                                  rec, K, H, W, s)
+            if fused:
+                _hotpath_raster_fin(params, kinds, cam, gt_sil, gt_depth, H, W, sigma, gamma, z_far, sil_mse, w_sil, w_depth, rec,
+                                    lws, rws, cws, N, M, cd_w1, cd_w2, w_cd, losses, seed_dev if advance_seed else None, order, s)
+            else:
+                raster_alone(rec, lws, rws, 1, s)
+        else:
+            # the raster branch (independent of the sampler + Chamfer branch until the finalisation) runs on a side stream;
+            # fork / join is captured into HIP graphs as such
+            main = torch.cuda.current_stream()
+            rec = _workspace('vpn_raster_records_size', B, K, H, W, dev=dev)
+            lws = _workspace('vpn_raster_loss_workspace', B, H, W, dev=dev)
+            rws = _workspace('vpn_raster_bwd_workspace', B, K, H, W, dev=dev)
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                raster_branch(_lib.stream(), 0)
+                raster_alone(rec, lws, rws, 0, _lib.stream())
                 for t in (params, kinds, cam, gt_sil, gt_depth, rec, lws, rws):
                     if t is not None:
                         t.record_stream(side)
-        points = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
-        cws = torch.empty((L.vpn_chamfer_workspace(B, N, M) // 4,), dtype=torch.float32, device=dev)
-        chamfer_mode = 0
-        ntile = ((W + 15) // 16) * ((H + 15) // 16)
-        use_order = False
-        if side is None:        # one stream: the sampler's launch also writes the raster records of the same primitives
-            # ... and, when the Chamfer scan will be the matrix-pipe filter, that filter's features of both clouds
-            fused = bool(L.vpn_hotpath_fused_features(B, K, n, M))
-            # the scan launch can carry a rider that tests the tiles against the primitives and sorts them by weight
-            use_order = fused and TILE_ORDER and K <= 64 and ntile <= 16384 and K * 84 + (K + 2) * 4 + ntile <= 24576
-            _lib.call('vpn_hotpath_sample_fwd', _lib.ptr(params), _lib.ptr(kinds), None, seed_host, seed_dev,
-                      int(sample_base), B, K, n, _lib.ptr(points), _lib.ptr(cam), H, W, float(sigma),
-                      _lib.ptr(rec),
-                      _lib.ptr(lws), _lib.ptr(gt_points), M, _lib.ptr(cws) if fused else None, cws.numel() * 4, s)
-            chamfer_mode = 7 if fused else 0
-        else:
-            _lib.call('vpn_sample_fwd', _lib.ptr(params), _lib.ptr(kinds), None, seed_host, seed_dev, int(sample_base), B,
-                      K, n, _lib.ptr(points), s)
-        d1 = torch.empty((B, N), dtype=torch.float32, device=dev)
-        d2 = torch.empty((B, M), dtype=torch.float32, device=dev)
-        i1 = torch.empty((B, N), dtype=torch.int32, device=dev)
-        i2 = torch.empty((B, M), dtype=torch.int32, device=dev)
-        fused_fin = side is None and chamfer_mode == 7
-        order = None
-        if use_order:
-            # the scan launch also prepares the raster's tiles (a rider in its tail): one entry per tile wave -- which tile
-            # (heaviest first), which primitives it sees, which quadrants each of them reaches -- instead of every tile wave
-            # finding that out for itself
-            order = torch.empty((L.vpn_raster_order_size(B, H, W) // 8,), dtype=torch.int64, device=dev)   # 48-byte tile entries
-            _lib.call('vpn_hotpath_chamfer_fwd', _lib.ptr(points), _lib.ptr(gt_points), B, N, M, _lib.ptr(d1), _lib.ptr(i1),
-                      _lib.ptr(d2), _lib.ptr(i2), _lib.ptr(cws), cws.numel() * 4, chamfer_mode, _lib.ptr(rec), K, H, W,
-                      _lib.ptr(order), s)
-        else:
-            _lib.call('vpn_chamfer_fwd_ws', _lib.ptr(points), _lib.ptr(gt_points), B, N, M, _lib.ptr(d1), _lib.ptr(i1),
-                      _lib.ptr(d2), _lib.ptr(i2), _lib.ptr(cws), cws.numel() * 4, chamfer_mode, s)
-        if fused_fin:
-            # raster forward+backward pass and the loss finalisation (image losses, per-sample Chamfer terms from the
-            # scan's per-workgroup sums, total, optional advance of the step counter) in ONE launch
-            _lib.call('vpn_raster_total_fwd_fin', _lib.ptr(params), _lib.ptr(kinds), _lib.ptr(cam), B, K, H, W, float(sigma),
-                      float(gamma), float(z_far), _lib.ptr(gt_sil), _lib.ptr(gt_depth), sil_mse, float(w_sil),
-                      float(w_depth), _lib.ptr(rec), _lib.ptr(lws), _lib.ptr(rws), 1, _lib.ptr(cws), cws.numel() * 4, N, M,
-                      cd_w1, cd_w2, float(w_cd), _lib.ptr(losses), None, seed_dev if advance_seed else None, _lib.ptr(order), s)
-        else:
-            if side is not None:
-                main.wait_stream(side)
-            else:
-                raster_branch(s, 1)
-            _lib.call('vpn_loss_finalize', _lib.ptr(lws), B, H, W, _lib.ptr(d1), _lib.ptr(d2), N, M, cd_w1, cd_w2, float(w_cd),
-                      float(w_sil), float(w_depth), _lib.ptr(losses), None, s)
+            points = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
+            cws = _workspace('vpn_chamfer_workspace', B, N, M, dev=dev)
+            _lib.call('vpn_sample_fwd', params, kinds, None, seed_host, seed_dev, int(sample_base), B, K, n, points, s)
+            d1, i1, d2, i2, _ = _hotpath_scan(points, gt_points, cws, 0, False, None, K, H, W, s)
+            main.wait_stream(side)
+        if not fused:
+            _lib.call('vpn_loss_finalize', lws, B, H, W, d1, d2, N, M, cd_w1, cd_w2, float(w_cd), float(w_sil), float(w_depth),
+                      losses, None, s)
         pattern = _grad_pattern(B, w_cd, dev)
         empty = torch.empty(0, device=dev)
         seed_t = seed if isinstance(seed, torch.Tensor) else empty
-        if advance_seed and not fused_fin:
+        if advance_seed and not fused:
             # the side-stream / unfused form advances the caller's counter here; when the sampler launch did not keep the
             # seed it used (side stream), the backward must not read the advanced counter: it gets a copy of the old one
             if not (side is None and seed_dev is not None):
@@ -774,7 +796,7 @@ class HotPathLossFunction(Function):
         if seed_saved:                                          # seed_t is the loss workspace: effective seed at byte 8
             seed_dev = ctypes.c_void_p(seed_t.data_ptr() + 8)
         elif has_seed_dev:
-            seed_dev = _lib.ptr(seed_t)
+            seed_dev = seed_t
         if grad_total is None:                                  # the total was not used (set_materialize_grads(False))
             return (None,) * 21
         grad_total = _f32c(grad_total).reshape(1)
@@ -783,21 +805,16 @@ class HotPathLossFunction(Function):
         if M <= FUSED_BWD_MAX_GT:          # ... and the raster's finishing step rides in the same launch
             # d total / d loss_b = (w_cd / B) * grad_total for every sample: the constant goes into the two Chamfer
             # weights and the kernel reads grad_total itself (no ATen kernel between autograd and the launch)
-            _lib.call('vpn_hotpath_bwd', _lib.ptr(params), _lib.ptr(kinds), None, seed, seed_dev, base, B, K, n,
-                      _lib.ptr(points), _lib.ptr(gt_points), M, _lib.ptr(d1), _lib.ptr(i1), _lib.ptr(d2), _lib.ptr(i2),
-                      None, cd_w1 * w_cd_over_b, cd_w2 * w_cd_over_b, _lib.ptr(cam), H, W, _lib.ptr(rec), _lib.ptr(rws),
-                      _lib.ptr(grad_total), _lib.ptr(grad_params), s)
+            _lib.call('vpn_hotpath_bwd', params, kinds, None, seed, seed_dev, base, B, K, n, points, gt_points, M, d1, i1, d2, i2,
+                      None, cd_w1 * w_cd_over_b, cd_w2 * w_cd_over_b, cam, H, W, rec, rws, grad_total, grad_params, s)
             return (grad_params,) + (None,) * 20
         else:                                                   # GT clouds beyond the fused kernel's LDS match lists
             gvec = pattern * grad_total                         # d total / d loss_b [B]
             grad_points = torch.empty_like(points)
-            _lib.call('vpn_chamfer_bwd', _lib.ptr(points), _lib.ptr(gt_points), _lib.ptr(d1), _lib.ptr(i1), _lib.ptr(d2),
-                      _lib.ptr(i2), _lib.ptr(gvec), B, N, M, cd_w1, cd_w2, _lib.ptr(grad_points), None, s)
-            _lib.call('vpn_sample_bwd', _lib.ptr(params), _lib.ptr(kinds), None, seed, seed_dev, base, B, K, n,
-                      _lib.ptr(grad_points), _lib.ptr(grad_params), s)
+            _lib.call('vpn_chamfer_bwd', points, gt_points, d1, i1, d2, i2, gvec, B, N, M, cd_w1, cd_w2, grad_points, None, s)
+            _lib.call('vpn_sample_bwd', params, kinds, None, seed, seed_dev, base, B, K, n, grad_points, grad_params, s)
         # the raster's gradient partials were produced by the forward launch: chain rule x upstream gradient, added
-        _lib.call('vpn_raster_total_bwd', _lib.ptr(params), _lib.ptr(cam), B, K, H, W, _lib.ptr(rec), _lib.ptr(rws),
-                  _lib.ptr(grad_total), _lib.ptr(grad_params), 1, s)
+        _lib.call('vpn_raster_total_bwd', params, cam, B, K, H, W, rec, rws, grad_total, grad_params, 1, s)
         return (grad_params,) + (None,) * 20
 
 
@@ -841,14 +858,13 @@ class TrainStepLossFunction(Function):
         kinds = kinds_tensor(kinds, dev)
         w_view, w_can, w_sil, w_div, w_emd = (float(x) for x in weights)
         cd_w1, cd_w2, sil_mse = float(cd_w1), float(cd_w2), int(bool(sil_mse))
-        L = _lib.lib()
         s = _lib.stream()
         seed_host, seed_dev = _seed_args(seed)
         if advance_seed and seed_dev is None:
             raise ValueError('advance_seed needs a device seed (a CUDA int64 tensor of one element)')
         if w_emd and N != M:
             raise ValueError('the EMD term needs as many predicted as ground-truth points (emd_module.py:36): %d vs %d' % (N, M))
-        if not L.vpn_hotpath_fused_features(B, K, n, M):
+        if not _lib.lib().vpn_hotpath_fused_features(B, K, n, M):
             raise ValueError('TrainStepLossFunction needs a shape the fused sampler / Chamfer path takes (K <= 64, large clouds)')
         f32 = dict(dtype=torch.float32, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
@@ -858,18 +874,10 @@ class TrainStepLossFunction(Function):
         sigma, gamma, z_far = config.RASTER_SIGMA, config.RASTER_GAMMA, config.RASTER_Z_FAR
         # the render's buffers exist (tiny) even when the silhouette term is off: the sampler launch writes the records
         Hr, Wr = (H, W) if render else (16, 16)
-        rec = torch.empty((L.vpn_raster_records_size(B, K, Hr, Wr) // 4,), **f32)
-        lws = torch.empty((L.vpn_raster_loss_workspace(B, Hr, Wr) // 4,), **f32)
-        rws = torch.empty((L.vpn_raster_bwd_workspace(B, K, Hr, Wr) // 4,), **f32)
         hot = torch.empty((4,), **f32)
-        points = torch.empty((B, N, 3), **f32)
-        cws = torch.empty((L.vpn_chamfer_workspace(B, N, M) // 4,), **f32)
-        d1, d2 = torch.empty((B, N), **f32), torch.empty((B, M), **f32)
-        i1, i2 = torch.empty((B, N), **i32), torch.empty((B, M), **i32)
         # ---- hot path: sampler (+ records + features) -> view-centred Chamfer (+ tile rider) -> raster + finalisation
-        _lib.call('vpn_hotpath_sample_fwd', _lib.ptr(params), _lib.ptr(kinds), None, seed_host, seed_dev, int(sample_base), B, K, n,
-                  _lib.ptr(points), _lib.ptr(cam), Hr, Wr, float(sigma), _lib.ptr(rec), _lib.ptr(lws), _lib.ptr(gt_view), M,
-                  _lib.ptr(cws), cws.numel() * 4, s)
+        points, rec, lws, rws, cws = _hotpath_sample(params, kinds, cam, gt_view, n, seed_host, seed_dev, sample_base, Hr, Wr,
+                                                     sigma, True, s)
         # ---- EMD auction on the sampled cloud (train.py:193).  On a second stream when EMD_SIDE_STREAM: it needs only the
         #      sampler's points, nothing needs it before the final sums, and its workgroups (one per CU, 16 waves) leave
         #      every CU half of its wave slots and 32 KB of LDS -- the Chamfer scans and the raster run beside it
@@ -878,35 +886,22 @@ class TrainStepLossFunction(Function):
         if w_emd:
             emd_dist = torch.empty((B, N), **f32)
             emd_assign = torch.empty((B, N), **i32)
-            ews = torch.empty((max(1, L.vpn_emd_workspace(B, N) // 4),), **f32)
+            ews = _workspace('vpn_emd_workspace', B, N, dev=dev, floor=1)
             es = s
             if EMD_SIDE_STREAM:
                 main = torch.cuda.current_stream()
                 side = _side_stream(dev)
                 side.wait_stream(main)
                 es = ctypes.c_void_p(side.cuda_stream)
-            _lib.call('vpn_emd_fwd_ex', _lib.ptr(points), _lib.ptr(gt_view), B, N, float(eps), int(iters), _lib.ptr(emd_dist),
-                      _lib.ptr(emd_assign), _lib.ptr(ews), 1 if CONCURRENT_BRANCHES else int(os.environ.get('VPN_EMD_GROUP', '0')), es,
-                      EMD_TEST_GIVEUP_MASK)
-        ntile = ((Wr + 15) // 16) * ((Hr + 15) // 16)
-        use_order = render and TILE_ORDER and K <= 64 and ntile <= 16384 and K * 84 + (K + 2) * 4 + ntile <= 24576
-        order = None
-        if use_order:
-            order = torch.empty((L.vpn_raster_order_size(B, Hr, Wr) // 8,), dtype=torch.int64, device=dev)
-            _lib.call('vpn_hotpath_chamfer_fwd', _lib.ptr(points), _lib.ptr(gt_view), B, N, M, _lib.ptr(d1), _lib.ptr(i1), _lib.ptr(d2),
-                      _lib.ptr(i2), _lib.ptr(cws), cws.numel() * 4, 7, _lib.ptr(rec), K, Hr, Wr, _lib.ptr(order), s)
-        else:
-            _lib.call('vpn_chamfer_fwd_ws', _lib.ptr(points), _lib.ptr(gt_view), B, N, M, _lib.ptr(d1), _lib.ptr(i1), _lib.ptr(d2),
-                      _lib.ptr(i2), _lib.ptr(cws), cws.numel() * 4, 7, s)
+            _lib.call('vpn_emd_fwd_ex', points, gt_view, B, N, float(eps), int(iters), emd_dist, emd_assign, ews, _emd_group(None),
+                      es, EMD_TEST_GIVEUP_MASK)
+        d1, i1, d2, i2, order = _hotpath_scan(points, gt_view, cws, 7, render and _tile_rider_fits(K, Hr, Wr), rec, K, Hr, Wr, s)
         if render:
-            _lib.call('vpn_raster_total_fwd_fin', _lib.ptr(params), _lib.ptr(kinds), _lib.ptr(cam), B, K, H, W, float(sigma), float(gamma),
-                      float(z_far), _lib.ptr(gt_sil), None, sil_mse, w_sil, 0.0, _lib.ptr(rec), _lib.ptr(lws), _lib.ptr(rws), 1,
-                      _lib.ptr(cws), cws.numel() * 4, N, M, cd_w1, cd_w2, w_view, _lib.ptr(hot), None,
-                      seed_dev if advance_seed else None, _lib.ptr(order), s)
+            _hotpath_raster_fin(params, kinds, cam, gt_sil, None, H, W, sigma, gamma, z_far, sil_mse, w_sil, 0.0, rec, lws, rws,
+                                cws, N, M, cd_w1, cd_w2, w_view, hot, seed_dev if advance_seed else None, order, s)
         else:
             # train.py:167: no render; the Chamfer term alone (H = W = 0: no image losses)
-            _lib.call('vpn_loss_finalize', _lib.ptr(lws), B, 0, 0, _lib.ptr(d1), _lib.ptr(d2), N, M, cd_w1, cd_w2, w_view, 0.0, 0.0,
-                      _lib.ptr(hot), None, s)
+            _lib.call('vpn_loss_finalize', lws, B, 0, 0, d1, d2, N, M, cd_w1, cd_w2, w_view, 0.0, 0.0, hot, None, s)
             if advance_seed:
                 raise ValueError('advance_seed rides in the raster launch: it needs the silhouette term (L_SIL != 0)')
         # ---- object-centred Chamfer (train.py:158-161): computed even at weight 0, like the reference
@@ -916,35 +911,29 @@ class TrainStepLossFunction(Function):
             Mc = gt_canon.shape[1]
             cam4 = [_f32c(c.reshape(-1)) for c in (dists, elevs, azims, angles)]
             canon = torch.empty_like(points)
-            _lib.call('vpn_camera_transform_fwd', _lib.ptr(points), _lib.ptr(cam4[0]), _lib.ptr(cam4[1]), _lib.ptr(cam4[2]),
-                      _lib.ptr(cam4[3]), B, N, 1, _lib.ptr(canon), s)
-            cd1, cd2 = torch.empty((B, N), **f32), torch.empty((B, Mc), **f32)
-            ci1, ci2 = torch.empty((B, N), **i32), torch.empty((B, Mc), **i32)
-            ccws = torch.empty((L.vpn_chamfer_workspace(B, N, Mc) // 4,), **f32)
-            _lib.call('vpn_chamfer_fwd_ws', _lib.ptr(canon), _lib.ptr(gt_canon), B, N, Mc, _lib.ptr(cd1), _lib.ptr(ci1), _lib.ptr(cd2),
-                      _lib.ptr(ci2), _lib.ptr(ccws), ccws.numel() * 4, 0, s)
+            _lib.call('vpn_camera_transform_fwd', points, cam4[0], cam4[1], cam4[2], cam4[3], B, N, 1, canon, s)
+            cd1, ci1, cd2, ci2 = _nn_outputs(B, N, Mc, dev)
+            ccws = _workspace('vpn_chamfer_workspace', B, N, Mc, dev=dev)
+            _lib.call('vpn_chamfer_fwd_ws', canon, gt_canon, B, N, Mc, cd1, ci1, cd2, ci2, ccws, ccws.numel() * 4, 0, s)
             mat = None
             if w_can:
                 mat = torch.empty((B, 9), **f32)
-                _lib.call('vpn_camera_matrix', _lib.ptr(cam4[0]), _lib.ptr(cam4[1]), _lib.ptr(cam4[2]), _lib.ptr(cam4[3]), B, 1,
-                          _lib.ptr(mat), s)
+                _lib.call('vpn_camera_matrix', cam4[0], cam4[1], cam4[2], cam4[3], B, 1, mat, s)
             cn = (canon, gt_canon, mat, cd1, ci1, cd2, ci2, Mc)
         # ---- VP-diversity (train.py:185)
         dv = dws = None
         if w_div:
-            dv = (torch.empty((B, K), **f32), torch.empty((B, K), **i32), torch.empty((B, M), **f32), torch.empty((B, M), **i32))
-            dws = torch.empty((L.vpn_vpdiv_workspace(B, K) // 8,), dtype=torch.int64, device=dev)
+            dv = _nn_outputs(B, K, M, dev)
+            dws = _workspace('vpn_vpdiv_workspace', B, K, dev=dev, dtype=torch.int64)
             # the centres' direction stays in the workspace: the finalisation's per-sample pass merges it
-            _lib.call('vpn_vpdiv_fwd', _lib.ptr(params), _lib.ptr(gt_view), B, K, M, None, None, _lib.ptr(dv[2]),
-                      _lib.ptr(dv[3]), _lib.ptr(dws), s)
+            _lib.call('vpn_vpdiv_fwd', params, gt_view, B, K, M, None, None, dv[2], dv[3], dws, s)
         out = torch.empty((6,), **f32)
         if side is not None:
             torch.cuda.current_stream().wait_stream(side)
-        fws = torch.empty((L.vpn_trainstep_workspace(B) // 4,), **f32)
-        _lib.call('vpn_trainstep_finalize', _lib.ptr(hot), _lib.ptr(emd_dist), _lib.ptr(cn[3]) if cn else None,
-                  _lib.ptr(cn[5]) if cn else None, None, _lib.ptr(dv[2]) if dv else None, B, N, M,
-                  cn[7] if cn else 0, K, w_view, w_can, w_sil if render else 0.0, w_div, w_emd, cd_w1, cd_w2, _lib.ptr(fws),
-                  _lib.ptr(dws) if dv else None, _lib.ptr(dv[0]) if dv else None, _lib.ptr(dv[1]) if dv else None, _lib.ptr(out), s)
+        fws = _workspace('vpn_trainstep_workspace', B, dev=dev)
+        _lib.call('vpn_trainstep_finalize', hot, emd_dist, cn[3] if cn else None, cn[5] if cn else None, None,
+                  dv[2] if dv else None, B, N, M, cn[7] if cn else 0, K, w_view, w_can, w_sil if render else 0.0, w_div, w_emd,
+                  cd_w1, cd_w2, fws, dws, dv[0] if dv else None, dv[1] if dv else None, out, s)
         ctx.meta = (B, K, n, M, H, W, seed_host, int(sample_base), cd_w1, cd_w2, w_view, w_can, w_div, w_emd, render,
                     seed_dev is not None, cn[7] if cn else 0)
         # the sampler's launch keeps the seed it used at loss_ws + 8: backward reads it from there
@@ -962,22 +951,17 @@ class TrainStepLossFunction(Function):
             return (None,) * 21
         (B, K, n, M, H, W, seed_host, base, cd_w1, cd_w2, w_view, w_can, w_div, w_emd, render, has_seed_dev, Mc) = ctx.meta
         N = K * n
-        p = _lib.ptr
         g = _f32c(grad_total).reshape(1)
         grad_params = torch.empty_like(t['params'])
         seed_dev = ctypes.c_void_p(t['lws'].data_ptr() + 8) if has_seed_dev else None
-        dv, cn = t['dv'], t['cn']
-        _lib.call('vpn_trainstep_bwd', p(t['params']), p(t['kinds']), 0 if has_seed_dev else seed_host, seed_dev, base, B, K, n,
-                  p(t['points']), p(t['gt_view']), M, p(t['d1']), p(t['i1']), p(t['d2']), p(t['i2']),
-                  cd_w1 * w_view / B, cd_w2 * w_view / B, p(t['cam']), H, W, p(t['rec']) if render else None,
-                  p(t['rws']) if render else None, p(g),
-                  p(t['emd_dist']) if w_emd else None, p(t['emd_assign']) if w_emd else None, w_emd / (B * N),
-                  p(dv[0]) if dv else None, p(dv[1]) if dv else None, p(dv[2]) if dv else None, p(dv[3]) if dv else None,
-                  w_div * 0.5 / (K * B), w_div * 1.0 / (M * B),
-                  p(cn[0]) if cn else None, p(cn[1]) if cn else None, p(cn[2]) if cn else None, p(cn[3]) if cn else None,
-                  p(cn[4]) if cn else None, p(cn[5]) if cn else None, p(cn[6]) if cn else None,
-                  (w_can * cd_w1 / (N * B)) if cn else 0.0, (w_can * cd_w2 / (Mc * B)) if cn else 0.0, Mc if cn else 0,
-                  p(grad_params), _lib.stream())
+        has_cn = t['cn'] is not None
+        dv, cn = t['dv'] or (None,) * 4, t['cn'] or (None,) * 7       # a term that is off: NULL for each of its tensors
+        _lib.call('vpn_trainstep_bwd', t['params'], t['kinds'], 0 if has_seed_dev else seed_host, seed_dev, base, B, K, n,
+                  t['points'], t['gt_view'], M, t['d1'], t['i1'], t['d2'], t['i2'], cd_w1 * w_view / B, cd_w2 * w_view / B,
+                  t['cam'], H, W, t['rec'] if render else None, t['rws'] if render else None, g,
+                  t['emd_dist'], t['emd_assign'], w_emd / (B * N), *dv, w_div * 0.5 / (K * B), w_div * 1.0 / (M * B), *cn[:7],
+                  (w_can * cd_w1 / (N * B)) if has_cn else 0.0, (w_can * cd_w2 / (Mc * B)) if has_cn else 0.0, Mc if has_cn else 0,
+                  grad_params, _lib.stream())
         return (grad_params,) + (None,) * 20
 
 
@@ -1048,9 +1032,9 @@ def gcn_graph(faces, n, device):
 
 
 def _colsum(x, mask, S, R, ld, off, C):
-    ws = torch.empty((_lib.lib().vpn_gcn_colsum_workspace(S, R, C) // 4,), dtype=torch.float32, device=x.device)
+    ws = _workspace('vpn_gcn_colsum_workspace', S, R, C, dev=x.device)
     out = torch.empty((S, C), dtype=torch.float32, device=x.device)
-    _lib.call('vpn_gcn_colsum', _lib.ptr(x), _lib.ptr(mask), S, R, ld, off, C, _lib.ptr(ws), _lib.ptr(out), _lib.stream())
+    _lib.call('vpn_gcn_colsum', x, mask, S, R, ld, off, C, ws, out, _lib.stream())
     return out
 
 
@@ -1065,8 +1049,7 @@ class GcnAggregateFunction(Function):
         assert row_ptr.numel() == N + 1, 'graph has %d vertices, features %d' % (row_ptr.numel() - 1, N)
         b = _f32c(bias) if bias is not None else None
         y = torch.empty_like(h)
-        _lib.call('vpn_gcn_aggregate', _lib.ptr(h), _lib.ptr(row_ptr), _lib.ptr(col), _lib.ptr(w), _lib.ptr(b), None, B, N, C,
-                  int(bool(relu)), _lib.ptr(y), _lib.stream())
+        _lib.call('vpn_gcn_aggregate', h, row_ptr, col, w, b, None, B, N, C, int(bool(relu)), y, _lib.stream())
         ctx.save_for_backward(row_ptr, col, w, y if relu else None)
         ctx.meta = (B, N, C, bias is not None)
         return y
@@ -1079,8 +1062,7 @@ class GcnAggregateFunction(Function):
         gh = gb = None
         if ctx.needs_input_grad[0]:
             gh = torch.empty_like(g)
-            _lib.call('vpn_gcn_aggregate', _lib.ptr(g), _lib.ptr(row_ptr), _lib.ptr(col), _lib.ptr(w), None, _lib.ptr(y),
-                      B, N, C, 0, _lib.ptr(gh), _lib.stream())
+            _lib.call('vpn_gcn_aggregate', g, row_ptr, col, w, None, y, B, N, C, 0, gh, _lib.stream())
         if has_bias and ctx.needs_input_grad[1]:
             gb = _colsum(g, y, 1, B * N, C, 0, C).reshape(C)
         return gh, gb, None, None, None, None
@@ -1093,7 +1075,7 @@ def gcn_bounds(rgbs):
     assert img.dim() == 4
     B, C, H, W = img.shape
     out = torch.empty((B, 4), dtype=torch.float32, device=img.device)
-    _lib.call('vpn_gcn_bounds', _lib.ptr(img), B, C, H, W, _lib.ptr(out), _lib.stream())
+    _lib.call('vpn_gcn_bounds', img, B, C, H, W, out, _lib.stream())
     return out
 
 
@@ -1132,10 +1114,10 @@ class GcnInputFunction(Function):
             ext = torch.empty((B, 4), dtype=torch.float32, device=dev)
             ext_idx = torch.empty((B, 4), dtype=torch.int32, device=dev)
             grid = torch.empty((B, N, 2), dtype=torch.float32, device=dev)
-            mws = torch.empty((_lib.lib().vpn_gcn_maps_workspace(B, L, *dims) // 4,), dtype=torch.float32, device=dev)
-        fp = [_lib.ptr(maps[l]) if l < L else None for l in range(4)]
-        _lib.call('vpn_gcn_input_fwd', _lib.ptr(verts), _lib.ptr(bounds) if L else None, _lib.ptr(gf), B, N, G, int(venc), L,
-                  *fp, *dims, _lib.ptr(ext), _lib.ptr(ext_idx), _lib.ptr(grid), _lib.ptr(mws), _lib.ptr(out), _lib.stream())
+            mws = _workspace('vpn_gcn_maps_workspace', B, L, *dims, dev=dev)
+        fp = [maps[l] if l < L else None for l in range(4)]
+        _lib.call('vpn_gcn_input_fwd', verts, bounds if L else None, gf, B, N, G, int(venc), L, *fp, *dims, ext, ext_idx, grid,
+                  mws, out, _lib.stream())
         ctx.save_for_backward(verts, bounds if L else None, ext, ext_idx, grid, mws)
         ctx.meta = (B, N, G, int(venc), L, dims, [tuple(m.shape) for m in maps])
         return out
@@ -1151,11 +1133,9 @@ class GcnInputFunction(Function):
         gv = torch.empty((B, N, 3), dtype=torch.float32, device=dev) if need_v else None
         gm = [torch.empty(s, dtype=torch.float32, device=dev) for s in shapes] if need_m else []
         if need_v or need_m:
-            ws = torch.empty((max(_lib.lib().vpn_gcn_input_bwd_workspace(B, N, L, *dims), 4) // 4,), dtype=torch.float32,
-                             device=dev)
-            fp = [_lib.ptr(gm[l]) if l < len(gm) else None for l in range(4)]
-            _lib.call('vpn_gcn_input_bwd', _lib.ptr(g), _lib.ptr(verts), _lib.ptr(bounds), B, N, G, venc, L, *dims,
-                      _lib.ptr(ext), _lib.ptr(ext_idx), _lib.ptr(grid), _lib.ptr(mws), _lib.ptr(ws), _lib.ptr(gv), *fp,
+            ws = _workspace('vpn_gcn_input_bwd_workspace', B, N, L, *dims, dev=dev, floor=1)
+            fp = [gm[l] if l < len(gm) else None for l in range(4)]
+            _lib.call('vpn_gcn_input_bwd', g, verts, bounds, B, N, G, venc, L, *dims, ext, ext_idx, grid, mws, ws, gv, *fp,
                       _lib.stream())
         gg = None
         if G and ctx.needs_input_grad[2]:
@@ -1203,9 +1183,8 @@ def cutmix_points(points, indices, cut, seed, sample_base=0, n_out=None):
     out = torch.empty((B, n_out, 3), dtype=torch.float32, device=dev)
     src = torch.empty((B, n_out), dtype=torch.int32, device=dev)
     count = torch.empty((B,), dtype=torch.int32, device=dev)
-    _lib.call('vpn_cutmix_points', _lib.ptr(points), _lib.ptr(indices), _lib.ptr(cut_t), float(cut),
-              int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_base), B, N, n_out, _lib.ptr(out), _lib.ptr(src), _lib.ptr(count),
-              _lib.stream())
+    _lib.call('vpn_cutmix_points', points, indices, cut_t, float(cut), int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_base), B, N,
+              n_out, out, src, count, _lib.stream())
     return out, src, count
 
 
@@ -1221,8 +1200,7 @@ def cutmix_images(rgbs, silhouettes, indices, cut_index):
         assert silhouettes.size(0) == B and silhouettes.shape[2:] == rgbs.shape[2:]
         Cb = silhouettes.size(1)
         out_b = torch.empty_like(silhouettes)
-    _lib.call('vpn_cutmix_images', _lib.ptr(rgbs), _lib.ptr(silhouettes), _lib.ptr(indices), B, Ca, Cb, H, W, int(cut_index),
-              _lib.ptr(out_a), _lib.ptr(out_b), _lib.stream())
+    _lib.call('vpn_cutmix_images', rgbs, silhouettes, indices, B, Ca, Cb, H, W, int(cut_index), out_a, out_b, _lib.stream())
     return out_a, out_b
 
 
@@ -1234,17 +1212,14 @@ def mixup_points(points, indices, ratio, eps=0.005, iters=100, max_group=None):
     B, n, _ = points.shape
     dev = points.device
     partner = torch.empty_like(points)
-    _lib.call('vpn_mixup_gather', _lib.ptr(points), _lib.ptr(indices), B, n, _lib.ptr(partner), _lib.stream())
+    _lib.call('vpn_mixup_gather', points, indices, B, n, partner, _lib.stream())
     dist = torch.empty((B, n), dtype=torch.float32, device=dev)
     assignment = torch.empty((B, n), dtype=torch.int32, device=dev)
-    ws = torch.empty((max(1, _lib.lib().vpn_emd_workspace(B, n) // 4),), dtype=torch.float32, device=dev)
-    if max_group is None:
-        max_group = 1 if CONCURRENT_BRANCHES else int(os.environ.get('VPN_EMD_GROUP', '0'))
-    _lib.call('vpn_emd_fwd_ex', _lib.ptr(points), _lib.ptr(partner), B, n, float(eps), int(iters), _lib.ptr(dist),
-              _lib.ptr(assignment), _lib.ptr(ws), int(max_group), _lib.stream(), EMD_TEST_GIVEUP_MASK)
+    ws = _workspace('vpn_emd_workspace', B, n, dev=dev, floor=1)
+    _lib.call('vpn_emd_fwd_ex', points, partner, B, n, float(eps), int(iters), dist, assignment, ws, _emd_group(max_group),
+              _lib.stream(), EMD_TEST_GIVEUP_MASK)
     ratio = float(ratio)
     mixed = torch.empty_like(points)
     # (1 - r) and r as torch rounds the two Python doubles of point_mixup.py:36 to fp32
-    _lib.call('vpn_mixup_lerp', _lib.ptr(points), _lib.ptr(partner), _lib.ptr(assignment), B, n, 1.0 - ratio, ratio,
-              _lib.ptr(mixed), _lib.stream())
+    _lib.call('vpn_mixup_lerp', points, partner, assignment, B, n, 1.0 - ratio, ratio, mixed, _lib.stream())
     return mixed, dist, assignment
