@@ -1,0 +1,84 @@
+"""The evaluation loops of the reference on the drop-in surface, with stand-in networks and synthetic data.
+
+    python examples/eval_step.py [--batches 6] [--batch 8]          # test.py:68-135: Chamfer only
+    python examples/eval_step.py --gcn                              # test_gcn.py:115-178: Chamfer + EMD on refined vertices
+
+The trained networks, the dataset and the visual dumps are out of scope; what the loops do with a batch is
+the reference's, under torch.no_grad():
+
+    test.py       head -> Sampling (16 x 128 points) -> ChamferDistanceLoss(each_batch=True) * L_VIEW_CD   test.py:93-102
+    test_gcn.py   VPN -> sphere meshes -> GCNModel (2048 vertices) -> Chamfer + sqrt(EMD dist).mean(1)     test_gcn.py:136-143
+    bookkeeping   batch means, per-class sums and counts, the table at the end                             EvaluationMeter
+
+The class indices cycle over the reference's 13 ShapeNet classes; the last batch is short."""
+import argparse
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import vpn_amd  # noqa: E402
+from examples.train_gcn_step import StandInVPN, compose_vp_meshes, get_vp_meshes  # noqa: E402
+from examples.train_step import Heads  # noqa: E402
+from vpn_amd.modules.network import GCNModel  # noqa: E402
+
+CLASS_NAMES = ['airplane', 'rifle', 'display', 'table', 'telephone', 'car', 'chair', 'bench', 'lamp', 'cabinet', 'loudspeaker',
+               'sofa', 'watercraft']
+L_VIEW_CD = 1.0
+VP_NUM, SAMPLE_NUM = 16, 128
+
+
+def batches(n, B):
+    """(batch size, class indices as a DataLoader yields them) of n batches, the last one short."""
+    seen = 0
+    for k in range(n):
+        b = B if k < n - 1 or B < 3 else B - 3
+        yield b, torch.arange(seen, seen + b) % len(CLASS_NAMES)
+        seen += b
+
+
+@torch.no_grad()
+def test(args, dev):
+    model = Heads(64, VP_NUM).to(dev).eval()
+    kinds = [vpn_amd.SPHERE] * VP_NUM
+    meter = vpn_amd.EvaluationMeter(CLASS_NAMES, dev, emd=False, cd_scale=L_VIEW_CD)
+    for it, (b, class_indices) in enumerate(batches(args.batches, args.batch)):
+        feats = torch.randn(b, 64, device=dev)
+        view_points = (torch.rand(b, VP_NUM * SAMPLE_NUM, 3, device=dev) - 0.5) * 0.8
+        params = vpn_amd.pack_head_outputs(*model(feats))
+        predict_points = vpn_amd.Sampling.sample_primitives(params, kinds, SAMPLE_NUM, seed=100 + it)
+        meter.update(predict_points, view_points, class_indices)
+    return meter.report(args.epoch)
+
+
+@torch.no_grad()
+def test_gcn(args, dev):
+    vpn = StandInVPN().to(dev).eval()
+    gcn = GCNModel().to(dev).eval()
+    meter = vpn_amd.EvaluationMeter(CLASS_NAMES, dev, emd=True)
+    for b, class_indices in batches(args.batches, args.batch):
+        rgbs = torch.zeros(b, 3, 128, 128, device=dev)
+        rgbs[:, :, 24:104, 16:112] = torch.rand(b, 3, 80, 96, device=dev)
+        gt_points = (torch.rand(b, VP_NUM * 128, 3, device=dev) - 0.5) * 0.8
+        volumes, rotates, translates, perceptual_features, global_features = vpn(rgbs)
+        predict_meshes = compose_vp_meshes(get_vp_meshes(volumes, rotates, translates))
+        predict_vertices = gcn(predict_meshes, rgbs, perceptual_features, global_features)
+        meter.update(predict_vertices, gt_points, class_indices)
+    return meter.report(args.epoch)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--gcn', action='store_true', help='the test_gcn.py loop (Chamfer + EMD on the refined vertices)')
+    ap.add_argument('--batches', type=int, default=6)
+    ap.add_argument('--batch', type=int, default=8)
+    ap.add_argument('--epoch', type=int, default=0)
+    args = ap.parse_args(argv)
+    torch.manual_seed(1234)
+    dev = torch.device('cuda')
+    return (test_gcn if args.gcn else test)(args, dev)
+
+
+if __name__ == '__main__':
+    main()

@@ -34,12 +34,12 @@
 extern "C" {
 #endif
 
-/* 8: the batch augmentation stage (vpn_cutmix_*, vpn_mixup_*).  7: the GCN refinement stage (vpn_gcn_*).  6: vpn_emd_fwd_ex, vpn_emd_recovered_samples, vpn_emd_last_group.
+/* 9: the evaluation stage (vpn_eval_state_size, vpn_eval_accumulate).  8: the batch augmentation stage (vpn_cutmix_*, vpn_mixup_*).  7: the GCN refinement stage (vpn_gcn_*).  6: vpn_emd_fwd_ex, vpn_emd_recovered_samples, vpn_emd_last_group.
  * 5 (round 4): vpn_vpdiv_fwd, vpn_camera_matrix, vpn_trainstep_finalize, vpn_trainstep_bwd (the reference's whole training
  * step in one autograd node).  4 (round 3): raster records are 16 float4 per primitive (vpn_raster_records_size grew), tile_order is a buffer of
  * 48-byte tile entries (vpn_raster_order_size, K <= 64).  3: vpn_raster_total_fwd_fin, vpn_hotpath_chamfer_fwd, the mesh
  * entry points. */
-#define VPN_ABI_VERSION 8
+#define VPN_ABI_VERSION 9
 
 /* primitive kinds (reference: train.py:106-116 cuboids first, then spheres, cones are stubs) */
 #define VPN_SPHERE 0
@@ -530,6 +530,36 @@ int vpn_cutmix_images(const float* img_a, const float* img_b, const int32_t* ind
 int vpn_mixup_gather(const float* points, const int32_t* indices, int B, int n, float* out, void* stream);
 int vpn_mixup_lerp(const float* points, const float* partner, const int32_t* assignment, int B, int n, float wa, float wb,
                    float* out, void* stream);
+
+/* ---- the evaluation stage (test.py:68-135, test_gcn.py:115-178): per-sample metrics of a batch and the per-class
+ * bookkeeping of an evaluation epoch on the device.  One launch per batch replaces the last reduction of
+ * ChamferDistanceLoss(each_batch=True) (chamfer_distance.py:25-30, called at test.py:101 / test_gcn.py:89), torch.sqrt(dist)
+ * .mean(1) (test_gcn.py:83), the two batch means with their .item() (test.py:104, test_gcn.py:145-146) and the class loop
+ * with its 2 B .item() calls (test.py:105-107, test_gcn.py:149-152).
+ * state: vpn_eval_state_size(C) bytes, 8-byte aligned, ZEROED BY THE CALLER before the first batch of an epoch (there is no
+ *   reset entry point), then owned by the launches.  Layout, for C = num_classes: 3 + 2 C doubles
+ *     [0] total_cd = sum over batches of mean_b cd_b     [1] total_emd likewise
+ *     [2] the arrival ticket of the launch in flight, an int in an 8-byte slot: 0 between launches (reads as 0.0)
+ *     [3, 3+C) class_sum_cd     [3+C, 3+2C) class_sum_emd
+ *   followed by 2 + C int64:  [0] n_batches   [1] n_invalid   [2, 2+C) class_n.
+ *   Two states are merged by adding them field by field (ranks that each evaluated a shard).
+ * vpn_eval_accumulate: dist1 [B,N] / dist2 [B,M] = the nearest-neighbour distances of vpn_chamfer_fwd*; emd_dist [B,N] =
+ *   the auction's dist (needs N == M), or NULL: Chamfer only, the test.py form (emd_b unused, the EMD fields keep their
+ *   value); class_index [B] int32 on the device.  Writes
+ *     cd_b[b]  = cd_scale * (w1 mean_i dist1[b,i] + w2 mean_j dist2[b,j]): the bits of vpn_chamfer_loss (one shared
+ *                summation order), times cd_scale in fp32 (test.py:101 multiplies by L_VIEW_CD);
+ *     emd_b[b] = mean_i sqrtf(emd_dist[b,i]), summed in fp64 in a fixed order and rounded to fp32 once;
+ *   and then, by the workgroup that arrives last, in sample order b = 0 .. B-1 and in fp64 (what Python's `+= x.item()`
+ *   does): class_sum_cd[c] += cd_b[b], class_sum_emd[c] += emd_b[b], class_n[c] += 1 for c = class_index[b]; total_cd +=
+ *   mean_b cd_b, total_emd += mean_b emd_b (the mean formed in fp64); n_batches += 1.  A class index outside [0, C) -- the
+ *   reference raises IndexError or wraps a negative one, which needs a host synchronisation -- is left out of the class
+ *   sums and counted in n_invalid; its sample still enters the batch means.  No floating-point atomics: bitwise
+ *   reproducible.  The ticket is reset by the launch itself, so a captured launch can be replayed.  Launches on one state
+ *   must be ordered (one stream). */
+size_t vpn_eval_state_size(int num_classes);
+int vpn_eval_accumulate(const float* dist1, const float* dist2, const float* emd_dist, const int32_t* class_index,
+                        int B, int N, int M, int num_classes, float w1, float w2, float cd_scale, void* state,
+                        float* cd_b, float* emd_b, void* stream);
 
 #ifdef __cplusplus
 }

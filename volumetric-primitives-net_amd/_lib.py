@@ -9,7 +9,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('VPN_HIP_LIB') or os.path.join(_HERE, 'libvpn_hip.so')     # VPN_HIP_LIB: the sanitizer build of the tests
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _c_f = ctypes.c_void_p      # device pointers travel as void*
 _i, _f, _u64, _sz = ctypes.c_int, ctypes.c_float, ctypes.c_uint64, ctypes.c_size_t
@@ -89,6 +89,8 @@ SIGNATURES = {
     'vpn_cutmix_images': (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _i, _i, _i, _c_f, _c_f, _c_f]),
     'vpn_mixup_gather': (_i, [_c_f, _c_f, _i, _i, _c_f, _c_f]),
     'vpn_mixup_lerp': (_i, [_c_f, _c_f, _c_f, _i, _i, _f, _f, _c_f, _c_f]),
+    'vpn_eval_state_size': (_sz, [_i]),
+    'vpn_eval_accumulate': (_i, [_c_f, _c_f, _c_f, _c_f, _i, _i, _i, _i, _f, _f, _f, _c_f, _c_f, _c_f, _c_f]),
 }
 
 _lib = None

@@ -18,6 +18,7 @@
 //   minimum the wave re-scans the earlier targets with the sqrt compare.
 #include "vpn_common.h"
 #include "vpn_chamfer_feat.h"
+#include "vpn_chamfer_loss.h"
 #include "vpn_raster_common.h"      // the tile-order rider of the training step (raster_order_wg)
 #include <stdlib.h>
 #include <string.h>
@@ -199,36 +200,15 @@ __global__ __launch_bounds__(CH_BLOCK) void chamfer_nn_kernel(const float* __res
     }
 }
 
-// loss_b = w1 * mean(dist1[b,:]) + w2 * mean(dist2[b,:])      (chamfer_distance.py:25-28)
-// sum of n floats by one workgroup of 256 lanes: float4 loads when the row is 16-byte aligned, 4 independent
-// accumulators so the loads pipeline; fixed summation order (deterministic)
-__device__ inline float row_sum_256(const float* __restrict__ p, int n) {
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    int done = 0;
-    if ((reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-        const float4* p4 = reinterpret_cast<const float4*>(p);
-        const int n4 = n >> 2;
-        for (int i = threadIdx.x; i < n4; i += 256) { const float4 v = p4[i]; a0 += v.x; a1 += v.y; a2 += v.z; a3 += v.w; }
-        done = n4 << 2;
-    }
-    for (int i = done + threadIdx.x; i < n; i += 256) a0 += p[i];
-    return (a0 + a1) + (a2 + a3);
-}
-
+// loss_b = w1 * mean(dist1[b,:]) + w2 * mean(dist2[b,:])      (chamfer_distance.py:25-28): the summation order lives in
+// vpn_chamfer_loss.h (chamfer_sample_loss_256), shared with the evaluation stage's accumulate kernel
 __global__ __launch_bounds__(256) void chamfer_loss_kernel(const float* __restrict__ d1, const float* __restrict__ d2,
                                                            int N, int M, float w1, float w2,
                                                            float* __restrict__ loss_b) {
     __shared__ float red[2][4];
     const int b = blockIdx.x;
-    float s1 = wave_sum(row_sum_256(d1 + (size_t)b * N, N));
-    float s2 = wave_sum(row_sum_256(d2 + (size_t)b * M, M));
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s1; red[1][threadIdx.x >> 6] = s2; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float a = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        float c = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-        loss_b[b] = w1 * (a / (float)N) + w2 * (c / (float)M);
-    }
+    const float loss = chamfer_sample_loss_256(d1 + (size_t)b * N, d2 + (size_t)b * M, N, M, w1, w2, red);
+    if (threadIdx.x == 0) loss_b[b] = loss;
 }
 
 // direct terms: every point's own nearest neighbour.  grad_p1[i] = g1 (a_i - b_j*)/d ;

@@ -98,3 +98,20 @@ class GradAllGather:
         self.pack(local_grad, local_loss)
         self.gather()
         return self.result()
+
+
+def all_reduce_eval_state(state, C, group=None):
+    """Sum of the evaluation states (modules/evaluation.py; 3 + 2 C float64 sums, then 2 + C int64 counts in one float64
+    tensor) of the ranks of `group`, on every rank, by ONE all-reduce: the counts travel as float64 beside the sums
+    (exact below 2^53) and come back as int64.  Returns a new tensor; `state` is left as it is."""
+    nd = 3 + 2 * C
+    if state.dtype != torch.float64 or state.numel() != nd + 2 + C:
+        raise ValueError('not an evaluation state of %d classes' % C)
+    if not dist.is_initialized():
+        raise RuntimeError('all_reduce_eval_state needs an initialised process group')
+    buf = torch.cat([state[:nd], state[nd:].view(torch.int64).to(torch.float64)])
+    dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+    out = torch.empty_like(state)
+    out[:nd].copy_(buf[:nd])
+    out[nd:].view(torch.int64).copy_(buf[nd:].round().to(torch.int64))
+    return out

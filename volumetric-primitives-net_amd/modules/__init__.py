@@ -10,3 +10,5 @@ from .meshing import Meshing, TriangleMesh, load_obj
 from .dataset import parse_split_csv, parse_rendering_metadata, split_rgba
 from . import augmentation
 from .augmentation import cut_mix_data, cut_mix_batch_points, adjust_point_num, mixup_points
+from . import evaluation
+from .evaluation import EvaluationMeter

@@ -452,6 +452,21 @@ def emd_last_group():
     return int(_lib.lib().vpn_emd_last_group())
 
 
+def _auction(xyz1, xyz2, eps, iters, group, stream):
+    """The auction launch (vpn_emd_fwd_ex) of contiguous fp32 clouds [B,n,3] on `stream` (a hipStream_t as ctypes gives it)
+    with at most `group` workgroups per sample (see _emd_group) -> (dist [B,n], assignment [B,n] int32, the workspace).
+    When `stream` is not the current stream the caller keeps all three alive until it has joined that stream: the
+    allocator hands a freed block to the next torch.empty on the current stream, while the auction may still be running."""
+    B, n, _ = xyz1.shape
+    dev = xyz1.device
+    dist = torch.empty((B, n), dtype=torch.float32, device=dev)
+    assignment = torch.empty((B, n), dtype=torch.int32, device=dev)
+    ws = _workspace('vpn_emd_workspace', B, n, dev=dev, floor=1)
+    _lib.call('vpn_emd_fwd_ex', xyz1, xyz2, B, n, float(eps), int(iters), dist, assignment, ws, group, stream,
+              EMD_TEST_GIVEUP_MASK)
+    return dist, assignment, ws
+
+
 class EmdFunction(Function):
     """emdFunction (modules/loss/emd/emd_module.py:29-70) on vpn_emd_fwd / vpn_emd_bwd: auction
     approximation of the Earth Mover's Distance.  Returns (dist [B,n] squared distance to the assigned
@@ -471,12 +486,7 @@ class EmdFunction(Function):
         assert n == xyz2.size(1)                       # emd_module.py:36-37
         assert B == xyz2.size(0)
         xyz1, xyz2 = _f32c(xyz1), _f32c(xyz2)
-        dev = xyz1.device
-        dist = torch.empty((B, n), dtype=torch.float32, device=dev)
-        assignment = torch.empty((B, n), dtype=torch.int32, device=dev)
-        ws = _workspace('vpn_emd_workspace', B, n, dev=dev, floor=1)
-        _lib.call('vpn_emd_fwd_ex', xyz1, xyz2, B, n, float(eps), int(iters), dist, assignment, ws, _emd_group(max_group),
-                  _lib.stream(), EMD_TEST_GIVEUP_MASK)
+        dist, assignment, _ = _auction(xyz1, xyz2, eps, iters, _emd_group(max_group), _lib.stream())
         ctx.save_for_backward(xyz1, xyz2, assignment)
         ctx.mark_non_differentiable(assignment)
         return dist, assignment
@@ -627,6 +637,14 @@ def _side_stream(dev):
     if key not in _SIDE:
         _SIDE[key] = torch.cuda.Stream(device=dev)
     return _SIDE[key]
+
+
+def _fork_side(dev):
+    """The side stream of `dev`, made to wait for everything enqueued on the current stream so far (the fork; the caller
+    joins with current_stream().wait_stream(side)).  Both are captured into HIP graphs as such."""
+    side = _side_stream(dev)
+    side.wait_stream(torch.cuda.current_stream())
+    return side
 
 
 def _grad_pattern(B, w_cd, dev):
@@ -867,7 +885,6 @@ class TrainStepLossFunction(Function):
         if not _lib.lib().vpn_hotpath_fused_features(B, K, n, M):
             raise ValueError('TrainStepLossFunction needs a shape the fused sampler / Chamfer path takes (K <= 64, large clouds)')
         f32 = dict(dtype=torch.float32, device=dev)
-        i32 = dict(dtype=torch.int32, device=dev)
         render = w_sil != 0.0 and gt_sil is not None
         cam = _view_camera(B, dev)
         gt_sil = _f32c(gt_sil).reshape(B, H, W) if render else None
@@ -884,17 +901,10 @@ class TrainStepLossFunction(Function):
         emd_dist = emd_assign = None
         side = None
         if w_emd:
-            emd_dist = torch.empty((B, N), **f32)
-            emd_assign = torch.empty((B, N), **i32)
-            ews = _workspace('vpn_emd_workspace', B, N, dev=dev, floor=1)
-            es = s
-            if EMD_SIDE_STREAM:
-                main = torch.cuda.current_stream()
-                side = _side_stream(dev)
-                side.wait_stream(main)
-                es = ctypes.c_void_p(side.cuda_stream)
-            _lib.call('vpn_emd_fwd_ex', points, gt_view, B, N, float(eps), int(iters), emd_dist, emd_assign, ews, _emd_group(None),
-                      es, EMD_TEST_GIVEUP_MASK)
+            side = _fork_side(dev) if EMD_SIDE_STREAM else None
+            # ews: the auction's workspace stays alive until the join in front of the finalisation
+            emd_dist, emd_assign, ews = _auction(points, gt_view, eps, iters, _emd_group(None),
+                                            ctypes.c_void_p(side.cuda_stream) if side is not None else s)
         d1, i1, d2, i2, order = _hotpath_scan(points, gt_view, cws, 7, render and _tile_rider_fits(K, Hr, Wr), rec, K, Hr, Wr, s)
         if render:
             _hotpath_raster_fin(params, kinds, cam, gt_sil, None, H, W, sigma, gamma, z_far, sil_mse, w_sil, 0.0, rec, lws, rws,
@@ -1213,13 +1223,64 @@ def mixup_points(points, indices, ratio, eps=0.005, iters=100, max_group=None):
     dev = points.device
     partner = torch.empty_like(points)
     _lib.call('vpn_mixup_gather', points, indices, B, n, partner, _lib.stream())
-    dist = torch.empty((B, n), dtype=torch.float32, device=dev)
-    assignment = torch.empty((B, n), dtype=torch.int32, device=dev)
-    ws = _workspace('vpn_emd_workspace', B, n, dev=dev, floor=1)
-    _lib.call('vpn_emd_fwd_ex', points, partner, B, n, float(eps), int(iters), dist, assignment, ws, _emd_group(max_group),
-              _lib.stream(), EMD_TEST_GIVEUP_MASK)
+    dist, assignment, _ = _auction(points, partner, eps, iters, _emd_group(max_group), _lib.stream())
     ratio = float(ratio)
     mixed = torch.empty_like(points)
     # (1 - r) and r as torch rounds the two Python doubles of point_mixup.py:36 to fp32
     _lib.call('vpn_mixup_lerp', points, partner, assignment, B, n, 1.0 - ratio, ratio, mixed, _lib.stream())
     return mixed, dist, assignment
+
+
+# ---- the evaluation stage (csrc/evaluate.hip; test.py:68-135, test_gcn.py:115-178).  Plain functions: nothing is
+# differentiable, the metrics are reported values.
+
+def eval_state(C, device):
+    """A zeroed state of the evaluation stage for C classes (include/vpn_hip.h, vpn_eval_accumulate): one float64 tensor of
+    5 + 3 C elements, the last 2 + C of which hold int64 bit patterns (eval_state_fields splits it)."""
+    nbytes = _lib.lib().vpn_eval_state_size(int(C))
+    if nbytes == 0:
+        raise ValueError('the evaluation state needs at least one class')
+    return torch.zeros((nbytes // 8,), dtype=torch.float64, device=device)
+
+
+def eval_state_fields(state, C):
+    """Views of a state tensor (any device): (sums float64 [3 + 2 C], counts int64 [2 + C])."""
+    if state.dtype != torch.float64 or state.numel() != 5 + 3 * C:
+        raise ValueError('not an evaluation state of %d classes' % C)
+    return state[:3 + 2 * C], state[3 + 2 * C:].view(torch.int64)
+
+
+def eval_step(predict_points, gt_points, class_index, state, C, *, emd=True, eps=0.005, iters=50, w1=None, w2=None,
+              cd_scale=1.0, max_group=None):
+    """One evaluation batch (test_gcn.py:142-152; emd=False: test.py:101-108): the Chamfer scan on the current stream, the
+    auction beside it on the side stream (EMD_SIDE_STREAM, the group rule of the training step), joined in front of ONE
+    vpn_eval_accumulate launch that writes the per-sample metrics and adds the batch to `state` (eval_state).
+    class_index: [B] int32 on the device.  No host synchronisation.  -> (cd_b [B], emd_b [B] or None)."""
+    from . import config
+    p, g = _f32c(predict_points.detach()), _f32c(gt_points.detach())
+    B, N, _ = p.shape
+    M = g.shape[1]
+    if emd and N != M:
+        raise ValueError('the EMD metric needs as many predicted as ground-truth points (emd_module.py:36): %d vs %d' % (N, M))
+    if g.shape[0] != B or class_index.numel() != B:
+        raise ValueError('predicted points, ground-truth points and class indices must agree on the batch size')
+    if not (class_index.is_cuda and class_index.dtype == torch.int32):
+        raise ValueError('class_index must be an int32 tensor on the device')
+    eval_state_fields(state, C)
+    dev = p.device
+    w1 = config.CD_W1 if w1 is None else w1
+    w2 = config.CD_W2 if w2 is None else w2
+    emd_dist = _assignment = _ews = side = None
+    if emd:
+        # launched first, so that its workgroups are placed while the CUs are empty (include/vpn_hip.h, vpn_emd_fwd)
+        side = _fork_side(dev) if EMD_SIDE_STREAM else None
+        emd_dist, _assignment, _ews = _auction(p, g, eps, iters, _emd_group(max_group),       # alive until the join below
+                               ctypes.c_void_p(side.cuda_stream) if side is not None else _lib.stream())
+    d1, _, d2, _ = chamfer_nn(p, g)
+    if side is not None:
+        torch.cuda.current_stream().wait_stream(side)
+    cd_b = torch.empty((B,), dtype=torch.float32, device=dev)
+    emd_b = torch.empty((B,), dtype=torch.float32, device=dev) if emd else None
+    _lib.call('vpn_eval_accumulate', d1, d2, emd_dist, class_index.contiguous(), B, N, M, int(C), float(w1), float(w2),
+              float(cd_scale), state, cd_b, emd_b, _lib.stream())
+    return cd_b, emd_b
