@@ -3,12 +3,15 @@
     python examples/eval_step.py [--batches 6] [--batch 8]          # test.py:68-135: Chamfer only
     python examples/eval_step.py --gcn                              # test_gcn.py:115-178: Chamfer + EMD on refined vertices
 
-The trained networks, the dataset and the visual dumps are out of scope; what the loops do with a batch is
+    python examples/eval_step.py --dump DIR [--three-elev] [--gcn]  # also write the visual dump of sample 0 every third batch
+
+The trained networks and the dataset are out of scope; what the loops do with a batch is
 the reference's, under torch.no_grad():
 
     test.py       head -> Sampling (16 x 128 points) -> ChamferDistanceLoss(each_batch=True) * L_VIEW_CD   test.py:93-102
     test_gcn.py   VPN -> sphere meshes -> GCNModel (2048 vertices) -> Chamfer + sqrt(EMD dist).mean(1)     test_gcn.py:136-143
     bookkeeping   batch means, per-class sums and counts, the table at the end                             EvaluationMeter
+    dumps         Visualizer.render_vp_meshes (test.py:110-124) / render_refine_vp_meshes (test_gcn.py:154-161)
 
 The class indices cycle over the reference's 13 ShapeNet classes; the last batch is short."""
 import argparse
@@ -49,6 +52,11 @@ def test(args, dev):
         params = vpn_amd.pack_head_outputs(*model(feats))
         predict_points = vpn_amd.Sampling.sample_primitives(params, kinds, SAMPLE_NUM, seed=100 + it)
         meter.update(predict_points, view_points, class_indices)
+        if args.dump and it % 3 == 0:                                    # test.py:110-124: the K meshes of sample 0
+            volumes, rotates, translates = vpn_amd.split_primitives(params)
+            vp_meshes = [vpn_amd.Meshing.sphere_meshing(volumes[k][:1], rotates[k][:1], translates[k][:1])[0] for k in range(VP_NUM)]
+            vpn_amd.Visualizer.render_vp_meshes(torch.rand(3, 128, 128, device=dev), vp_meshes,
+                                                os.path.join(args.dump, 'vp_%03d.gif' % it), is_three_elev=args.three_elev)
     return meter.report(args.epoch)
 
 
@@ -57,14 +65,18 @@ def test_gcn(args, dev):
     vpn = StandInVPN().to(dev).eval()
     gcn = GCNModel().to(dev).eval()
     meter = vpn_amd.EvaluationMeter(CLASS_NAMES, dev, emd=True)
-    for b, class_indices in batches(args.batches, args.batch):
+    for it, (b, class_indices) in enumerate(batches(args.batches, args.batch)):
         rgbs = torch.zeros(b, 3, 128, 128, device=dev)
         rgbs[:, :, 24:104, 16:112] = torch.rand(b, 3, 80, 96, device=dev)
         gt_points = (torch.rand(b, VP_NUM * 128, 3, device=dev) - 0.5) * 0.8
         volumes, rotates, translates, perceptual_features, global_features = vpn(rgbs)
-        predict_meshes = compose_vp_meshes(get_vp_meshes(volumes, rotates, translates))
+        vp_meshes = get_vp_meshes(volumes, rotates, translates)
+        predict_meshes = compose_vp_meshes(vp_meshes)
         predict_vertices = gcn(predict_meshes, rgbs, perceptual_features, global_features)
         meter.update(predict_vertices, gt_points, class_indices)
+        if args.dump and it % 3 == 0:                                    # test_gcn.py:154-161
+            vpn_amd.Visualizer.render_refine_vp_meshes(rgbs[0], vp_meshes[0], predict_vertices[0],
+                                                       os.path.join(args.dump, 'refine_%03d.gif' % it))
     return meter.report(args.epoch)
 
 
@@ -74,7 +86,11 @@ def main(argv=None):
     ap.add_argument('--batches', type=int, default=6)
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--epoch', type=int, default=0)
+    ap.add_argument('--dump', default='', metavar='DIR', help='write the visual dump of sample 0 every third batch into DIR')
+    ap.add_argument('--three-elev', action='store_true', help='three elevations per frame (is_three_elev of render_vp_meshes)')
     args = ap.parse_args(argv)
+    if args.dump:
+        os.makedirs(args.dump, exist_ok=True)
     torch.manual_seed(1234)
     dev = torch.device('cuda')
     return (test_gcn if args.gcn else test)(args, dev)

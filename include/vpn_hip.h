@@ -34,7 +34,9 @@
 extern "C" {
 #endif
 
-/* 9: the evaluation stage (vpn_eval_state_size, vpn_eval_accumulate).  8: the batch augmentation stage (vpn_cutmix_*, vpn_mixup_*).  7: the GCN refinement stage (vpn_gcn_*).  6: vpn_emd_fwd_ex, vpn_emd_recovered_samples, vpn_emd_last_group.
+/* Still 9 with the visualisation stage (vpn_vis_primitives, vpn_vis_mesh, vpn_vis_mesh_workspace): entries were added, none
+ * changed, and the binding resolves every symbol by name when it loads the library, so a library without them is refused
+ * there.  9: the evaluation stage (vpn_eval_state_size, vpn_eval_accumulate).  8: the batch augmentation stage (vpn_cutmix_*, vpn_mixup_*).  7: the GCN refinement stage (vpn_gcn_*).  6: vpn_emd_fwd_ex, vpn_emd_recovered_samples, vpn_emd_last_group.
  * 5 (round 4): vpn_vpdiv_fwd, vpn_camera_matrix, vpn_trainstep_finalize, vpn_trainstep_bwd (the reference's whole training
  * step in one autograd node).  4 (round 3): raster records are 16 float4 per primitive (vpn_raster_records_size grew), tile_order is a buffer of
  * 48-byte tile entries (vpn_raster_order_size, K <= 64).  3: vpn_raster_total_fwd_fin, vpn_hotpath_chamfer_fwd, the mesh
@@ -56,6 +58,8 @@ extern "C" {
 #define VPN_MAX_PRIMS 1024
 /* largest cloud vpn_cutmix_points takes: the 2 N candidate keys of a sample live in one workgroup's LDS */
 #define VPN_CUTMIX_MAX_POINTS 8192
+/* largest K vpn_vis_primitives takes: the records of one (sample, view) live in one workgroup's LDS (116 bytes each) */
+#define VPN_VIS_MAX_PRIMS 512
 
 int vpn_abi_version(void);
 /* static description of a code returned by any entry point below */
@@ -560,6 +564,37 @@ size_t vpn_eval_state_size(int num_classes);
 int vpn_eval_accumulate(const float* dist1, const float* dist2, const float* emd_dist, const int32_t* class_index,
                         int B, int N, int M, int num_classes, float w1, float w2, float cd_scale, void* state,
                         float* cd_b, float* emd_b, void* stream);
+
+/* ---- the visualisation stage (modules/visualize/render.py:13-24 as driven by vp_mesh.py:14-32,73-92 and mesh.py:7-50):
+ * colour renders of V views of S samples in ONE launch, written as uint8 RGB (HWC) into a caller-owned frame buffer.  The
+ * reference renders one view of one mesh per DIBRenderer call (13 to 37 per dump) and copies each to the host.
+ * DIBRenderer is kaolin's: pixel values are parity-unpinned; the specification is DESIGN.md 4.10, restated by
+ * tests/visualize_ref.py.  Forward only; plain launches on `stream`; no atomics; nothing is allocated.
+ * cams [S,V,3] = (dist, elev deg, azim deg): the look-at camera of vpn_raster_fwd.  ambient in [0,1]: colour = base *
+ *   (ambient + (1 - ambient) * cos(normal, ray)); 1 = flat colours, the reference's VertexColor look.  bg_*: background.
+ * frames / frames_bytes / pitch / view_offset: pixel (row, col) of view (s, v) goes to
+ *     frames + view_offset[s * V + v] + row * pitch + col * 3        (bytes; pitch >= 3 W)
+ *   view_offset: S * V int64 on the device, or NULL for the dense layout [S,V,H,pitch].  A view whose rectangle leaves
+ *   [0, frames_bytes) is skipped by the kernel (nothing of it is written); overlapping views are the caller's business.
+ *   Quantisation: clamp to [0,1], times 255, truncate (torchvision's ToPILImage after a clamp).
+ * vpn_vis_primitives (render.py:13-24 on primitives): params [S,K,10], kinds [K], palette [>= K,3] fp32.  Per pixel centre
+ *   the ray eye + s (fwd + px right + py up) meets primitive k, in its scaled frame (o~, d~ of vpn_raster_fwd), at
+ *     ellipsoid: hit iff 1 - m2 > 0, z = s* - sqrt((1 - m2) / (d~.d~))      cuboid: slab test on the unit box, hit iff
+ *     t_near <= t_far, z = t_near (components |d~_i| < 1e-9 replaced as in the raster);
+ *   a hit needs z > 1e-3; the nearest hit wins, equal depths go to the lowest k; no hit: background.  K <=
+ *   VPN_VIS_MAX_PRIMS (VPN_E_TOOBIG beyond).
+ * vpn_vis_mesh (render.py:13-24 on triangles): verts [S,P,3], faces [F,3] int32 shared by the samples, colors [S,P,3].
+ *   workspace: vpn_vis_mesh_workspace(S, V, P) bytes, 16-byte aligned (the projected vertices; first launch).  Second
+ *   launch: per pixel centre the faces that contain it (the inside rule of vpn_mesh_raster_fwd, faces with a corner at depth
+ *   <= 1e-3 skipped, no back-face culling), depth and colour interpolated perspective-correctly, the nearest face wins,
+ *   equal depths go to the lowest face; shading two-sided on the unit face normal. */
+int vpn_vis_primitives(const float* params, const int32_t* kinds, const float* cams, const float* palette, int S, int K, int V,
+                       int H, int W, float ambient, float bg_r, float bg_g, float bg_b, uint8_t* frames, size_t frames_bytes,
+                       long long pitch, const long long* view_offset, void* stream);
+size_t vpn_vis_mesh_workspace(int S, int V, int P);
+int vpn_vis_mesh(const float* verts, const int32_t* faces, const float* colors, const float* cams, int S, int P, int F, int V,
+                 int H, int W, float ambient, float bg_r, float bg_g, float bg_b, void* workspace, uint8_t* frames,
+                 size_t frames_bytes, long long pitch, const long long* view_offset, void* stream);
 
 #ifdef __cplusplus
 }

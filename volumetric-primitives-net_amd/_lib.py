@@ -91,6 +91,9 @@ SIGNATURES = {
     'vpn_mixup_lerp': (_i, [_c_f, _c_f, _c_f, _i, _i, _f, _f, _c_f, _c_f]),
     'vpn_eval_state_size': (_sz, [_i]),
     'vpn_eval_accumulate': (_i, [_c_f, _c_f, _c_f, _c_f, _i, _i, _i, _i, _f, _f, _f, _c_f, _c_f, _c_f, _c_f]),
+    'vpn_vis_primitives': (_i, [_c_f, _c_f, _c_f, _c_f, _i, _i, _i, _i, _i, _f, _f, _f, _f, _c_f, _sz, ctypes.c_longlong, _c_f, _c_f]),
+    'vpn_vis_mesh_workspace': (_sz, [_i, _i, _i]),
+    'vpn_vis_mesh': (_i, [_c_f, _c_f, _c_f, _c_f, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _c_f, _c_f, _sz, ctypes.c_longlong, _c_f, _c_f]),
 }
 
 _lib = None

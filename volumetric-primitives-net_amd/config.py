@@ -25,3 +25,6 @@ RASTER_SIGMA = 0.05
 RASTER_GAMMA = 0.1
 RASTER_Z_FAR = 2.0
 MESH_RASTER_SIGMA = 1e-4    # triangle-mesh silhouettes (oracle/vpn_oracle.py::mesh_raster): NDC^2, ~1 pixel of softness at 128^2
+
+# visual dumps (modules/visualize.py; specification: DESIGN.md 4.10)
+VIS_REFINE_AMBIENT = 0.35   # headlight shading of the refine dump: colour * (ambient + (1 - ambient) |n.d|); the reference's Phong atlas is absent

@@ -12,3 +12,5 @@ from . import augmentation
 from .augmentation import cut_mix_data, cut_mix_batch_points, adjust_point_num, mixup_points
 from . import evaluation
 from .evaluation import EvaluationMeter
+from . import visualize
+from .visualize import Visualizer

@@ -18,7 +18,7 @@ The one deliberate deviation: a class index outside [0, len(class_names)) makes 
 negative, silently count the sample for a class from the end).  Raising needs a synchronisation; here the sample is left out
 of every class sum, still enters the batch mean like in the reference, and `result()['n_invalid']` counts it.
 
-Out of scope: the visual dumps of the evaluation scripts (Visualizer.render_*, test.py:110-124)."""
+The visual dumps of the evaluation scripts (Visualizer.render_*, test.py:110-124) are modules/visualize.py."""
 import torch
 
 from .. import dist as vdist

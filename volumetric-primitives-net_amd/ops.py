@@ -1284,3 +1284,142 @@ def eval_step(predict_points, gt_points, class_index, state, C, *, emd=True, eps
     _lib.call('vpn_eval_accumulate', d1, d2, emd_dist, class_index.contiguous(), B, N, M, int(C), float(w1), float(w2),
               float(cd_scale), state, cd_b, emd_b, _lib.stream())
     return cd_b, emd_b
+
+
+# ---- the visualisation stage (csrc/visualize.hip; modules/visualize/render.py:13-24).  Plain functions: a picture has no
+# gradient.
+
+_CONSTS = {}
+
+
+def const_tensor(values, dtype, device):
+    """Device tensor of a host tuple of numbers, one per (values, dtype, device): view lists, frame offsets and default
+    palettes are the same call after call.  Uploaded once through pinned memory without blocking; a later call -- also one
+    inside a HIP-graph capture -- finds the tensor and touches neither the host nor the copy engine."""
+    device = torch.device(device)
+    if device.type == 'cuda' and device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    key = (values, dtype, str(device))
+    t = _CONSTS.get(key)
+    if t is None:
+        if len(_CONSTS) > 512:
+            _CONSTS.clear()
+        t = torch.tensor(values, dtype=dtype)
+        t = t.pin_memory().to(device, non_blocking=True) if device.type == 'cuda' else t
+        _CONSTS[key] = t
+    return t
+
+
+def _vis_target(S, V, H, W, dev, out, pitch, view_offset):
+    """(frame buffer, its size in bytes, pitch, offsets or None, what to return) of a render call, validated on the host."""
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0:
+        raise ValueError('image size must be positive, got %d x %d' % (H, W))
+    if out is None:
+        if pitch is not None or view_offset is not None:
+            raise ValueError('pitch and view_offset describe a frame buffer: pass it as out=')
+        out = torch.empty((S, V, H, W, 3), dtype=torch.uint8, device=dev)
+        return out, out.numel(), W * 3, None
+    if not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.is_contiguous()):
+        raise ValueError('out must be a contiguous uint8 tensor')
+    if out.device != dev:
+        raise ValueError('out lives on %s, the scene on %s' % (out.device, dev))
+    pitch = W * 3 if pitch is None else int(pitch)
+    if pitch < W * 3:
+        raise ValueError('pitch %d is shorter than a row of %d pixels' % (pitch, W))
+    nbytes = out.numel()
+    if view_offset is None:
+        if S * V * H * pitch > nbytes:
+            raise ValueError('out holds %d bytes, %d views of %d rows at pitch %d need %d' % (nbytes, S * V, H, pitch, S * V * H * pitch))
+        return out, nbytes, pitch, None
+    if isinstance(view_offset, torch.Tensor):
+        if not (view_offset.dtype == torch.int64 and view_offset.numel() == S * V and view_offset.device == dev):
+            raise ValueError('view_offset must hold S * V = %d int64 byte offsets on the device' % (S * V))
+        return out, nbytes, pitch, view_offset.contiguous()         # device data: the kernel skips a view that would leave `out`
+    offs = tuple(int(o) for o in view_offset)
+    if len(offs) != S * V:
+        raise ValueError('%d view offsets for S * V = %d views' % (len(offs), S * V))
+    for o in offs:
+        if o < 0 or o + (H - 1) * pitch + W * 3 > nbytes:
+            raise ValueError('view offset %d puts a %d x %d view outside the %d bytes of out' % (o, H, W, nbytes))
+    return out, nbytes, pitch, const_tensor(offs, torch.int64, dev)
+
+
+def _vis_common(cams, S, dev, ambient, background):
+    if not (isinstance(cams, torch.Tensor) and cams.dim() == 3 and cams.size(0) == S and cams.size(2) == 3 and cams.size(1) > 0):
+        raise ValueError('cams must be [S, V, 3] = (dist, elev, azim) with S = %d, got %s' % (S, tuple(getattr(cams, 'shape', ()))))
+    if cams.dtype != torch.float32 or cams.device != dev:
+        raise ValueError('cams must be a float32 tensor on %s' % dev)
+    ambient = float(ambient)
+    if not 0.0 <= ambient <= 1.0:
+        raise ValueError('ambient must lie in [0, 1], got %r' % ambient)
+    bg = tuple(float(c) for c in background)
+    if len(bg) != 3:
+        raise ValueError('background is an RGB triple')
+    return cams.contiguous(), ambient, bg
+
+
+def _vis_f32(name, t, shape_ok, want):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not shape_ok(t):
+        raise ValueError('%s must be a float32 tensor of shape %s, got %s %s' % (name, want, getattr(t, 'dtype', type(t).__name__),
+                                                                               tuple(getattr(t, 'shape', ()))))
+    return t.detach().contiguous()
+
+
+def _vis_on_device(dev, **tensors):
+    if dev.type != 'cuda':
+        raise ValueError('the scene lives on the %s: the renderer runs on the GPU only, there is no CPU path' % dev.type)
+    for name, t in tensors.items():
+        if t.device != dev:
+            raise ValueError('%s lives on %s, the scene on %s' % (name, t.device, dev))
+
+
+@torch.no_grad()
+def vis_primitives(params, kinds, cams, palette, H, W, *, ambient=1.0, background=(0.0, 0.0, 0.0), out=None, pitch=None,
+                   view_offset=None):
+    """Colour render of primitives (csrc/visualize.hip, vis_primitives_kernel): params [S,K,10], kinds (list or int32 device
+    tensor [K]), cams [S,V,3] = (dist, elev, azim), palette [>= K,3] -> uint8 [S,V,H,W,3]; all views of all samples in ONE
+    launch on the current stream, no host synchronisation.
+    out / pitch / view_offset: write into a frame buffer instead (uint8, contiguous): pixel (row, col) of view (s, v) goes to
+    byte view_offset[s * V + v] + row * pitch + col * 3 of it; offsets as a host sequence are checked here, as a device
+    int64 tensor by the kernel.  Returns `out` then.  Everything is validated (ValueError) before the launch."""
+    params = _vis_f32('params', params, lambda t: t.dim() == 3 and t.size(2) == PARAM_STRIDE and t.size(0) > 0 and t.size(1) > 0, '[S,K,10]')
+    S, K, _ = params.shape
+    dev = params.device
+    if K > 512:
+        raise ValueError('K = %d primitives: the renderer stages at most 512 (VPN_VIS_MAX_PRIMS)' % K)
+    if len(kinds) != K:
+        raise ValueError('%d kinds for K = %d primitives' % (len(kinds), K))
+    palette = _vis_f32('palette', palette, lambda t: t.dim() == 2 and t.size(1) == 3, '[>= K,3]')
+    if palette.shape[0] < K:
+        raise ValueError('the palette has %d colours for K = %d primitives' % (palette.shape[0], K))
+    _vis_on_device(dev, palette=palette)
+    kinds = kinds_tensor(kinds, dev)
+    cams, ambient, bg = _vis_common(cams, S, dev, ambient, background)
+    V = cams.size(1)
+    out, nbytes, pitch, offs = _vis_target(S, V, H, W, dev, out, pitch, view_offset)
+    _lib.call('vpn_vis_primitives', params, kinds, cams, palette, S, K, V, int(H), int(W), ambient, bg[0], bg[1], bg[2], out,
+              nbytes, pitch, offs, _lib.stream())
+    return out
+
+
+@torch.no_grad()
+def vis_mesh(verts, faces, colors, cams, H, W, *, ambient=1.0, background=(0.0, 0.0, 0.0), out=None, pitch=None, view_offset=None):
+    """Colour render of triangle meshes of one topology (vis_project_kernel + vis_mesh_kernel): verts [S,P,3], faces [F,3]
+    int32 on the device, colors [S,P,3], cams [S,V,3] -> uint8 [S,V,H,W,3]; two launches for all views of all samples, no
+    host synchronisation.  out / pitch / view_offset as in vis_primitives."""
+    verts = _vis_f32('verts', verts, lambda t: t.dim() == 3 and t.size(2) == 3 and t.size(0) > 0 and t.size(1) > 0, '[S,P,3]')
+    S, P, _ = verts.shape
+    dev = verts.device
+    colors = _vis_f32('colors', colors, lambda t: tuple(t.shape) == (S, P, 3), '[S,P,3] = %s' % ((S, P, 3),))
+    if not (isinstance(faces, torch.Tensor) and faces.dtype == torch.int32 and faces.dim() == 2 and faces.size(1) == 3
+            and faces.size(0) > 0):
+        raise ValueError('faces must be an int32 tensor [F,3] (ops.faces_i32 makes one)')
+    _vis_on_device(dev, colors=colors, faces=faces)
+    cams, ambient, bg = _vis_common(cams, S, dev, ambient, background)
+    V = cams.size(1)
+    out, nbytes, pitch, offs = _vis_target(S, V, H, W, dev, out, pitch, view_offset)
+    ws = _workspace('vpn_vis_mesh_workspace', S, V, P, dev=dev)
+    _lib.call('vpn_vis_mesh', verts, faces.contiguous(), colors, cams, S, P, faces.size(0), V, int(H), int(W), ambient, bg[0], bg[1],
+              bg[2], ws, out, nbytes, pitch, offs, _lib.stream())
+    return out
