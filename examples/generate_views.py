@@ -1,0 +1,86 @@
+"""The view loop of the reference's generate.py:150-173 for one mesh: 20 random cameras, ONE PhongRenderer.views call (one
+Phong launch and one silhouette launch for all of them), then per view the three files ACDMixDataset reads:
+
+    img_%.6d.png    RGBA: the Phong render, alpha = the soft silhouette SilhouetteLoss renders during training
+    mesh_%.6d.obj   the mesh in the view-centred frame (obj_to_view_points)
+    meta_%.6d.json  {"dist", "elev", "azim"}
+
+    python examples/generate_views.py OUT_DIR [--views 20] [--size 128] [--seed 0] [--obj A.obj B.obj ...]
+
+Without --obj the mesh is two Meshing spheres merged by merge_meshes (one colour per part): no dataset is needed.  The
+reference decomposes a mix of two ShapeNet models into convex hulls first (trimesh, V-HACD: not part of this project); every
+--obj file is taken as one part of the atlas instead."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from vpn_amd import Meshing, PhongRenderer, TriangleMesh, merge_meshes, obj_to_view_points  # noqa: E402
+
+
+def default_mesh(device='cuda'):
+    """Two ellipsoids made by Meshing.sphere_meshing, merged into one mesh with a two-texel atlas (colours: torch.rand)."""
+    v = torch.tensor([[0.30, 0.22, 0.26], [0.18, 0.30, 0.20]], device=device)
+    q = torch.tensor([[0.3, 0.5, 0.2, 0.4], [0.1, 0.9, 0.3, 1.1]], device=device)
+    t = torch.tensor([[0.0, 0.05, 0.25], [0.05, -0.05, -0.30]], device=device)
+    parts = [TriangleMesh(m.vertices.detach().clone(), m.faces) for m in Meshing.sphere_meshing(v, q, t)]
+    return merge_meshes(parts)
+
+
+def random_cameras(n):
+    """generate.py:153-155, drawn in its order: dist 3 .. 5, elev -45 .. 45, azim 0 .. 360."""
+    cams = []
+    for _ in range(n):
+        dist = 3.0 + torch.rand(1).item() * 2
+        elev = (torch.rand(1).item() - 0.5) * 90
+        azim = torch.rand(1).item() * 360
+        cams.append((dist, elev, azim))
+    return cams
+
+
+@torch.no_grad()
+def generate(mesh, uv, texture, out_dir, n_views=20, img_size=128, first=0):
+    from PIL import Image
+    os.makedirs(out_dir, exist_ok=True)
+    cams = random_cameras(n_views)
+    rgb, alpha = PhongRenderer.views(mesh, cams, uv, texture, img_size=img_size)        # [V,S,S,3], [V,S,S,1]
+    dev = mesh.vertices.device
+    cam_t = torch.tensor(cams, dtype=torch.float32).to(dev)
+    centred = obj_to_view_points(mesh.vertices.detach()[None].expand(n_views, -1, -1).contiguous(), cam_t[:, 0].contiguous(),
+                                 cam_t[:, 1].contiguous(), cam_t[:, 2].contiguous())
+    rgba = (torch.cat([rgb, alpha], -1).clamp(0.0, 1.0) * 255.0).to(torch.uint8).cpu().numpy()      # ToPILImage's quantisation
+    centred = centred.cpu()
+    faces = mesh.faces.cpu()
+    for j, (dist, elev, azim) in enumerate(cams):
+        n = first + j
+        Image.fromarray(rgba[j], 'RGBA').save(os.path.join(out_dir, 'img_%.6d.png' % n))
+        TriangleMesh(centred[j], faces).save_mesh(os.path.join(out_dir, 'mesh_%.6d.obj' % n))
+        with open(os.path.join(out_dir, 'meta_%.6d.json' % n), 'w') as f:
+            f.write(json.dumps({'dist': dist, 'elev': elev, 'azim': azim}))
+    return n_views
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('out_dir')
+    ap.add_argument('--views', type=int, default=20)
+    ap.add_argument('--size', type=int, default=128)
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--obj', nargs='*', default=[], help='OBJ files, one per part of the atlas')
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), 'the renderer runs on the GPU only'
+    torch.manual_seed(args.seed)
+    if args.obj:
+        mesh, uv, texture = merge_meshes([TriangleMesh.from_obj(p).cuda() for p in args.obj])
+    else:
+        mesh, uv, texture = default_mesh()
+    n = generate(mesh, uv, texture, args.out_dir, args.views, args.size)
+    print('wrote %d img / mesh / meta triples to %s' % (n, args.out_dir))
+
+
+if __name__ == '__main__':
+    main()

@@ -596,6 +596,27 @@ int vpn_vis_mesh(const float* verts, const int32_t* faces, const float* colors, 
                  int H, int W, float ambient, float bg_r, float bg_g, float bg_b, void* workspace, uint8_t* frames,
                  size_t frames_bytes, long long pitch, const long long* view_offset, void* stream);
 
+/* ---- the Phong renderer (modules/render/phong_renderer.py:12-38 as driven by generate.py:150-161 and
+ * point_mixup.py:58-70): textured, lit float renders of V views of S scenes of one topology.  The reference constructs a
+ * DIBRenderer(mode='Phong') per view and copies each image to the host; DIBRenderer is kaolin's: pixel values are
+ * parity-unpinned; the specification is DESIGN.md 4.11, restated by tests/phong_ref.py.  Forward only; plain
+ * launches on `stream`; no atomics; nothing is allocated.  Added without a change of VPN_ABI_VERSION (entries
+ * that are only added leave it).
+ * vpn_phong_mesh: verts [S,P,3], faces [F,3] int32 shared by the scenes, uv [S,P,2], texture [S,3,TH,TW], cams [S,V,3] =
+ *   (dist, elev deg, azim deg), light [3] in the camera basis (right, up, fwd), material [3,3] = rows ambient, diffuse,
+ *   specular (RGB), all fp32 on the device; shininess >= 0.  workspace: vpn_phong_mesh_workspace(S, V, P) bytes, 16-byte
+ *   aligned (the projected vertices; first launch).  Second launch: which face a pixel centre sees is the rule of
+ *   vpn_vis_mesh (nearest face, equal depths to the lowest face, either winding, corners at depth <= 1e-3 skip the face);
+ *   for that face (u, v) is interpolated perspective-correctly, tex = texture[s, :, clamp(floor(v TH)), clamp(floor(u TW))],
+ *   n = the unit face normal turned towards the eye, l = the unit light, d = the unit pixel ray,
+ *     cosT = clamp(n.l, 0, 1), r = 2 cosT n - l, cosA = clamp(-(r.d), 0, 1),
+ *     rgb = clamp(tex * (ambient + diffuse * cosT) + specular * powf(cosA, shininess), 0, 1);
+ *   a pixel that sees no face is (0, 0, 0).  rgb [S,V,H,W,3] fp32, every pixel written. */
+size_t vpn_phong_mesh_workspace(int S, int V, int P);
+int vpn_phong_mesh(const float* verts, const int32_t* faces, const float* uv, const float* texture, const float* cams,
+                   const float* light, const float* material, float shininess, int S, int P, int F, int V, int TH, int TW,
+                   int H, int W, void* workspace, float* rgb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

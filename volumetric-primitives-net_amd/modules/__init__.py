@@ -2,11 +2,11 @@
 same import names as train.py:11-15 (`from modules.sampling import Sampling`, ...)."""
 from .sampling import Sampling
 from .loss import ChamferDistanceLoss, EarthMoverDistanceLoss, SilhouetteLoss, VPDiverseLoss
-from .render import VertexRenderer
+from .render import VertexRenderer, PhongRenderer
 from .transform import (transform_points, rotate_points, translate_points, view_to_obj_points,
                         obj_to_view_points, rotate_points_forward_x_axis)
 from .network import pack_head_outputs, split_primitives, GCNModel, GCNConv
-from .meshing import Meshing, TriangleMesh, load_obj
+from .meshing import Meshing, TriangleMesh, load_obj, merge_meshes
 from .dataset import parse_split_csv, parse_rendering_metadata, split_rgba
 from . import augmentation
 from .augmentation import cut_mix_data, cut_mix_batch_points, adjust_point_num, mixup_points

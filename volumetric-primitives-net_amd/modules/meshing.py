@@ -69,6 +69,17 @@ class TriangleMesh:
     def cuda(self):
         return self.to('cuda')                                   # train_sphere.py:54
 
+    def save_mesh(self, path):
+        """kaolin's TriangleMesh.save_mesh as generate.py:168 uses it: a plain Wavefront OBJ (`v x y z`, `f a b c`, 1-based)
+        that load_obj reads back.  %.9g keeps every fp32 vertex exactly."""
+        verts = self.vertices.detach().cpu().tolist()
+        faces = (self.faces.detach().cpu().long() + 1).tolist()
+        with open(path, 'w') as fh:
+            for v in verts:
+                fh.write('v %.9g %.9g %.9g\n' % tuple(v))
+            for f in faces:
+                fh.write('f %d %d %d\n' % tuple(f))
+
     def sample(self, num_samples: int, seed=None):
         """kaolin's TriangleMesh.sample as train_sphere.py:76 uses it: `num_samples` points drawn uniformly from the
         surface (faces chosen in proportion to their area, uniform inside the face) -> (points [n,3], face_choices
@@ -105,6 +116,33 @@ def load_obj(path):
                 for j in range(1, len(idx) - 1):
                     fs.append([idx[0], idx[j], idx[j + 1]])
     return torch.tensor(vs, dtype=torch.float32), torch.tensor(fs, dtype=torch.int64).reshape(-1, 3)
+
+
+def merge_meshes(meshes, colors=None):
+    """The texture atlas of convex_decomposition.py:32-58: vertices concatenated, faces offset, every vertex of part i at
+    uv = i / n + 0.01, and a 1 x n texture whose texel i is the colour of part i -- torch.rand(3) per part, drawn in the
+    reference's order, or row i of `colors` [n,3] -> (mesh, uv [1,P,2], texture [1,3,1,n]) on the device of the parts.
+    With the nearest-texel lookup of the Phong renderer part i renders in colour i, unblended."""
+    n = len(meshes)
+    if n == 0:
+        raise ValueError('merge_meshes needs at least one mesh')
+    if colors is not None:
+        colors = torch.as_tensor(colors, dtype=torch.float32)
+        if tuple(colors.shape) != (n, 3):
+            raise ValueError('colors must be [%d,3], one row per mesh, got %s' % (n, tuple(colors.shape)))
+    vertex_num = 0
+    vertices, faces, texture, uv = [], [], [], []
+    for i, mesh in enumerate(meshes):
+        vertices.append(mesh.vertices)
+        faces.append(mesh.faces + vertex_num)
+        uv.append(torch.full((mesh.vertices.size(0), 2), i / n + 0.01))
+        c = torch.rand(3) if colors is None else colors[i].cpu()
+        texture.append(c.reshape(3, 1, 1))
+        vertex_num += mesh.vertices.size(0)
+    vertices = torch.cat(vertices)
+    dev = vertices.device
+    merged = TriangleMesh.from_tensors(vertices, torch.cat(faces))
+    return merged, torch.cat(uv)[None].to(dev), torch.cat(texture, 2)[None].to(dev)
 
 
 def normalize_sphere_template(vertices):

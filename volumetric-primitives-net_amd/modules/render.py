@@ -1,7 +1,7 @@
-"""modules/render of the reference (vertex_renderer.py) on the HIP primitive raster."""
+"""modules/render of the reference (vertex_renderer.py, phong_renderer.py) on the HIP rasters."""
 import torch
 
-from .. import config
+from .. import config, ops
 from ..ops import MeshRasterFunction, RasterFunction, faces_i32
 from ..primitives import PrimitivePack, mesh_batches
 
@@ -88,3 +88,78 @@ class VertexRenderer:
                 normals[i] = nrm[j]
         face_norms = torch.stack(normals) if len(batches) == 1 else normals
         return render_rgbs, render_alphas, face_norms
+
+
+class PhongRenderer:
+    """phong_renderer.py:12-66 on csrc/phong.hip: a textured, lit render of a triangle mesh.  Same entry
+    point, constants and helpers as the reference.  Differences, all forced by the reference rendering through kaolin
+    (absent): pixel values follow the specification of DESIGN.md 4.11 (parity unpinned); alpha is the soft silhouette of
+    VertexRenderer.triangle_alpha -- the operator SilhouetteLoss renders during training -- not DIB-R's; the texture
+    lookup is nearest texel; `views` renders all cameras of a mesh in one launch and nothing is copied to the host."""
+    material = ((0.7, 0.7, 0.7), (0.9, 0.9, 0.9), (0.3, 0.3, 0.3))          # phong_renderer.py:7  rows ambient, diffuse, specular
+    light = (0.0, 10.0, -10.0)                                               # phong_renderer.py:8  in the camera basis (right, up, fwd)
+    shininess = 1.0                                                          # phong_renderer.py:9
+
+    def __init__(self):
+        pass
+
+    @classmethod
+    def render(cls, mesh, dist, elev, azim, uv=None, texture=None, img_size=128):
+        """-> rgb (1,S,S,3), alpha (1,S,S,1), unit world-space face normals (1,F,3)."""
+        cls.check_mesh_parameters(mesh, uv, texture)
+        dist, elev, azim = cls.check_camera_parameters(dist, elev, azim)
+        if uv is None and texture is None:
+            uv, texture = cls.get_random_color(mesh.vertices.size(0))
+        rgb, alpha = cls.views(mesh, ((dist, elev, azim),), uv, texture, img_size)
+        tri = mesh.vertices.detach()[mesh.faces.long(), :]
+        nrm = torch.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0], dim=-1)
+        face_norms = (nrm / nrm.norm(dim=-1, keepdim=True).clamp_min(1e-20))[None]
+        return rgb, alpha, face_norms
+
+    @classmethod
+    def views(cls, mesh, cams, uv, texture, img_size=128):
+        """All cameras of one mesh in one launch (the loop of generate.py:150-161): cams [V,3] = (dist, elev deg, azim deg),
+        a float32 device tensor or a host sequence (uploaded once and cached) -> rgb [V,S,S,3], alpha [V,S,S,1]."""
+        cls.check_mesh_parameters(mesh, uv, texture)
+        verts = mesh.vertices.detach().float().contiguous()
+        dev = verts.device
+        if not isinstance(cams, torch.Tensor) or not cams.is_cuda and dev.type == 'cuda':
+            host = torch.as_tensor(cams, dtype=torch.float32)
+            cams = ops.const_tensor(tuple(host.reshape(-1).tolist()), torch.float32, dev).reshape(host.shape)
+        if cams.dim() != 2 or cams.size(1) != 3:
+            raise ValueError('cams must be [V,3] = (dist, elev, azim), got %s' % (tuple(cams.shape),))
+        cams = cams.contiguous()
+        V, S = cams.size(0), int(img_size)
+        rgb = ops.phong_mesh(verts[None], faces_i32(mesh.faces, dev), uv.to(dev), texture.to(dev), cams[None], S, S,
+                             light=cls.light, material=cls.material, shininess=cls.shininess)[0]
+        alpha, _ = VertexRenderer.triangle_alpha([mesh] * V, cams[:, 0], cams[:, 1], cams[:, 2], S, S)
+        return rgb, alpha[..., None]
+
+    @staticmethod
+    def check_camera_parameters(dist, elev, azim):
+        if isinstance(dist, torch.Tensor):                       # phong_renderer.py:41-48: a device scalar is read back
+            dist = dist.item()
+        if isinstance(elev, torch.Tensor):
+            elev = elev.item()
+        if isinstance(azim, torch.Tensor):
+            azim = azim.item()
+        return dist, elev, azim
+
+    @staticmethod
+    def check_mesh_parameters(mesh, uv, texture):
+        assert hasattr(mesh, 'vertices') and hasattr(mesh, 'faces')          # phong_renderer.py:52 (kaolin's class is absent)
+        if uv is None and texture is None:
+            return
+
+        assert uv.ndimension() == 3  # (B, N, 2)
+        assert texture.ndimension() == 4  # (B, 3, TH, TW)
+        assert uv.size(1) == mesh.vertices.size(0) and uv.size(2) == 2
+        assert texture.size(1) == 3
+
+    @staticmethod
+    def get_random_color(vertex_num):
+        """phong_renderer.py:62-66, drawn on the host in the reference's order (`views` moves the pair to the mesh)."""
+        uv = torch.rand((1, vertex_num, 2))
+        texture = torch.rand((1, 3, 1, 1)) * 255
+
+        return uv, texture

@@ -1423,3 +1423,61 @@ def vis_mesh(verts, faces, colors, cams, H, W, *, ambient=1.0, background=(0.0, 
     _lib.call('vpn_vis_mesh', verts, faces.contiguous(), colors, cams, S, P, faces.size(0), V, int(H), int(W), ambient, bg[0], bg[1],
               bg[2], ws, out, nbytes, pitch, offs, _lib.stream())
     return out
+
+
+def _phong_const(name, value, shape, dev):
+    """light / material of a render call on the device: a host sequence is uploaded once (const_tensor), a tensor is checked."""
+    if isinstance(value, torch.Tensor):
+        if value.dtype != torch.float32 or tuple(value.shape) != shape:
+            raise ValueError('%s must be a float32 tensor of shape %s, got %s %s' % (name, shape, value.dtype, tuple(value.shape)))
+        if value.device != dev:
+            raise ValueError('%s lives on %s, the scene on %s' % (name, value.device, dev))
+        return value.detach().contiguous()
+    flat = tuple(float(x) for x in torch.as_tensor(value, dtype=torch.float64).reshape(-1).tolist())
+    n = 1
+    for d in shape:
+        n *= d
+    if len(flat) != n:
+        raise ValueError('%s must hold %d numbers (shape %s), got %d' % (name, n, shape, len(flat)))
+    return const_tensor(flat, torch.float32, dev).reshape(shape)
+
+
+@torch.no_grad()
+def phong_mesh(verts, faces, uv, texture, cams, H, W, *, light, material, shininess, out=None):
+    """Textured, lit render of triangle meshes of one topology (csrc/phong.hip, phong_project_kernel + phong_mesh_kernel;
+    DESIGN.md 4.11): verts [S,P,3], faces [F,3] int32 on the device, uv [S,P,2], texture [S,3,TH,TW], cams [S,V,3] = (dist,
+    elev, azim) -> float32 rgb [S,V,H,W,3] in [0,1], background (0,0,0); two launches for all views of all scenes on the
+    current stream, no host synchronisation.
+    light: 3 numbers, a direction in the camera basis (right, up, fwd); material: 3 x 3 numbers, rows ambient, diffuse,
+    specular; host sequences (uploaded once and cached) or float32 device tensors.  shininess: the specular exponent, a
+    number >= 0.  out: a contiguous float32 [S,V,H,W,3] tensor to write into.  Everything is validated (ValueError) before the
+    launch."""
+    verts = _vis_f32('verts', verts, lambda t: t.dim() == 3 and t.size(2) == 3 and t.size(0) > 0 and t.size(1) > 0, '[S,P,3]')
+    S, P, _ = verts.shape
+    dev = verts.device
+    uv = _vis_f32('uv', uv, lambda t: tuple(t.shape) == (S, P, 2), '[S,P,2] = %s' % ((S, P, 2),))
+    texture = _vis_f32('texture', texture, lambda t: t.dim() == 4 and t.size(0) == S and t.size(1) == 3 and t.size(2) > 0 and t.size(3) > 0,
+                       '[S,3,TH,TW] with S = %d' % S)
+    if not (isinstance(faces, torch.Tensor) and faces.dtype == torch.int32 and faces.dim() == 2 and faces.size(1) == 3
+            and faces.size(0) > 0):
+        raise ValueError('faces must be an int32 tensor [F,3] (ops.faces_i32 makes one)')
+    cams, _, _ = _vis_common(cams, S, dev, 1.0, (0.0, 0.0, 0.0))
+    _vis_on_device(dev, uv=uv, texture=texture, faces=faces)
+    V = cams.size(1)
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0:
+        raise ValueError('image size must be positive, got %d x %d' % (H, W))
+    shininess = float(shininess)
+    if not shininess >= 0.0:
+        raise ValueError('shininess must be >= 0, got %r' % shininess)
+    light = _phong_const('light', light, (3,), dev)
+    material = _phong_const('material', material, (3, 3), dev)
+    if out is None:
+        out = torch.empty((S, V, H, W, 3), dtype=torch.float32, device=dev)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (S, V, H, W, 3)
+              and out.device == dev):
+        raise ValueError('out must be a contiguous float32 tensor of shape %s on %s' % ((S, V, H, W, 3), dev))
+    ws = _workspace('vpn_phong_mesh_workspace', S, V, P, dev=dev)
+    _lib.call('vpn_phong_mesh', verts, faces.contiguous(), uv, texture, cams, light, material, shininess, S, P, faces.size(0), V,
+              texture.size(2), texture.size(3), H, W, ws, out, _lib.stream())
+    return out
