@@ -9,7 +9,13 @@ Phong launch and one silhouette launch for all of them), then per view the three
 
 Without --obj the mesh is two Meshing spheres merged by merge_meshes (one colour per part): no dataset is needed.  The
 reference decomposes a mix of two ShapeNet models into convex hulls first (trimesh, V-HACD: not part of this project); every
---obj file is taken as one part of the atlas instead."""
+--obj file is taken as one part of the atlas instead.
+
+    python examples/generate_views.py OUT_DIR --dataset point_mixup [--batch 8] [--batches 1] [--size 128]
+
+writes the files of generate.py:42-66 instead: per mixed sample `rgb_%d.png`, `silhouette_%d.png` and `mesh_%d.obj`, numbered
+from 1, made by generate_point_mixup_data.  Without a dataset the clouds are surface samples of random
+ellipsoid pairs."""
 import argparse
 import json
 import os
@@ -64,9 +70,37 @@ def generate(mesh, uv, texture, out_dir, n_views=20, img_size=128, first=0):
     return n_views
 
 
+def default_clouds(B, n=2048, device='cuda'):
+    """Stand-ins for data['view_center_points']: n surface points of two random ellipsoids per sample."""
+    from vpn_amd import SPHERE, Sampling
+    v = (torch.rand(B, 2, 3) + 0.3) / 5.0
+    params = torch.cat([v, torch.rand(B, 2, 4), 0.25 * (torch.rand(B, 2, 3) * 2 - 1)], 2).to(device)
+    return Sampling.sample_primitives(params, [SPHERE, SPHERE], n // 2, seed=int(torch.randint(0, 2 ** 31, (1,)).item()))
+
+
+@torch.no_grad()
+def generate_point_mixup(clouds, out_dir, img_size=128, first=1):
+    """generate.py:54-66 for one batch of view-centred clouds [B,N,3]: -> the number of triples written."""
+    from PIL import Image
+    from vpn_amd import generate_point_mixup_data
+    os.makedirs(out_dir, exist_ok=True)
+    rgbs, silhouettes, meshes = generate_point_mixup_data(clouds, img_size=img_size)
+    rgb8 = (rgbs.clamp(0.0, 1.0) * 255.0).to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()         # ToPILImage's quantisation
+    sil8 = (silhouettes.clamp(0.0, 1.0) * 255.0).to(torch.uint8)[:, 0].cpu().numpy()
+    for i, mesh in enumerate(meshes):
+        n = first + i
+        Image.fromarray(rgb8[i], 'RGB').save(os.path.join(out_dir, 'rgb_%d.png' % n))
+        Image.fromarray(sil8[i], 'L').save(os.path.join(out_dir, 'silhouette_%d.png' % n))
+        TriangleMesh(mesh.vertices.cpu(), mesh.faces.cpu()).save_mesh(os.path.join(out_dir, 'mesh_%d.obj' % n))
+    return len(meshes)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('out_dir')
+    ap.add_argument('-d', '--dataset', default='views', choices=['views', 'point_mixup'], help='what to write (generate.py -d)')
+    ap.add_argument('--batch', type=int, default=8, help='point_mixup: samples per batch (config.py:9)')
+    ap.add_argument('--batches', type=int, default=1, help='point_mixup: batches to write')
     ap.add_argument('--views', type=int, default=20)
     ap.add_argument('--size', type=int, default=128)
     ap.add_argument('--seed', type=int, default=0)
@@ -74,6 +108,12 @@ def main():
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'the renderer runs on the GPU only'
     torch.manual_seed(args.seed)
+    if args.dataset == 'point_mixup':
+        n = 0
+        for _ in range(args.batches):
+            n += generate_point_mixup(default_clouds(args.batch), args.out_dir, args.size, first=n + 1)
+        print('wrote %d rgb / silhouette / mesh triples to %s' % (n, args.out_dir))
+        return
     if args.obj:
         mesh, uv, texture = merge_meshes([TriangleMesh.from_obj(p).cuda() for p in args.obj])
     else:

@@ -89,8 +89,9 @@ def make_batch(B, K, sample_num, size, dev, seed=0):
 
 def augment_batch(batch, which, it):
     """train.py:232-237 on the HIP augmentation stage, in the reference's order.  The stand-in network reads features, not
-    pixels, so the mixed rgbs (here: the silhouette repeated over three channels) have no consumer; the mix-up moves the
-    points only -- re-meshing and re-rendering them (the rest of point_mixup_data) is host-side mesh processing."""
+    pixels, so the mixed rgbs (here: the silhouette repeated over three channels) have no consumer.  `mixup` moves the
+    points only; `pointmixup` is the whole point_mixup_data: mixed clouds, a mesh of convex parts from each, its render as
+    the new silhouette and its surface samples as the new points."""
     feats, gt_points, gt_sil, dists, elevs, azims, angles, kinds = batch
     if 'rotate' in which:
         gt_points = vpn_amd.rotate_points_forward_x_axis(gt_points, angles)
@@ -98,6 +99,10 @@ def augment_batch(batch, which, it):
         _, gt_sil, gt_points = vpn_amd.cut_mix_data(gt_sil.expand(-1, 3, -1, -1), gt_sil, gt_points, seed=2000 + it)
     if 'mixup' in which:
         gt_points = vpn_amd.mixup_points(gt_points)
+    if 'pointmixup' in which:
+        _, sil, gt_points = vpn_amd.point_mixup_data(gt_points, img_size=gt_sil.shape[-1], num_points=gt_points.shape[1],
+                                                     seed=3000 + it)
+        gt_sil = (sil > 0.5).float()
     return feats, gt_points, gt_sil, dists, elevs, azims, angles, kinds
 
 
@@ -109,10 +114,10 @@ def main():
     ap.add_argument('--sample-num', type=int, default=128)   # config.py:8
     ap.add_argument('--size', type=int, default=128)         # config.py:49
     ap.add_argument('--fused', action='store_true', help='the whole loss as one autograd node (TrainStepLossFunction)')
-    ap.add_argument('--augment', default='', help='comma-separated subset of rotate,cutmix,mixup (config.py AUGMENT_3D; default: none)')
+    ap.add_argument('--augment', default='', help='comma-separated subset of rotate,cutmix,mixup,pointmixup (config.py AUGMENT_3D; default: none)')
     args = ap.parse_args()
     augment = [a for a in args.augment.split(',') if a]
-    assert set(augment) <= {'rotate', 'cutmix', 'mixup'}, augment
+    assert set(augment) <= {'rotate', 'cutmix', 'mixup', 'pointmixup'}, augment
     losses = training_losses_fused if args.fused else training_losses
     dev = torch.device('cuda')
     torch.manual_seed(1234)

@@ -58,6 +58,10 @@ extern "C" {
 #define VPN_MAX_PRIMS 1024
 /* largest cloud vpn_cutmix_points takes: the 2 N candidate keys of a sample live in one workgroup's LDS */
 #define VPN_CUTMIX_MAX_POINTS 8192
+/* largest cloud and most clusters vpn_cluster_points / vpn_support_hulls take: a sample's cloud (16 bytes a point) lives in
+ * one workgroup's LDS */
+#define VPN_CLUSTER_MAX_POINTS 8192
+#define VPN_CLUSTER_MAX_HULLS 32
 /* largest K vpn_vis_primitives takes: the records of one (sample, view) live in one workgroup's LDS (116 bytes each) */
 #define VPN_VIS_MAX_PRIMS 512
 
@@ -616,6 +620,33 @@ size_t vpn_phong_mesh_workspace(int S, int V, int P);
 int vpn_phong_mesh(const float* verts, const int32_t* faces, const float* uv, const float* texture, const float* cams,
                    const float* light, const float* material, float shininess, int S, int P, int F, int V, int TH, int TW,
                    int H, int W, void* workspace, float* rgb, void* stream);
+
+/* ---- cloud -> mesh of one topology (the step of point_mixup.py:43-55 between mixup_points and the Phong
+ * render).  The reference reconstructs a surface by ball pivoting (open3d, ball_pivot.py) and decomposes it with V-HACD
+ * (trimesh + an external binary, convex_decomposition.py:7-16) per sample on the host; this REPLACES both: the cloud is
+ * split into H clusters and every cluster becomes the polytope of its support points along D fixed directions, so all
+ * samples share one face list.  Parity with the reference is unpinned; the specification is restated by
+ * tests/reconstruct_ref.py and the outputs equal it bit for bit.  Forward only; plain launches on `stream`; nothing is
+ * allocated.  Inputs must be finite (not checked on the device).  All fp32 arithmetic is rounded per operation, sums run
+ * x, y, z from the left: dist2(p, c) = ((px-cx)^2 + (py-cy)^2) + (pz-cz)^2, dot(p, d) = (px dx + py dy) + pz dz.
+ * n <= VPN_CLUSTER_MAX_POINTS, H <= VPN_CLUSTER_MAX_HULLS, B <= 65535: VPN_E_TOOBIG beyond, before any HIP call.  Added
+ * without a change of VPN_ABI_VERSION.
+ * Integer mean of a set: per coordinate sum llrint(x * 2^20) as int64 (exact in any order), (double)sum / ((double)count *
+ *   2^20), rounded once to fp32.
+ * vpn_cluster_points: points [B,n,3] -> labels [B,n] int32, centres [B,H,3], counts [B,H] int32; one workgroup per sample.
+ *   Seeds: c_0 = the point with the largest dist2 to the integer mean of the cloud, c_k = the point with the largest
+ *   min_j<k dist2(p, c_j); equal values go to the lowest point index.  Then `iters` >= 0 Lloyd rounds: every point takes the
+ *   centre of smallest dist2 (equal values: the lowest centre), every non-empty cluster's centre becomes the integer mean
+ *   of its members, an empty cluster keeps its centre.  labels and counts are one last assignment against the final
+ *   centres.
+ * vpn_support_hulls: labels / centres as above (a label outside [0,H) belongs to no cluster), dirs [D,3] ->
+ *   verts [B,H*D,3], support [B,H*D] int32: vertex (h,d) is the member p of cluster h with the largest dot(p, dirs[d]),
+ *   equal values to the lowest point index, support its index; an empty cluster writes its centre D times with support
+ *   -1 (zero-area faces, which the raster and the sampler ignore).  One workgroup per (cluster, sample). */
+int vpn_cluster_points(const float* points, int B, int n, int H, int iters, int32_t* labels, float* centres,
+                       int32_t* counts, void* stream);
+int vpn_support_hulls(const float* points, const int32_t* labels, const float* centres, const float* dirs, int B, int n,
+                      int H, int D, float* verts, int32_t* support, void* stream);
 
 #ifdef __cplusplus
 }

@@ -96,6 +96,8 @@ SIGNATURES = {
     'vpn_vis_mesh': (_i, [_c_f, _c_f, _c_f, _c_f, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _c_f, _c_f, _sz, ctypes.c_longlong, _c_f, _c_f]),
     'vpn_phong_mesh_workspace': (_sz, [_i, _i, _i]),
     'vpn_phong_mesh': (_i, [_c_f] * 7 + [_f] + [_i] * 8 + [_c_f, _c_f, _c_f]),
+    'vpn_cluster_points': (_i, [_c_f, _i, _i, _i, _i, _c_f, _c_f, _c_f, _c_f]),
+    'vpn_support_hulls': (_i, [_c_f, _c_f, _c_f, _c_f, _i, _i, _i, _i, _c_f, _c_f, _c_f]),
 }
 
 _lib = None

@@ -19,6 +19,7 @@ SPHERE_NUM = 16             # config.py:34
 CONE_NUM = 0                # config.py:35
 VP_NUM = CUBOID_NUM + SPHERE_NUM + CONE_NUM
 IMG_SIZE = 128              # config.py:49
+DECOMPOSE_CONVEX_NUM = 16   # config.py:53: hulls per reconstructed mesh (modules/augmentation.py)
 
 # soft raster (new operator; specification: oracle/vpn_oracle.py::raster)
 RASTER_SIGMA = 0.05

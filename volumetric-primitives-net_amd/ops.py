@@ -1231,6 +1231,118 @@ def mixup_points(points, indices, ratio, eps=0.005, iters=100, max_group=None):
     return mixed, dist, assignment
 
 
+# ---- cloud -> mesh of one topology (csrc/reconstruct.hip): what point_mixup.py:43-55 does through open3d
+# ball pivoting and V-HACD on the host, replaced by a clustering and support polytopes on the device.  Data, like the rest
+# of the augmentation stage.
+
+def cluster_points(points, hull_num, iters=8):
+    """vpn_cluster_points: points [B,n,3] -> (labels [B,n] int32, centres [B,H,3], counts [B,H] int32): farthest-point
+    seeds and `iters` Lloyd rounds with exact integer means, one workgroup per sample (include/vpn_hip.h)."""
+    _augment_is_data(points)
+    points = _f32c(points.detach())
+    if points.dim() != 3 or points.size(2) != 3:
+        raise ValueError('points must be [B,n,3], got %s' % (tuple(points.shape),))
+    B, n, _ = points.shape
+    H = int(hull_num)
+    dev = points.device
+    labels = torch.empty((B, n), dtype=torch.int32, device=dev)
+    centres = torch.empty((B, H, 3), dtype=torch.float32, device=dev)
+    counts = torch.empty((B, H), dtype=torch.int32, device=dev)
+    _lib.call('vpn_cluster_points', points, B, n, H, int(iters), labels, centres, counts, _lib.stream())
+    return labels, centres, counts
+
+
+def support_hulls(points, labels, centres, dirs):
+    """vpn_support_hulls: points [B,n,3], labels [B,n] int32, centres [B,H,3], dirs [D,3] -> (verts [B,H*D,3], support
+    [B,H*D] int32): vertex (h,d) is the member of cluster h farthest along dirs[d] (include/vpn_hip.h)."""
+    _augment_is_data(points, centres, dirs)
+    if (points.dim() != 3 or points.size(2) != 3 or centres.dim() != 3 or centres.size(2) != 3 or centres.size(0) != points.size(0)
+            or dirs.dim() != 2 or dirs.size(1) != 3 or labels.dtype != torch.int32 or tuple(labels.shape) != tuple(points.shape[:2])):
+        raise ValueError('support_hulls: points [B,n,3], labels [B,n] int32, centres [B,H,3], dirs [D,3] expected, got %s %s %s %s %s'
+                         % (tuple(points.shape), labels.dtype, tuple(labels.shape), tuple(centres.shape), tuple(dirs.shape)))
+    points, centres, dirs = _f32c(points.detach()), _f32c(centres.detach()), _f32c(dirs.detach())
+    B, n, _ = points.shape
+    H, D = centres.size(1), dirs.size(0)
+    dev = points.device
+    verts = torch.empty((B, H * D, 3), dtype=torch.float32, device=dev)
+    support = torch.empty((B, H * D), dtype=torch.int32, device=dev)
+    _lib.call('vpn_support_hulls', points, labels.contiguous(), centres, dirs, B, n, H, D, verts, support, _lib.stream())
+    return verts, support
+
+
+_HULL_TEMPLATES = {}
+
+
+def hull_template(hull_num, device, template=None):
+    """(dirs [D,3] float32, faces [H*Ft,3] int32) of `hull_num` hulls on `device`: the template's vertices, normalised,
+    and its faces repeated with a per-hull vertex offset.  template: (vertices [D,3], faces [Ft,3]) host tensors, default
+    meshing.uv_sphere().  Uploaded once per (template, hull_num, device) through pinned memory without blocking
+    (const_tensor style): later calls, also inside a HIP-graph capture, touch neither the host nor the copy engine."""
+    device = torch.device(device)
+    if device.type == 'cuda' and device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    H = int(hull_num)
+    if template is None:
+        tkey = 'uv_sphere'
+    else:
+        tv, tf = (torch.as_tensor(t).detach().cpu().contiguous() for t in template)
+        tkey = (tuple(tv.shape), hash(tv.numpy().tobytes()), tuple(tf.shape), hash(tf.numpy().tobytes()))
+    key = (tkey, H, str(device))
+    hit = _HULL_TEMPLATES.get(key)
+    if hit is None:
+        if template is None:
+            from .modules.meshing import uv_sphere
+            tv, tf = uv_sphere()
+        tv = tv.to(torch.float32)
+        if tv.dim() != 2 or tv.size(1) != 3 or tf.dim() != 2 or tf.size(1) != 3:
+            raise ValueError('template must be (vertices [D,3], faces [Ft,3])')
+        D = tv.size(0)
+        if tf.numel() and (int(tf.min()) < 0 or int(tf.max()) >= D):
+            raise ValueError('template faces index outside its %d vertices' % D)
+        dirs = tv / tv.norm(dim=1, keepdim=True)
+        faces = torch.cat([tf.long() + h * D for h in range(H)]).to(torch.int32)
+        if len(_HULL_TEMPLATES) > 64:
+            _HULL_TEMPLATES.clear()
+        up = (lambda t: t.contiguous().pin_memory().to(device, non_blocking=True)) if device.type == 'cuda' else (lambda t: t.contiguous())
+        hit = (up(dirs), up(faces))
+        faces_remember(hit[1], ('hulls', tkey, H))        # the content key without a device read (mesh_batches, gcn_graph)
+        _HULL_TEMPLATES[key] = hit
+    return hit
+
+
+def hull_meshes(points, hull_num, iters=8, template=None):
+    """Cloud -> mesh of one topology for the whole batch, two launches, no host synchronisation: points [B,n,3] ->
+    (verts [B,H*D,3], faces [H*Ft,3] int32 shared by the samples, labels [B,n] int32, support [B,H*D] int32).  Hull h of
+    sample b is the template (default meshing.uv_sphere(): D = 128, Ft = 252) with vertex d moved to the member of cluster
+    h farthest along the template's direction d: an inner approximation of the cluster's convex hull with every vertex on
+    it.  Faces between coinciding vertices have zero area; the raster and the sampler ignore them."""
+    _augment_is_data(points)
+    dirs, faces = hull_template(hull_num, points.device, template)
+    labels, centres, _counts = cluster_points(points, hull_num, iters)
+    verts, support = support_hulls(points, labels, centres, dirs)
+    return verts, faces, labels, support
+
+
+def sample_meshes(verts, faces, n, seed, mesh_base=0):
+    """n area-weighted uniform surface points on each of B meshes of one topology as data (vpn_mesh_sample_fwd, one launch
+    pair, no autograd node): verts [B,P,3], faces [F,3] int32 -> (points [B,n,3], face index [B,n] int32, barycentric weights
+    [B,n,3]); points[b,i] = sum_k bary[b,i,k] * verts[b, faces[face[b,i], k]].  Draws: Philox(seed; mesh_base + b, point)."""
+    _augment_is_data(verts)
+    verts = _f32c(verts.detach())
+    B, P, _ = verts.shape
+    F = faces.shape[0]
+    assert faces.dtype == torch.int32 and faces.is_cuda and faces.is_contiguous()
+    dev = verts.device
+    n = int(n)
+    cdf = torch.empty((B, F), dtype=torch.float32, device=dev)
+    points = torch.empty((B, n, 3), dtype=torch.float32, device=dev)
+    fidx = torch.empty((B, n), dtype=torch.int32, device=dev)
+    bary = torch.empty((B, n, 3), dtype=torch.float32, device=dev)
+    _lib.call('vpn_mesh_sample_fwd', verts, faces, None, int(seed) & 0xFFFFFFFFFFFFFFFF, int(mesh_base), B, P, F, n, cdf, points,
+              fidx, bary, _lib.stream())
+    return points, fidx, bary
+
+
 # ---- the evaluation stage (csrc/evaluate.hip; test.py:68-135, test_gcn.py:115-178).  Plain functions: nothing is
 # differentiable, the metrics are reported values.
 
