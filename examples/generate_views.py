@@ -7,9 +7,15 @@ Phong launch and one silhouette launch for all of them), then per view the three
 
     python examples/generate_views.py OUT_DIR [--views 20] [--size 128] [--seed 0] [--obj A.obj B.obj ...]
 
-Without --obj the mesh is two Meshing spheres merged by merge_meshes (one colour per part): no dataset is needed.  The
-reference decomposes a mix of two ShapeNet models into convex hulls first (trimesh, V-HACD: not part of this project); every
---obj file is taken as one part of the atlas instead.
+Without --obj the mesh is two Meshing spheres merged by merge_meshes (one colour per part): no dataset is needed.  Every
+--obj file is taken as one part of the atlas.
+
+    python examples/generate_views.py OUT_DIR --dataset acd_mix [--batch 8] [--batches 1] [--views 20] [--size 128] [--obj A.obj B.obj ...]
+
+writes the same triples for ACD mixes, the whole of generate.py:108-173 on the device (acd_mix_data): two
+objects are decomposed into convex hulls, augmented, merged and decomposed again, then rendered from --views cameras each.
+The objects are the vertices of the --obj files, paired at random as generate.py:120 does (at least two files); without
+--obj they are surface samples of random ellipsoid pairs.
 
     python examples/generate_views.py OUT_DIR --dataset point_mixup [--batch 8] [--batches 1] [--size 128]
 
@@ -95,12 +101,42 @@ def generate_point_mixup(clouds, out_dir, img_size=128, first=1):
     return len(meshes)
 
 
+@torch.no_grad()
+def generate_acd_mix(clouds1, clouds2, out_dir, n_views=20, img_size=128, first=0):
+    """generate.py:125-173 for S pairs of objects given as clouds [S,N,3]: -> the number of triples written, S * n_views."""
+    from PIL import Image
+    from vpn_amd import acd_mix_data
+    os.makedirs(out_dir, exist_ok=True)
+    rgba, centred, _gt, dists, elevs, azims, parts = acd_mix_data(clouds1, clouds2, views=n_views, img_size=img_size, return_parts=True)
+    rgba8 = (rgba.clamp(0.0, 1.0) * 255.0).to(torch.uint8).permute(0, 1, 3, 4, 2).cpu().numpy()     # ToPILImage's quantisation
+    centred, faces = centred.cpu(), parts['faces'].cpu()
+    dists, elevs, azims = dists.cpu(), elevs.cpu(), azims.cpu()
+    n = first
+    for s in range(rgba8.shape[0]):
+        for v in range(n_views):
+            Image.fromarray(rgba8[s, v], 'RGBA').save(os.path.join(out_dir, 'img_%.6d.png' % n))
+            TriangleMesh(centred[s, v], faces).save_mesh(os.path.join(out_dir, 'mesh_%.6d.obj' % n))
+            with open(os.path.join(out_dir, 'meta_%.6d.json' % n), 'w') as f:
+                f.write(json.dumps({'dist': float(dists[s, v]), 'elev': float(elevs[s, v]), 'azim': float(azims[s, v])}))
+            n += 1
+    return n - first
+
+
+def obj_cloud_pairs(paths, B, n=2048, device='cuda'):
+    """B random pairs of the OBJ files' vertex clouds (generate.py:120-126), each resampled to n vertices with replacement."""
+    import random
+    clouds = [TriangleMesh.from_obj(p).vertices.float() for p in paths]
+    pick = lambda v: v[torch.randint(0, v.size(0), (n,))]
+    pairs = [random.sample(clouds, 2) for _ in range(B)]
+    return torch.stack([pick(a) for a, _ in pairs]).to(device), torch.stack([pick(b) for _, b in pairs]).to(device)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('out_dir')
-    ap.add_argument('-d', '--dataset', default='views', choices=['views', 'point_mixup'], help='what to write (generate.py -d)')
-    ap.add_argument('--batch', type=int, default=8, help='point_mixup: samples per batch (config.py:9)')
-    ap.add_argument('--batches', type=int, default=1, help='point_mixup: batches to write')
+    ap.add_argument('-d', '--dataset', default='views', choices=['views', 'point_mixup', 'acd_mix'], help='what to write (generate.py -d)')
+    ap.add_argument('--batch', type=int, default=8, help='point_mixup / acd_mix: samples per batch (config.py:9)')
+    ap.add_argument('--batches', type=int, default=1, help='point_mixup / acd_mix: batches to write')
     ap.add_argument('--views', type=int, default=20)
     ap.add_argument('--size', type=int, default=128)
     ap.add_argument('--seed', type=int, default=0)
@@ -113,6 +149,19 @@ def main():
         for _ in range(args.batches):
             n += generate_point_mixup(default_clouds(args.batch), args.out_dir, args.size, first=n + 1)
         print('wrote %d rgb / silhouette / mesh triples to %s' % (n, args.out_dir))
+        return
+    if args.dataset == 'acd_mix':
+        import random
+        random.seed(args.seed)
+        n = 0
+        for _ in range(args.batches):
+            if args.obj:
+                assert len(args.obj) >= 2, 'a mix needs two objects'
+                c1, c2 = obj_cloud_pairs(args.obj, args.batch)
+            else:
+                c1, c2 = default_clouds(args.batch), default_clouds(args.batch)
+            n += generate_acd_mix(c1, c2, args.out_dir, args.views, args.size, first=n)
+        print('wrote %d img / mesh / meta triples to %s' % (n, args.out_dir))
         return
     if args.obj:
         mesh, uv, texture = merge_meshes([TriangleMesh.from_obj(p).cuda() for p in args.obj])

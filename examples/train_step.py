@@ -91,8 +91,16 @@ def augment_batch(batch, which, it):
     """train.py:232-237 on the HIP augmentation stage, in the reference's order.  The stand-in network reads features, not
     pixels, so the mixed rgbs (here: the silhouette repeated over three channels) have no consumer.  `mixup` moves the
     points only; `pointmixup` is the whole point_mixup_data: mixed clouds, a mesh of convex parts from each, its render as
-    the new silhouette and its surface samples as the new points."""
+    the new silhouette and its surface samples as the new points.  `acdmix` is the data of train.py -a_mix
+    made on the fly (generate.py:108-173): every sample's cloud is mixed with its successor's as two objects,
+    and one random view of the mix gives the silhouette, the points and the camera."""
     feats, gt_points, gt_sil, dists, elevs, azims, angles, kinds = batch
+    if 'acdmix' in which:
+        torch.manual_seed(4000 + it)
+        rgba, _verts, gt, d, e, a = vpn_amd.acd_mix_data(gt_points, gt_points.roll(1, 0), views=1, img_size=gt_sil.shape[-1],
+                                                         num_points=gt_points.shape[1])
+        gt_points, gt_sil = gt[:, 0].contiguous(), (rgba[:, 0, 3:4] > 0.5).float()
+        dists, elevs, azims = d[:, 0].contiguous(), e[:, 0].contiguous(), a[:, 0].contiguous()
     if 'rotate' in which:
         gt_points = vpn_amd.rotate_points_forward_x_axis(gt_points, angles)
     if 'cutmix' in which:
@@ -114,10 +122,10 @@ def main():
     ap.add_argument('--sample-num', type=int, default=128)   # config.py:8
     ap.add_argument('--size', type=int, default=128)         # config.py:49
     ap.add_argument('--fused', action='store_true', help='the whole loss as one autograd node (TrainStepLossFunction)')
-    ap.add_argument('--augment', default='', help='comma-separated subset of rotate,cutmix,mixup,pointmixup (config.py AUGMENT_3D; default: none)')
+    ap.add_argument('--augment', default='', help='comma-separated subset of rotate,cutmix,mixup,pointmixup,acdmix (config.py AUGMENT_3D; default: none)')
     args = ap.parse_args()
     augment = [a for a in args.augment.split(',') if a]
-    assert set(augment) <= {'rotate', 'cutmix', 'mixup', 'pointmixup'}, augment
+    assert set(augment) <= {'rotate', 'cutmix', 'mixup', 'pointmixup', 'acdmix'}, augment
     losses = training_losses_fused if args.fused else training_losses
     dev = torch.device('cuda')
     torch.manual_seed(1234)

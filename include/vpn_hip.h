@@ -62,6 +62,12 @@ extern "C" {
  * one workgroup's LDS */
 #define VPN_CLUSTER_MAX_POINTS 8192
 #define VPN_CLUSTER_MAX_HULLS 32
+/* most hulls, directions, samples and candidates vpn_hull_augment / vpn_union_surface take: the directions (16 bytes each),
+ * the G * D support values and the nc survivor indices of a sample live in one workgroup's LDS (132 KiB at the limits) */
+#define VPN_UNION_MAX_HULLS 64
+#define VPN_UNION_MAX_DIRS 256
+#define VPN_UNION_MAX_SAMPLES 65535
+#define VPN_UNION_MAX_CAND 16384
 /* largest K vpn_vis_primitives takes: the records of one (sample, view) live in one workgroup's LDS (116 bytes each) */
 #define VPN_VIS_MAX_PRIMS 512
 
@@ -647,6 +653,53 @@ int vpn_cluster_points(const float* points, int B, int n, int H, int iters, int3
                        int32_t* counts, void* stream);
 int vpn_support_hulls(const float* points, const int32_t* labels, const float* centres, const float* dirs, int B, int n,
                       int H, int D, float* verts, int32_t* support, void* stream);
+
+/* ---- the middle of the ACD-mix stage (generate.py:140-148 with modules/augmentation/acd.py:31-77,114-119):
+ * the hulls of the objects of a mix are augmented per object and merged.  The reference merges them with
+ * trimesh.boolean.union (acd.py:105-111) on the host and decomposes the result again; this REPLACES the boolean by sampling
+ * the surface of the union: candidates drawn on all augmented hulls survive unless they lie inside another kept hull, and
+ * the surviving cloud is hulled again (vpn_cluster_points / vpn_support_hulls).  Parity with trimesh is unpinned; the
+ * specification is restated by tests/acdmix_ref.py and the outputs equal it bit for bit.  Forward only; plain launches on
+ * `stream`; no floating-point atomics; nothing is allocated.  Inputs must be finite (not checked on the device).  fp32
+ * arithmetic is rounded per operation, dot(p, d) = (px dx + py dy) + pz dz.  G <= VPN_UNION_MAX_HULLS, D <=
+ * VPN_UNION_MAX_DIRS, S <= VPN_UNION_MAX_SAMPLES, nc <= VPN_UNION_MAX_CAND: VPN_E_TOOBIG beyond, before any HIP call.  Added
+ * without a change of VPN_ABI_VERSION.
+ * vpn_hull_augment (acd.py:31-77,114-119): verts [S,G,D,3] = G hulls of D vertices per sample, group [G] int32 = the object
+ *   a hull belongs to (0 .. O-1; for a mix of two objects of H hulls G = 2 H, O = 2; a hull with another value belongs to no
+ *   object and is cut) -> out [S,G,D,3], keep [S,G] int32 (1 kept, 0 cut).  The draws of the reference come as data, per
+ *   (sample, object) [S,O]: coin int32 (random.choice([True, False]), acd.py:70), u_num fp32 in [0,1) (for random.randint(1,
+ *   |C|-1), :71), scale fp32 (:38), turn int32 0..4 indexing {90, -90, 0, 180, -180} degrees (:59; another value turns
+ *   nothing), shift fp32 (:47); and per hull u_hull [S,G] fp32, the keys that stand for random.sample (:72).  One workgroup
+ *   per (object, sample).
+ *   is_center(h) (:31-34) = (some z > 0 and some z < 0) or some |z| < 0.05 over the D vertices of h as given.  With C the
+ *   centre hulls of the object: if coin != 0 and |C| > 1, 1 + floor(u_num * (|C|-1)) hulls are cut, clamped to 1 .. |C|-1:
+ *   those of C with the smallest u_hull, equal keys to the lowest hull index; every other hull of the object is kept (:73).
+ *   Otherwise exactly C is kept (:75).  THE ONE DEVIATION: if C is empty all hulls of the object are kept (the reference
+ *   goes on with an empty list and fails in the boolean).
+ *   A kept hull gets, in the reference's order (:115-118): v *= scale; the turn about z; y += shift.  The turn is an exact
+ *   signed swap: rotate_points with axis (0,0,1) multiplies by R = [[c,-s,0],[s,c,0],[0,0,1]] (rotate.py:23,36-44, angle / 360
+ *   mod 1 turns, so -90 is 270 degrees): 90: (x,y) -> (-y,x); -90: (x,y) -> (y,-x); 0: unchanged; 180 and -180: (x,y) ->
+ *   (-x,-y).  The reference's route through sinf / cosf of fp32 pi and a normalised quaternion gives these up to rounding
+ *   (sin(pi) != 0 in fp32); the exact swap is what is specified here.  A cut hull collapses onto its first vertex as given
+ *   (D copies): all its faces have zero area, which the mesh sampler and the rasters ignore.
+ * vpn_union_surface: verts [S,G,D,3] and keep [S,G] as written above, dirs [D,3] the template's directions, cand [S,nc,3]
+ *   candidates with cand_hull [S,nc] int32 = the hull a candidate was drawn on -> support [S,G,D], outside [S,nc] int32,
+ *   points [S,n_out,3], src [S,n_out] int32, count [S] int32.  One workgroup per sample.
+ *     support[h,d] = max_j dot(verts[h,j], dirs[d]) over the hull's own D vertices (the first of equal values), for every
+ *       hull, cut or kept;
+ *     p is outside h in direction d iff dot(p, dirs[d]) > support[h,d] - margin (the subtraction rounded to fp32); p is
+ *       inside h iff no direction says outside;
+ *     outside[c] = 1 iff candidate c's own hull is kept (cand_hull in [0,G) and keep != 0) and c is inside no other kept
+ *       hull; count = the number of such candidates;
+ *     points / src = the survivors in candidate order (stable compaction): slot i < count is survivor i, slot i >= count
+ *       repeats survivor i mod count; count == 0 falls back to the candidates themselves, src[i] = i mod nc.
+ *   points[s,i] is cand[s,src[s,i]] bit for bit.  margin: any finite fp32 (NaN is VPN_E_BADARG). */
+int vpn_hull_augment(const float* verts, const int32_t* group, const int32_t* coin, const float* u_num, const float* scale,
+                     const int32_t* turn, const float* shift, const float* u_hull, int S, int G, int D, int O, float* out,
+                     int32_t* keep, void* stream);
+int vpn_union_surface(const float* verts, const int32_t* keep, const float* dirs, const float* cand, const int32_t* cand_hull,
+                      int S, int G, int D, int nc, int n_out, float margin, float* support, int32_t* outside, float* points,
+                      int32_t* src, int32_t* count, void* stream);
 
 #ifdef __cplusplus
 }

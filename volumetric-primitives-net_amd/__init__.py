@@ -8,12 +8,13 @@ from .ops import (SPHERE, CUBOID, SampleFunction, TransformFunction, ChamferFunc
                   CameraTransformFunction, RasterFunction,
                   RasterLossFunction, RasterTotalFunction, HotPathLossFunction, TrainStepLossFunction, chamfer_nn, kinds_tensor,
                   emd_recovered_samples, emd_last_group, eval_step, vis_primitives, vis_mesh, phong_mesh,
-                  cluster_points, support_hulls, hull_meshes)
+                  cluster_points, support_hulls, hull_meshes, hull_augment, union_surface, acd_mix_points)
 from .primitives import PrimitivePack, pack_primitives, kinds_from_counts
 from .modules import (Sampling, ChamferDistanceLoss, EarthMoverDistanceLoss, SilhouetteLoss, VPDiverseLoss, VertexRenderer, PhongRenderer,
                       transform_points, rotate_points, translate_points, view_to_obj_points,
                       obj_to_view_points, rotate_points_forward_x_axis, pack_head_outputs, split_primitives, Meshing, TriangleMesh, load_obj, merge_meshes,
                       cut_mix_data, cut_mix_batch_points, adjust_point_num, mixup_points, point_mixup_data,
-                      points_to_meshes_and_colors, points_to_mesh_batch, meshes_to_imgs, generate_point_mixup_data, EvaluationMeter,
+                      points_to_meshes_and_colors, points_to_mesh_batch, meshes_to_imgs, generate_point_mixup_data, acd, augment,
+                      acd_mix_meshes, acd_mix_data, EvaluationMeter,
                       Visualizer)
 from . import modules

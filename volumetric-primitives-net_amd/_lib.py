@@ -98,6 +98,8 @@ SIGNATURES = {
     'vpn_phong_mesh': (_i, [_c_f] * 7 + [_f] + [_i] * 8 + [_c_f, _c_f, _c_f]),
     'vpn_cluster_points': (_i, [_c_f, _i, _i, _i, _i, _c_f, _c_f, _c_f, _c_f]),
     'vpn_support_hulls': (_i, [_c_f, _c_f, _c_f, _c_f, _i, _i, _i, _i, _c_f, _c_f, _c_f]),
+    'vpn_hull_augment': (_i, [_c_f] * 8 + [_i] * 4 + [_c_f, _c_f, _c_f]),
+    'vpn_union_surface': (_i, [_c_f] * 5 + [_i] * 5 + [_f] + [_c_f] * 6),
 }
 
 _lib = None

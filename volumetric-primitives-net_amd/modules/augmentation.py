@@ -21,7 +21,13 @@ an inner approximation of the cluster's convex hull with all vertices on it.  Al
 so the render and the re-sampling are one launch each for the batch.  Parity with the reference's meshes is unpinned;
 the atlas rule (uv = i / n + 0.01, one torch.rand(3) per hull) is convex_decomposition.py:32-58's.
 
-Out of scope (host-side mesh processing through trimesh / an external binary): acd.py."""
+The ACD-mix data of generate.py:108-173 (acd.py) runs on the device as well, with a third deliberate deviation (DESIGN.md
+4.13): the hulls of the two objects are ops.hull_meshes' (as above), and trimesh.boolean.union is REPLACED by a sampled
+union surface: candidates drawn on all augmented hulls survive unless they lie inside another kept hull, and the surviving
+cloud is hulled again.  The reference's draws through Python's `random` (acd.py:59,70-72) are drawn from torch's CPU
+generator instead, always (the reference skips random.randint when the coin says no), in the order stated at acd_mix_data."""
+import collections
+
 import torch
 
 from .. import config, ops
@@ -239,3 +245,162 @@ def generate_point_mixup_data(view_center_points: torch.Tensor, *, ratio=None, i
     rgbs, silhouettes, parts = _mixup_batch(view_center_points, ratio, indices, colors, hull_num, iters, img_size, eps, emd_iters)
     verts, faces = parts['verts'], parts['faces']
     return rgbs, silhouettes, [TriangleMesh.from_tensors(verts[b], faces) for b in range(verts.size(0))]
+
+
+# ---- ACD-mix data: generate.py:108-173 with acd.py on the device (csrc/acdmix.hip)
+
+ACD_HULL_NUM = 8                         # acd.py:24, generate.py:148
+ACD_VIEWS = 20                           # generate.py:150
+ACD_POINTS = 2048                        # acd_mix.py:73
+ACD_UNION_POINTS = 2048                  # the size of the union-surface cloud that is hulled again
+ACD_MARGIN = 1e-3                        # how deep inside another hull a candidate must lie to be dropped
+ACD_TURNS = (90.0, -90.0, 0.0, 180.0, -180.0)      # acd.py:59
+
+MeshBatch = collections.namedtuple('MeshBatch', ['vertices', 'faces'])      # [S,P,3] and the [F,3] int32 all samples share
+
+
+def acd(points: torch.Tensor, hull_num: int = ACD_HULL_NUM, *, iters=LLOYD_ITERS, template=None):
+    """acd.py:24-28 on a batch of clouds: points [B,N,3] -> hulls [B,hull_num,D,3], every hull the support polytope of one
+    cluster along the template's D directions (ops.hull_meshes; what replaces V-HACD, see the module text)."""
+    check_parameters(points)
+    verts, _faces, _labels, _support = ops.hull_meshes(points, int(hull_num), iters, template)
+    B = verts.size(0)
+    return verts.reshape(B, int(hull_num), -1, 3)
+
+
+def _augment_draws(S, O, H, coin, u_num, scale, turn, shift, u_hull):
+    """The draws of acd.augment for O objects of H hulls per sample, sample after sample, object after object, each in the
+    reference's order (acd.py:114-119): the coin and the number of the cut-out (:70-71), the keys of its choice (:72), the
+    scale (:38), the turn (:59), the shift (:47).  A draw that is given is not drawn."""
+    need = dict(coin=coin is None, u_num=u_num is None, u_hull=u_hull is None, scale=scale is None, turn=turn is None, shift=shift is None)
+    d = dict(coin=torch.zeros(S, O, dtype=torch.int32), u_num=torch.zeros(S, O), u_hull=torch.zeros(S, O * H), scale=torch.zeros(S, O),
+             turn=torch.zeros(S, O, dtype=torch.int32), shift=torch.zeros(S, O))
+    for s in range(S):
+        for o in range(O):
+            if need['coin']:
+                d['coin'][s, o] = int(torch.randint(0, 2, (1,)).item())
+            if need['u_num']:
+                d['u_num'][s, o] = torch.rand(1).item()
+            if need['u_hull']:
+                d['u_hull'][s, o * H:(o + 1) * H] = torch.rand(H)
+            if need['scale']:
+                d['scale'][s, o] = 0.8 + torch.rand(1).item() * 0.4                     # s ~ [0.8, 1.2]
+            if need['turn']:
+                d['turn'][s, o] = int(torch.randint(0, len(ACD_TURNS), (1,)).item())
+            if need['shift']:
+                d['shift'][s, o] = (torch.rand(1).item() - 0.5) / 5                     # t ~ [-0.1, 0.1]
+    given = dict(coin=coin, u_num=u_num, scale=scale, turn=turn, shift=shift, u_hull=u_hull)
+    return {k: (d[k] if need[k] else given[k]) for k in d}
+
+
+def augment(hulls: torch.Tensor, *, coin=None, u_num=None, scale=None, turn=None, shift=None, u_hull=None):
+    """acd.py:114-119 for the hulls of ONE object per sample: hulls [S,H,D,3] -> (augmented hulls [S,H,D,3], keep [S,H]
+    int32).  A hull the cut-out removes stays in the tensor, collapsed onto its first vertex (keep == 0): the topology is
+    fixed.  Draws ([S,1] each, u_hull [S,H]; see _augment_draws) come from torch's CPU generator when not given."""
+    assert hulls.ndimension() == 4 and hulls.size(-1) == 3          # (S, H, D, 3)
+    S, H = hulls.size(0), hulls.size(1)
+    d = _augment_draws(S, 1, H, coin, u_num, scale, turn, shift, u_hull)
+    group = ops.const_tensor((0,) * H, torch.int32, hulls.device)
+    return ops.hull_augment(hulls, group, d['coin'], d['u_num'], d['scale'], d['turn'], d['shift'], d['u_hull'])
+
+
+def _normalised(points):
+    return points / points.amax(dim=(1, 2), keepdim=True)          # generate.py:128-129: vertices /= vertices.max()
+
+
+def _acd_mix_cloud(points1, points2, draws, hull_num, iters, union_points, n_cand, margin, seed, sample_base, template, normalize):
+    check_parameters(points1)
+    check_parameters(points2)
+    assert points1.size(0) == points2.size(0)
+    ops._augment_is_data(points1, points2)
+    p1, p2 = points1.detach().float(), points2.detach().float()
+    if normalize:
+        p1, p2 = _normalised(p1), _normalised(p2)
+    h1 = acd(p1, hull_num, iters=iters, template=template)
+    h2 = acd(p2, hull_num, iters=iters, template=template)
+    return ops.acd_mix_points(h1, h2, draws['coin'], draws['u_num'], draws['scale'], draws['turn'], draws['shift'], draws['u_hull'],
+                              union_points, seed, sample_base, n_cand=n_cand, margin=margin, template=template)
+
+
+def acd_mix_meshes(points1: torch.Tensor, points2: torch.Tensor, *, coin=None, u_num=None, scale=None, turn=None, shift=None,
+                   u_hull=None, colors=None, seed=None, sample_base=0, hull_num=ACD_HULL_NUM, mix_hull_num=ACD_HULL_NUM,
+                   iters=LLOYD_ITERS, union_points=ACD_UNION_POINTS, n_cand=None, margin=ACD_MARGIN, template=None,
+                   normalize=True, return_parts=False):
+    """generate.py:125-148 for S pairs of objects given as clouds [S,N,3]: normalise, decompose each into hull_num hulls
+    (acd), augment per object, merge, decompose the merge into mix_hull_num hulls with a texture atlas -> (MeshBatch(vertices
+    [S,P,3], faces [F,3] int32), uv [S,P,2], texture [S,3,1,mix_hull_num]), through points_to_mesh_batch.  Draws when not
+    given, from torch's CPU generator: the augment draws ([S,2] each, u_hull [S,2 hull_num]; _augment_draws), then one
+    colour per hull mesh after mesh (colors [S,mix_hull_num,3]), then seed, the Philox key of the candidates (one
+    torch.randint; sample_base + s names sample s).  return_parts=True appends ops.acd_mix_points' dict plus cloud and count."""
+    S = points1.size(0)
+    d = _augment_draws(S, 2, int(hull_num), coin, u_num, scale, turn, shift, u_hull)
+    if colors is None:
+        colors = torch.stack([torch.rand(3) for _ in range(S * int(mix_hull_num))]).reshape(S, int(mix_hull_num), 3)
+    cloud, count, parts = _acd_mix_cloud(points1, points2, d, hull_num, iters, union_points, n_cand, margin, _philox_seed(seed),
+                                         sample_base, template, normalize)
+    verts, faces, uv, texture = points_to_mesh_batch(cloud, hull_num=mix_hull_num, iters=iters, colors=colors, template=template)
+    out = (MeshBatch(verts, faces), uv, texture)
+    if return_parts:
+        parts.update(cloud=cloud, count=count)
+        return out + (parts,)
+    return out
+
+
+def _acd_cameras(S, V, cams, dev):
+    """cams [S,V,3] = (dist, elev, azim) on the device; drawn as generate.py:153-155 does, view after view, when not given."""
+    if cams is None:
+        rows = []
+        for _ in range(S * V):
+            dist = 3.0 + torch.rand(1).item() * 2
+            elev = (torch.rand(1).item() - 0.5) * 90
+            azim = torch.rand(1).item() * 360
+            rows.append((dist, elev, azim))
+        cams = torch.tensor(rows, dtype=torch.float32).reshape(S, V, 3)
+    return ops._draw_tensor('cams', cams, (S, V, 3), torch.float32, dev)
+
+
+def acd_mix_data(points1: torch.Tensor, points2: torch.Tensor, *, views=ACD_VIEWS, img_size=None, num_points=ACD_POINTS,
+                 coin=None, u_num=None, scale=None, turn=None, shift=None, u_hull=None, colors=None, cams=None, seed=None,
+                 gt_seed=None, sample_base=0, hull_num=ACD_HULL_NUM, mix_hull_num=ACD_HULL_NUM, iters=LLOYD_ITERS,
+                 union_points=ACD_UNION_POINTS, n_cand=None, margin=ACD_MARGIN, template=None, normalize=True, return_parts=False):
+    """generate.py:119-173 with ACDMixDataset.load_points (acd_mix.py:71-73) for S pairs of objects given as clouds
+    [S,N,3] -> (rgba [S,V,4,I,I] (the Phong render and the soft silhouette, the img_*.png of :157-167), the mesh vertices
+    in each view's frame [S,V,P,3] (mesh_*.obj, :164-168), gt_points [S,V,num_points,3] sampled on those meshes, dists,
+    elevs, azims [S,V] (meta_*.json)), I = img_size (default config.IMG_SIZE), V = views.  The faces are
+    parts['faces'] (return_parts=True appends acd_mix_meshes' dict plus faces, uv, texture, verts, cams, face_idx, bary).
+    Draws when not given, from torch's CPU generator, in the reference's order as far as it has one: the augment draws of
+    all samples (_augment_draws), one colour per hull mesh after mesh, the cameras (dist 3 .. 5, elev -45 .. 45, azim 0 ..
+    360, :153-155) view after view; then the two Philox keys the reference has no counterpart of: seed (the candidates of the
+    union surface) and gt_seed (the ground-truth points; mesh sample_base + s V + v).  All views of all scenes are one
+    ops.phong_mesh launch pair, one silhouette batch, one obj_to_view_points and one sample_meshes; no host
+    synchronisation: with the draws given the call can be captured into a HIP graph."""
+    from .render import PhongRenderer, VertexRenderer
+    from .transform import obj_to_view_points
+    S, V = points1.size(0), int(views)
+    d = _augment_draws(S, 2, int(hull_num), coin, u_num, scale, turn, shift, u_hull)
+    if colors is None:
+        colors = torch.stack([torch.rand(3) for _ in range(S * int(mix_hull_num))]).reshape(S, int(mix_hull_num), 3)
+    cams = _acd_cameras(S, V, cams, points1.device)
+    seed, gt_seed = _philox_seed(seed), _philox_seed(gt_seed)
+    (verts, faces), uv, texture, parts = acd_mix_meshes(points1, points2, colors=colors, seed=seed, sample_base=sample_base,
+                                                        hull_num=hull_num, mix_hull_num=mix_hull_num, iters=iters,
+                                                        union_points=union_points, n_cand=n_cand, margin=margin, template=template,
+                                                        normalize=normalize, return_parts=True, **d)
+    I = int(config.IMG_SIZE if img_size is None else img_size)
+    P = verts.size(1)
+    rgb = ops.phong_mesh(verts, faces, uv, texture, cams, I, I, light=PhongRenderer.light, material=PhongRenderer.material,
+                         shininess=PhongRenderer.shininess)                                     # [S,V,I,I,3]
+    flat_cams = cams.reshape(S * V, 3)
+    per_view = verts[:, None].expand(S, V, P, 3).reshape(S * V, P, 3)
+    alpha = ops.MeshRasterFunction.apply(per_view, faces, flat_cams, I, I, VertexRenderer.mesh_sigma)          # [S*V,I,I]
+    dists, elevs, azims = (flat_cams[:, k].contiguous() for k in range(3))
+    centred = obj_to_view_points(per_view, dists, elevs, azims)                                 # generate.py:164-165
+    gt_points, face_idx, bary = ops.sample_meshes(centred, faces, num_points, gt_seed, int(sample_base) * V)
+    rgba = torch.cat([rgb.permute(0, 1, 4, 2, 3), alpha.reshape(S, V, 1, I, I)], 2)
+    out = (rgba, centred.reshape(S, V, P, 3), gt_points.reshape(S, V, int(num_points), 3), dists.reshape(S, V), elevs.reshape(S, V),
+           azims.reshape(S, V))
+    if return_parts:
+        parts.update(faces=faces, uv=uv, texture=texture, verts=verts, cams=cams, face_idx=face_idx.reshape(S, V, -1),
+                     bary=bary.reshape(S, V, -1, 3))
+        return out + (parts,)
+    return out

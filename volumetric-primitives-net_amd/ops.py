@@ -1343,6 +1343,103 @@ def sample_meshes(verts, faces, n, seed, mesh_base=0):
     return points, fidx, bary
 
 
+# ---- the middle of the ACD-mix stage (csrc/acdmix.hip): acd.py:31-77,114-119 and the merge of
+# generate.py:140-148, the boolean union replaced by a sampled union surface.  Data, like the rest of the augmentation stage.
+
+def _draw_tensor(name, value, shape, dtype, dev):
+    """A draw of the stage as the contiguous device tensor the kernels read: a device tensor is checked and converted at
+    most; host values are uploaded from pinned memory without blocking."""
+    if isinstance(value, torch.Tensor) and value.is_cuda:
+        _augment_is_data(value)
+        if tuple(value.shape) != tuple(shape):
+            raise ValueError('%s must be %s, got %s' % (name, tuple(shape), tuple(value.shape)))
+        return value.detach().to(dtype).contiguous()
+    host = torch.as_tensor(value).detach().to(dtype)
+    if tuple(host.shape) != tuple(shape):
+        raise ValueError('%s must be %s, got %s' % (name, tuple(shape), tuple(host.shape)))
+    host = host.contiguous()
+    return host.pin_memory().to(dev, non_blocking=True) if torch.device(dev).type == 'cuda' else host
+
+
+def hull_augment(verts, group, coin, u_num, scale, turn, shift, u_hull):
+    """vpn_hull_augment: verts [S,G,D,3], group [G] (the object of each hull, 0 .. O-1), the draws per (sample, object)
+    coin / u_num / scale / turn / shift [S,O] and the keys u_hull [S,G] (host values or device tensors) -> (out [S,G,D,3],
+    keep [S,G] int32): cut-out, scale, quarter turn about z, shift along y (include/vpn_hip.h)."""
+    _augment_is_data(verts)
+    if verts.dim() != 4 or verts.size(3) != 3:
+        raise ValueError('verts must be [S,G,D,3], got %s' % (tuple(verts.shape),))
+    verts = _f32c(verts.detach())
+    S, G, D, _ = verts.shape
+    dev = verts.device
+    group = _draw_tensor('group', group, (G,), torch.int32, dev)
+    coin_t = torch.as_tensor(coin)
+    if coin_t.dim() != 2 or coin_t.size(0) != S:
+        raise ValueError('coin must be [S,O] with S = %d, got %s' % (S, tuple(coin_t.shape)))
+    O = coin_t.size(1)
+    coin, turn = (_draw_tensor(n, v, (S, O), torch.int32, dev) for n, v in (('coin', coin_t), ('turn', turn)))
+    u_num, scale, shift = (_draw_tensor(n, v, (S, O), torch.float32, dev) for n, v in (('u_num', u_num), ('scale', scale), ('shift', shift)))
+    u_hull = _draw_tensor('u_hull', u_hull, (S, G), torch.float32, dev)
+    out = torch.empty_like(verts)
+    keep = torch.empty((S, G), dtype=torch.int32, device=dev)
+    _lib.call('vpn_hull_augment', verts, group, coin, u_num, scale, turn, shift, u_hull, S, G, D, O, out, keep, _lib.stream())
+    return out, keep
+
+
+def union_surface(verts, keep, dirs, cand, cand_hull, n_out, margin=1e-3):
+    """vpn_union_surface: verts [S,G,D,3], keep [S,G] int32, dirs [D,3], candidates cand [S,nc,3] with the hull each was
+    drawn on, cand_hull [S,nc] int32 -> (support [S,G,D], outside [S,nc] int32, points [S,n_out,3], src [S,n_out] int32,
+    count [S] int32): the candidates that lie inside no other kept hull, in candidate order, repeated cyclically up to
+    n_out (include/vpn_hip.h)."""
+    _augment_is_data(verts, dirs, cand)
+    if (verts.dim() != 4 or verts.size(3) != 3 or dirs.dim() != 2 or tuple(dirs.shape) != (verts.size(2), 3) or cand.dim() != 3
+            or cand.size(2) != 3 or cand.size(0) != verts.size(0) or keep.dtype != torch.int32 or tuple(keep.shape) != tuple(verts.shape[:2])
+            or cand_hull.dtype != torch.int32 or tuple(cand_hull.shape) != tuple(cand.shape[:2])):
+        raise ValueError('union_surface: verts [S,G,D,3], keep [S,G] int32, dirs [D,3], cand [S,nc,3], cand_hull [S,nc] int32 expected, '
+                         'got %s %s %s %s %s %s %s' % (tuple(verts.shape), keep.dtype, tuple(keep.shape), tuple(dirs.shape),
+                                                     tuple(cand.shape), cand_hull.dtype, tuple(cand_hull.shape)))
+    verts, dirs, cand = _f32c(verts.detach()), _f32c(dirs.detach()), _f32c(cand.detach())
+    S, G, D, _ = verts.shape
+    nc, n_out = cand.size(1), int(n_out)
+    dev = verts.device
+    support = torch.empty((S, G, D), dtype=torch.float32, device=dev)
+    outside = torch.empty((S, nc), dtype=torch.int32, device=dev)
+    points = torch.empty((S, n_out, 3), dtype=torch.float32, device=dev)
+    src = torch.empty((S, n_out), dtype=torch.int32, device=dev)
+    count = torch.empty((S,), dtype=torch.int32, device=dev)
+    _lib.call('vpn_union_surface', verts, keep.contiguous(), dirs, cand, cand_hull.contiguous(), S, G, D, nc, n_out, float(margin),
+              support, outside, points, src, count, _lib.stream())
+    return support, outside, points, src, count
+
+
+def acd_mix_points(hulls1, hulls2, coin, u_num, scale, turn, shift, u_hull, n_out, seed, mesh_base=0, *, n_cand=None,
+                   margin=1e-3, template=None):
+    """The hulls of two objects -> a cloud on the surface of their augmented union (generate.py:140-146): hulls1 / hulls2
+    [S,H,D,3] (ops.hull_meshes' vertices of each object, D the template's), the draws of hull_augment with O = 2 and G = 2 H
+    (object 1's hulls first).  Three steps, four launches, no host synchronisation: hull_augment; n_cand (default 2 n_out)
+    area-weighted candidates on the merged hulls by sample_meshes (Philox(seed; mesh_base + s, point); the hull of a
+    candidate is its face // Ft); union_surface.  -> (points [S,n_out,3], count [S] int32, parts), parts a dict: hulls
+    (augmented, [S,G,D,3]), keep, faces, dirs, cand, cand_hull, support, outside, src."""
+    _augment_is_data(hulls1, hulls2)
+    if hulls1.dim() != 4 or hulls1.size(3) != 3 or tuple(hulls1.shape) != tuple(hulls2.shape):
+        raise ValueError('hulls1 and hulls2 must both be [S,H,D,3], got %s and %s' % (tuple(hulls1.shape), tuple(hulls2.shape)))
+    S, H, D, _ = hulls1.shape
+    G = 2 * H
+    dev = hulls1.device
+    dirs, faces = hull_template(G, dev, template)
+    if dirs.size(0) != D:
+        raise ValueError('the hulls have %d vertices each, the template %d' % (D, dirs.size(0)))
+    group = const_tensor((0,) * H + (1,) * H, torch.int32, dev)
+    merged = torch.cat([_f32c(hulls1.detach()), _f32c(hulls2.detach())], 1)
+    hulls, keep = hull_augment(merged, group, coin, u_num, scale, turn, shift, u_hull)
+    n_out = int(n_out)
+    nc = 2 * n_out if n_cand is None else int(n_cand)
+    cand, face_idx, _bary = sample_meshes(hulls.reshape(S, G * D, 3), faces, nc, seed, mesh_base)
+    cand_hull = torch.div(face_idx, faces.size(0) // G, rounding_mode='floor')
+    support, outside, points, src, count = union_surface(hulls, keep, dirs, cand, cand_hull, n_out, margin)
+    return points, count, dict(hulls=hulls, keep=keep, faces=faces, dirs=dirs, cand=cand, cand_hull=cand_hull, support=support,
+                               outside=outside, src=src)
+
+
 # ---- the evaluation stage (csrc/evaluate.hip; test.py:68-135, test_gcn.py:115-178).  Plain functions: nothing is
 # differentiable, the metrics are reported values.
 
