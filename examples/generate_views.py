@@ -21,7 +21,11 @@ The objects are the vertices of the --obj files, paired at random as generate.py
 
 writes the files of generate.py:42-66 instead: per mixed sample `rgb_%d.png`, `silhouette_%d.png` and `mesh_%d.obj`, numbered
 from 1, made by generate_point_mixup_data.  Without a dataset the clouds are surface samples of random
-ellipsoid pairs."""
+ellipsoid pairs.
+
+--prepare (any dataset) also pushes what was rendered, still on the device, through prepare_images -- the transform the
+reference's loader applies to every image it opens (Resize to --size, ColorJitter) -- and writes the network
+input beside each image as `input_%.6d.png` (rgb and silhouette put back together as RGBA)."""
 import argparse
 import json
 import os
@@ -54,8 +58,18 @@ def random_cameras(n):
     return cams
 
 
+def write_prepared(rgba_u8, out_dir, first, img_size):
+    """rgba_u8 [N,H,W,4] uint8 on the device -> input_%.6d.png: what prepare_images makes of each rendering."""
+    from PIL import Image
+    from vpn_amd import prepare_images
+    rgb, sil, _ = prepare_images(rgba_u8.contiguous(), size=img_size)
+    out = (torch.cat([rgb, sil], 1) * 255.0).round().to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
+    for i in range(out.shape[0]):
+        Image.fromarray(out[i], 'RGBA').save(os.path.join(out_dir, 'input_%.6d.png' % (first + i)))
+
+
 @torch.no_grad()
-def generate(mesh, uv, texture, out_dir, n_views=20, img_size=128, first=0):
+def generate(mesh, uv, texture, out_dir, n_views=20, img_size=128, first=0, prepare=False):
     from PIL import Image
     os.makedirs(out_dir, exist_ok=True)
     cams = random_cameras(n_views)
@@ -64,7 +78,10 @@ def generate(mesh, uv, texture, out_dir, n_views=20, img_size=128, first=0):
     cam_t = torch.tensor(cams, dtype=torch.float32).to(dev)
     centred = obj_to_view_points(mesh.vertices.detach()[None].expand(n_views, -1, -1).contiguous(), cam_t[:, 0].contiguous(),
                                  cam_t[:, 1].contiguous(), cam_t[:, 2].contiguous())
-    rgba = (torch.cat([rgb, alpha], -1).clamp(0.0, 1.0) * 255.0).to(torch.uint8).cpu().numpy()      # ToPILImage's quantisation
+    rgba = (torch.cat([rgb, alpha], -1).clamp(0.0, 1.0) * 255.0).to(torch.uint8)                    # ToPILImage's quantisation
+    if prepare:
+        write_prepared(rgba, out_dir, first, img_size)
+    rgba = rgba.cpu().numpy()
     centred = centred.cpu()
     faces = mesh.faces.cpu()
     for j, (dist, elev, azim) in enumerate(cams):
@@ -85,14 +102,17 @@ def default_clouds(B, n=2048, device='cuda'):
 
 
 @torch.no_grad()
-def generate_point_mixup(clouds, out_dir, img_size=128, first=1):
+def generate_point_mixup(clouds, out_dir, img_size=128, first=1, prepare=False):
     """generate.py:54-66 for one batch of view-centred clouds [B,N,3]: -> the number of triples written."""
     from PIL import Image
     from vpn_amd import generate_point_mixup_data
     os.makedirs(out_dir, exist_ok=True)
     rgbs, silhouettes, meshes = generate_point_mixup_data(clouds, img_size=img_size)
-    rgb8 = (rgbs.clamp(0.0, 1.0) * 255.0).to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()         # ToPILImage's quantisation
-    sil8 = (silhouettes.clamp(0.0, 1.0) * 255.0).to(torch.uint8)[:, 0].cpu().numpy()
+    rgb8 = (rgbs.clamp(0.0, 1.0) * 255.0).to(torch.uint8).permute(0, 2, 3, 1)                       # ToPILImage's quantisation
+    sil8 = (silhouettes.clamp(0.0, 1.0) * 255.0).to(torch.uint8)[:, 0]
+    if prepare:
+        write_prepared(torch.cat([rgb8, sil8[..., None]], -1), out_dir, first, img_size)
+    rgb8, sil8 = rgb8.cpu().numpy(), sil8.cpu().numpy()
     for i, mesh in enumerate(meshes):
         n = first + i
         Image.fromarray(rgb8[i], 'RGB').save(os.path.join(out_dir, 'rgb_%d.png' % n))
@@ -102,13 +122,16 @@ def generate_point_mixup(clouds, out_dir, img_size=128, first=1):
 
 
 @torch.no_grad()
-def generate_acd_mix(clouds1, clouds2, out_dir, n_views=20, img_size=128, first=0):
+def generate_acd_mix(clouds1, clouds2, out_dir, n_views=20, img_size=128, first=0, prepare=False):
     """generate.py:125-173 for S pairs of objects given as clouds [S,N,3]: -> the number of triples written, S * n_views."""
     from PIL import Image
     from vpn_amd import acd_mix_data
     os.makedirs(out_dir, exist_ok=True)
     rgba, centred, _gt, dists, elevs, azims, parts = acd_mix_data(clouds1, clouds2, views=n_views, img_size=img_size, return_parts=True)
-    rgba8 = (rgba.clamp(0.0, 1.0) * 255.0).to(torch.uint8).permute(0, 1, 3, 4, 2).cpu().numpy()     # ToPILImage's quantisation
+    rgba8 = (rgba.clamp(0.0, 1.0) * 255.0).to(torch.uint8).permute(0, 1, 3, 4, 2)                   # ToPILImage's quantisation
+    if prepare:
+        write_prepared(rgba8.reshape((-1,) + tuple(rgba8.shape[2:])), out_dir, first, img_size)
+    rgba8 = rgba8.cpu().numpy()
     centred, faces = centred.cpu(), parts['faces'].cpu()
     dists, elevs, azims = dists.cpu(), elevs.cpu(), azims.cpu()
     n = first
@@ -141,13 +164,14 @@ def main():
     ap.add_argument('--size', type=int, default=128)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--obj', nargs='*', default=[], help='OBJ files, one per part of the atlas')
+    ap.add_argument('--prepare', action='store_true', help='also write input_%%.6d.png: each rendering after prepare_images')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'the renderer runs on the GPU only'
     torch.manual_seed(args.seed)
     if args.dataset == 'point_mixup':
         n = 0
         for _ in range(args.batches):
-            n += generate_point_mixup(default_clouds(args.batch), args.out_dir, args.size, first=n + 1)
+            n += generate_point_mixup(default_clouds(args.batch), args.out_dir, args.size, first=n + 1, prepare=args.prepare)
         print('wrote %d rgb / silhouette / mesh triples to %s' % (n, args.out_dir))
         return
     if args.dataset == 'acd_mix':
@@ -160,14 +184,14 @@ def main():
                 c1, c2 = obj_cloud_pairs(args.obj, args.batch)
             else:
                 c1, c2 = default_clouds(args.batch), default_clouds(args.batch)
-            n += generate_acd_mix(c1, c2, args.out_dir, args.views, args.size, first=n)
+            n += generate_acd_mix(c1, c2, args.out_dir, args.views, args.size, first=n, prepare=args.prepare)
         print('wrote %d img / mesh / meta triples to %s' % (n, args.out_dir))
         return
     if args.obj:
         mesh, uv, texture = merge_meshes([TriangleMesh.from_obj(p).cuda() for p in args.obj])
     else:
         mesh, uv, texture = default_mesh()
-    n = generate(mesh, uv, texture, args.out_dir, args.views, args.size)
+    n = generate(mesh, uv, texture, args.out_dir, args.views, args.size, prepare=args.prepare)
     print('wrote %d img / mesh / meta triples to %s' % (n, args.out_dir))
 
 

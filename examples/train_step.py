@@ -102,6 +102,13 @@ def augment_batch(batch, which, it):
         gt_points, gt_sil = gt[:, 0].contiguous(), (rgba[:, 0, 3:4] > 0.5).float()
         dists, elevs, azims = d[:, 0].contiguous(), e[:, 0].contiguous(), a[:, 0].contiguous()
     if 'rotate' in which:
+        # AUGMENT_3D['rotate'] (dataset.py:120-121, train.py): the image and the points turn by the SAME angle.  The stand-in
+        # image is the silhouette as an opaque-white RGBA rendering; prepare_images draws the angles, rotates the image
+        # (PIL's nearest-neighbour rotation) and returns them for the points.
+        S = gt_sil.shape[-1]
+        a = (gt_sil[:, 0] * 255).to(torch.uint8)
+        rgba = torch.stack([a, a, a, a], -1).contiguous()
+        _, gt_sil, angles = vpn_amd.prepare_images(rgba, size=S, jitter=False, rotate=True, seed=5000 + it)
         gt_points = vpn_amd.rotate_points_forward_x_axis(gt_points, angles)
     if 'cutmix' in which:
         _, gt_sil, gt_points = vpn_amd.cut_mix_data(gt_sil.expand(-1, 3, -1, -1), gt_sil, gt_points, seed=2000 + it)

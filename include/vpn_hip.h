@@ -701,6 +701,37 @@ int vpn_union_surface(const float* verts, const int32_t* keep, const float* dirs
                       int S, int G, int D, int nc, int n_out, float margin, float* support, int32_t* outside, float* points,
                       int32_t* src, int32_t* count, void* stream);
 
+/* ---- the image input stage (csrc/input.hip; modules/dataset/dataset.py:15-19,115-139 of the reference):
+ * an RGBA rendering becomes the network input and the GT silhouette through PIL's Resize(BILINEAR), ColorJitter and
+ * rotate(NEAREST), every pixel operation in PIL's own integer or per-operation-rounded fp32 arithmetic: the outputs equal
+ * PIL's bit for bit (restated by tests/input_ref.py).  Forward only; three plain launches on `stream` (setup, resize,
+ * finish); the only atomics are 64-bit integer adds (one sum per image, independent of their order); nothing is allocated.
+ * Added without a change of VPN_ABI_VERSION.
+ *   rgba [B,Hs,Ws,4] uint8 (R,G,B,A bytes, 4-byte aligned) -> inter [B,H,W,4] uint8, the resized image (Hs == H and
+ *     Ws == W: a copy, as PIL); rgb [B,3,H,W], silhouette [B,1,H,W] fp32 = level / 255 (IEEE division) after jitter and
+ *     rotation; angles_out [B] fp32 degrees, the angle each image was rotated by (0 without VPN_INPUT_ROTATE).
+ *   tables: int32, hb [W,2] | hk [W,ksh] | vb [H,2] | vk [H,ksv]: for every output column / row the first source tap and
+ *     the tap count, and the taps' coefficients round(k 2^22), built by the host in float64 as PIL's precompute_coeffs does.
+ *     max_rows: the most source rows the vertical support of 8 consecutive output rows spans (the LDS of one tile: 128
+ *     max_rows bytes <= 64 KB, VPN_E_TOOBIG beyond).  Entries that point outside the source are clamped on the device.
+ *   flags: VPN_INPUT_JITTER | VPN_INPUT_ROTATE | VPN_INPUT_NORMALIZE (ImageNet mean / std, also on the rotation's zero fill).
+ *   factors [B,3] fp32 (brightness, contrast, saturation), order [B,3] int32 (the operation of each turn: 0 brightness,
+ *     1 contrast, 2 saturation), angles [B] fp32 degrees: the draws, each NULL or given.  A NULL one is drawn from
+ *     Philox4x32-10, key seed + *seed_dev (seed_dev NULL or a DEVICE uint64, as vpn_sample_fwd), counter (slot, 0x80000001,
+ *     sample_base + b): slot 0 gives u0..u3 = (word >> 8) 2^-24, factor_i = min(0.6 + 0.8 u_i, 1.4), angle = 360 u3 (360
+ *     itself: 0); slot 1 gives the order, the (word * 6 >> 32)-th permutation in lexicographic order with Lemire's rejection.
+ *   workspace: vpn_input_ws(B) bytes, 8-byte aligned (per image the L sum of the contrast mean and the fixed draws).
+ *   All sides <= 8192, B <= 65535, B H W and B Hs Ws < 2^29: VPN_E_TOOBIG beyond, before any HIP call. */
+#define VPN_INPUT_JITTER 1
+#define VPN_INPUT_ROTATE 2
+#define VPN_INPUT_NORMALIZE 4
+size_t vpn_input_ws(int B);
+int vpn_prepare_images(const uint8_t* rgba, const int32_t* tables, int ksh, int ksv, int max_rows, const float* factors,
+                       const int32_t* order, const float* angles, uint64_t seed, const uint64_t* seed_dev,
+                       uint64_t sample_base, int B, int Hs, int Ws, int H, int W, int flags, void* workspace,
+                       size_t workspace_bytes, uint8_t* inter, float* rgb, float* silhouette, float* angles_out,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

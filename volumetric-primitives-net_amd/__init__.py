@@ -15,6 +15,6 @@ from .modules import (Sampling, ChamferDistanceLoss, EarthMoverDistanceLoss, Sil
                       obj_to_view_points, rotate_points_forward_x_axis, pack_head_outputs, split_primitives, Meshing, TriangleMesh, load_obj, merge_meshes,
                       cut_mix_data, cut_mix_batch_points, adjust_point_num, mixup_points, point_mixup_data,
                       points_to_meshes_and_colors, points_to_mesh_batch, meshes_to_imgs, generate_point_mixup_data, acd, augment,
-                      acd_mix_meshes, acd_mix_data, EvaluationMeter,
+                      acd_mix_meshes, acd_mix_data, EvaluationMeter, prepare_images,
                       Visualizer)
 from . import modules

@@ -100,6 +100,8 @@ SIGNATURES = {
     'vpn_support_hulls': (_i, [_c_f, _c_f, _c_f, _c_f, _i, _i, _i, _i, _c_f, _c_f, _c_f]),
     'vpn_hull_augment': (_i, [_c_f] * 8 + [_i] * 4 + [_c_f, _c_f, _c_f]),
     'vpn_union_surface': (_i, [_c_f] * 5 + [_i] * 5 + [_f] + [_c_f] * 6),
+    'vpn_input_ws': (_sz, [_i]),
+    'vpn_prepare_images': (_i, [_c_f, _c_f, _i, _i, _i, _c_f, _c_f, _c_f, _u64, _c_f, _u64] + [_i] * 6 + [_c_f, _sz] + [_c_f] * 5),
 }
 
 _lib = None

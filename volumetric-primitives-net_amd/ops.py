@@ -5,6 +5,7 @@ emd_module.py:29-70): forward allocates the outputs, calls native code, saves wh
 backward needs; backward returns one gradient per tensor input and None for the rest.
 Unlike it, a non-zero return code raises."""
 import ctypes
+import math
 import os
 import weakref
 
@@ -1690,3 +1691,107 @@ def phong_mesh(verts, faces, uv, texture, cams, H, W, *, light, material, shinin
     _lib.call('vpn_phong_mesh', verts, faces.contiguous(), uv, texture, cams, light, material, shininess, S, P, faces.size(0), V,
               texture.size(2), texture.size(3), H, W, ws, out, _lib.stream())
     return out
+
+
+# ---- the image input stage (csrc/input.hip): dataset.py:15-19,115-139 of the reference -- Resize,
+# ColorJitter, ToTensor, the rotation, the rgb / silhouette split, Normalize -- bit-exact to PIL.  Data, no backward.
+
+INPUT_JITTER, INPUT_ROTATE, INPUT_NORMALIZE = 1, 2, 4
+INPUT_TILE_ROWS = 8                       # IN_TH of csrc/input.hip
+_INPUT_TABLES = {}
+
+
+def input_filter_table(in_size, out_size):
+    """PIL's coefficients of Image.resize(BILINEAR) along one axis, in float64 as precompute_coeffs builds them and in
+    22-bit fixed point as normalize_coeffs_8bpc rounds them: (bounds [out,2] int32 = first tap, tap count; coeffs
+    [out,ksize] int32).  The triangle filter's support is max(in / out, 1) source pixels either side."""
+    in_size, out_size = int(in_size), int(out_size)
+    scale = float(in_size) / out_size
+    fscale = max(scale, 1.0)
+    support, ss = 1.0 * fscale, 1.0 / fscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    bounds = torch.zeros((out_size, 2), dtype=torch.int32)
+    coeffs = torch.zeros((out_size, ksize), dtype=torch.int32)
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        n = min(int(center + support + 0.5), in_size) - xmin
+        w = [max(0.0, 1.0 - abs((x + xmin - center + 0.5) * ss)) for x in range(n)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        bounds[xx, 0], bounds[xx, 1] = xmin, n
+        for x in range(n):
+            coeffs[xx, x] = int(0.5 + (w[x] / ww if ww != 0.0 else w[x]) * (1 << 22))
+    return bounds, coeffs
+
+
+def input_tables(Hs, Ws, H, W, device):
+    """(tables, ksh, ksv, max_rows) of vpn_prepare_images for one (source size, output size): the horizontal and the vertical
+    filter table as one int32 device tensor hb | hk | vb | vk, and the most source rows 8 consecutive output rows need.
+    Built once per (Hs, Ws, H, W, device) and uploaded through pinned memory without blocking."""
+    device = torch.device(device)
+    if device.type == 'cuda' and device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    key = (int(Hs), int(Ws), int(H), int(W), str(device))
+    hit = _INPUT_TABLES.get(key)
+    if hit is None:
+        if len(_INPUT_TABLES) > 64:
+            _INPUT_TABLES.clear()
+        hb, hk = input_filter_table(Ws, W)
+        vb, vk = input_filter_table(Hs, H)
+        ends = vb[:, 0] + vb[:, 1]
+        max_rows = max(int(ends[min(y + INPUT_TILE_ROWS, H) - 1]) - int(vb[y, 0]) for y in range(0, H, INPUT_TILE_ROWS))
+        host = torch.cat([hb.reshape(-1), hk.reshape(-1), vb.reshape(-1), vk.reshape(-1)]).contiguous()
+        t = host.pin_memory().to(device, non_blocking=True) if device.type == 'cuda' else host
+        hit = (t, hk.size(1), vk.size(1), max_rows)
+        _INPUT_TABLES[key] = hit
+    return hit
+
+
+@torch.no_grad()
+def prepare_images(rgba_u8, H, W, *, jitter=True, rotate=False, normalize=False, factors=None, order=None, angles=None,
+                   seed=0, seed_dev=None, sample_base=0, return_intermediate=False):
+    """vpn_prepare_images: rgba_u8 [B,Hs,Ws,4] uint8 on the device -> (rgb [B,3,H,W], silhouette [B,1,H,W], angles [B]) fp32;
+    return_intermediate appends the resized 8-bit image [B,H,W,4].  factors [B,3] fp32, order [B,3] int32, angles [B] fp32
+    (degrees): the draws, host values or device tensors; one that is None is drawn in the kernel from (seed + *seed_dev,
+    sample_base + b).  Three launches on the current stream, no host synchronisation; everything is validated (ValueError)
+    before the launch."""
+    if not (isinstance(rgba_u8, torch.Tensor) and rgba_u8.dtype == torch.uint8 and rgba_u8.dim() == 4 and rgba_u8.size(3) == 4
+            and rgba_u8.numel() > 0):
+        raise ValueError('rgba_u8 must be a uint8 tensor [B,Hs,Ws,4] (np.asarray(Image.open(p)) per image)')
+    if not rgba_u8.is_cuda:
+        raise RuntimeError('vpn_amd operators run on the GPU only (got a %s tensor); there is no CPU path' % rgba_u8.device.type)
+    rgba_u8 = rgba_u8.contiguous()
+    B, Hs, Ws, _ = rgba_u8.shape
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0:
+        raise ValueError('output size must be positive, got %d x %d' % (H, W))
+    dev = rgba_u8.device
+    if not jitter and (factors is not None or order is not None):
+        raise ValueError('factors / order are the draws of the colour jitter: give them with jitter=True')
+    if not rotate and angles is not None:
+        raise ValueError('angles are the draws of the rotation: give them with rotate=True')
+    if factors is not None:
+        factors = _draw_tensor('factors', factors, (B, 3), torch.float32, dev)
+    if order is not None:
+        if not (isinstance(order, torch.Tensor) and order.is_cuda):          # host values are checked here, device ones in the kernel
+            host = torch.as_tensor(order).reshape(-1, 3)
+            if any(sorted(int(v) for v in row) != [0, 1, 2] for row in host):
+                raise ValueError('every row of order must be a permutation of 0 (brightness), 1 (contrast), 2 (saturation)')
+        order = _draw_tensor('order', order, (B, 3), torch.int32, dev)
+    if angles is not None:
+        angles = _draw_tensor('angles', angles, (B,), torch.float32, dev)
+    seed_host, seed_ptr = int(seed) & 0xFFFFFFFFFFFFFFFF, None
+    if seed_dev is not None:
+        _, seed_ptr = _seed_args(seed_dev)
+    tables, ksh, ksv, max_rows = input_tables(Hs, Ws, H, W, dev)
+    flags = (INPUT_JITTER if jitter else 0) | (INPUT_ROTATE if rotate else 0) | (INPUT_NORMALIZE if normalize else 0)
+    ws = _workspace('vpn_input_ws', B, dev=dev, dtype=torch.int64)
+    inter = torch.empty((B, H, W, 4), dtype=torch.uint8, device=dev)
+    rgb = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+    sil = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+    out_angles = torch.empty((B,), dtype=torch.float32, device=dev)
+    _lib.call('vpn_prepare_images', rgba_u8, tables, ksh, ksv, max_rows, factors, order, angles, seed_host, seed_ptr,
+              int(sample_base), B, Hs, Ws, H, W, flags, ws, ws.numel() * 8, inter, rgb, sil, out_angles, _lib.stream())
+    return (rgb, sil, out_angles, inter) if return_intermediate else (rgb, sil, out_angles)
