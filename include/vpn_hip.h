@@ -70,6 +70,10 @@ extern "C" {
 #define VPN_UNION_MAX_CAND 16384
 /* largest K vpn_vis_primitives takes: the records of one (sample, view) live in one workgroup's LDS (116 bytes each) */
 #define VPN_VIS_MAX_PRIMS 512
+/* faces per chunk of a ragged mesh batch (vpn_ragged_sample; the host's chunk table is cut with the same constant): one
+ * 256-lane workgroup scans a chunk, four consecutive faces a lane; most point sets per mesh */
+#define VPN_RAGGED_CHUNK 1024
+#define VPN_RAGGED_MAX_SETS 16
 
 int vpn_abi_version(void);
 /* static description of a code returned by any entry point below */
@@ -731,6 +735,35 @@ int vpn_prepare_images(const uint8_t* rgba, const int32_t* tables, int ksh, int 
                        uint64_t sample_base, int B, int Hs, int Ws, int H, int W, int flags, void* workspace,
                        size_t workspace_bytes, uint8_t* inter, float* rgb, float* silhouette, float* angles_out,
                        void* stream);
+
+/* ---- the ground-truth stage (csrc/gtpoints.hip; modules/dataset/dataset.py:161-165 of the reference, called twice per item
+ * at dataset.py:42-43, and genre.py:66-74): n area-weighted uniform surface points, T sets of them, on each
+ * of S meshes of DIFFERENT sizes, all sets of a mesh from one cumulative-area table.  kaolin's TriangleMesh.sample is
+ * absent: the result is this repository's specification (restated by tests/gtpoints_ref.py), parity
+ * unpinned.  Forward only (ground truth is data); three plain launches on `stream` whatever S is; no atomics; nothing is
+ * allocated; no host synchronisation.  Added without a change of VPN_ABI_VERSION.
+ *   verts [sumP,3] fp32 and faces [sumF,3] int32: the meshes packed one after the other, vertex indices MESH-LOCAL (clamped
+ *     to [0, P_s - 1] on the device); vert_offset / face_offset [S+1] int32: prefix sums of the vertex / face counts;
+ *     chunks [C,3] int32 = (mesh, first face in the packed list, face count <= VPN_RAGGED_CHUNK), in face order, none
+ *     straddling two meshes; chunk_offset [S+1] int32: the chunks of mesh s are [chunk_offset[s], chunk_offset[s+1]).
+ *     Every offset is clamped into its array on the device.
+ *   table: area_f = 0.5f * sqrtf(nx nx + ny ny + nz nz), n = (b - a) x (c - a), fp32, each operation rounded by itself;
+ *     cum_f = the inclusive fp64 prefix sum of a mesh's areas in face order, rounded to fp32 where it is compared.
+ *   draws: u [S,T,n,3] explicit uniforms, or NULL = Philox4x32-10, key seed + *seed_dev (seed_dev NULL or a DEVICE uint64),
+ *     counter (point, 0xFFFFFFFF - set, mesh_base + s): set 0 draws what vpn_mesh_sample_fwd draws for that mesh index.
+ *   face = the first whose (float)cum_f exceeds u0 * (float)cum_last, else the last; r = sqrtf(u1), bary = (1 - r,
+ *     r (1 - u2), r u2), point = w0 a + w1 b + w2 c per component, left to right; xforms [S,T,3,4] (NULL: none): the point
+ *     becomes row r: m[r][0] x + m[r][1] y + m[r][2] z + m[r][3], each product and sum rounded by itself, left to right,
+ *     in the sets t whose bit of xform_mask is set (the other sets keep the point as it is, bit for bit).
+ *   outputs: points [S,T,n,3]; face_idx [S,T,n] int32 (mesh-local) and bary [S,T,n,3], each may be NULL.
+ *   workspace: vpn_ragged_sample_workspace(sumF, C, S) bytes, 16-byte aligned (the in-chunk prefix sums, the chunk bases,
+ *     the mesh totals).
+ *   T <= VPN_RAGGED_MAX_SETS, S T <= 65535, sumP and sumF <= INT32_MAX / 3: VPN_E_TOOBIG beyond, before any HIP call. */
+size_t vpn_ragged_sample_workspace(int sumF, int C, int S);
+int vpn_ragged_sample(const float* verts, const int32_t* faces, const int32_t* vert_offset, const int32_t* face_offset,
+                      const int32_t* chunk_offset, const int32_t* chunks, const float* xforms, unsigned xform_mask, const float* u,
+                      uint64_t seed, const uint64_t* seed_dev, uint64_t mesh_base, int S, int T, int n, int sumP, int sumF, int C,
+                      void* workspace, size_t workspace_bytes, float* points, int32_t* face_idx, float* bary, void* stream);
 
 #ifdef __cplusplus
 }

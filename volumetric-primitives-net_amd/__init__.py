@@ -16,5 +16,6 @@ from .modules import (Sampling, ChamferDistanceLoss, EarthMoverDistanceLoss, Sil
                       cut_mix_data, cut_mix_batch_points, adjust_point_num, mixup_points, point_mixup_data,
                       points_to_meshes_and_colors, points_to_mesh_batch, meshes_to_imgs, generate_point_mixup_data, acd, augment,
                       acd_mix_meshes, acd_mix_data, EvaluationMeter, prepare_images,
+                      MeshBatch, sample_gt_points, gt_points, view_center_xforms, genre_xforms,
                       Visualizer)
 from . import modules

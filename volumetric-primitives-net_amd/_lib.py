@@ -102,6 +102,8 @@ SIGNATURES = {
     'vpn_union_surface': (_i, [_c_f] * 5 + [_i] * 5 + [_f] + [_c_f] * 6),
     'vpn_input_ws': (_sz, [_i]),
     'vpn_prepare_images': (_i, [_c_f, _c_f, _i, _i, _i, _c_f, _c_f, _c_f, _u64, _c_f, _u64] + [_i] * 6 + [_c_f, _sz] + [_c_f] * 5),
+    'vpn_ragged_sample_workspace': (_sz, [_i, _i, _i]),
+    'vpn_ragged_sample': (_i, [_c_f] * 7 + [ctypes.c_uint, _c_f, _u64, _c_f, _u64] + [_i] * 6 + [_c_f, _sz] + [_c_f] * 4),
 }
 
 _lib = None

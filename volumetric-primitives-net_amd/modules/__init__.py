@@ -7,7 +7,8 @@ from .transform import (transform_points, rotate_points, translate_points, view_
                         obj_to_view_points, rotate_points_forward_x_axis)
 from .network import pack_head_outputs, split_primitives, GCNModel, GCNConv
 from .meshing import Meshing, TriangleMesh, load_obj, merge_meshes
-from .dataset import parse_split_csv, parse_rendering_metadata, split_rgba, prepare_images, resized_size
+from .dataset import (parse_split_csv, parse_rendering_metadata, split_rgba, prepare_images, resized_size, MeshBatch,
+                      sample_gt_points, gt_points, view_center_xforms, genre_xforms)
 from . import augmentation
 from .augmentation import (cut_mix_data, cut_mix_batch_points, adjust_point_num, mixup_points, point_mixup_data,
                            points_to_meshes_and_colors, points_to_mesh_batch, meshes_to_imgs, generate_point_mixup_data,

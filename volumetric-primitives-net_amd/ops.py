@@ -1795,3 +1795,59 @@ def prepare_images(rgba_u8, H, W, *, jitter=True, rotate=False, normalize=False,
     _lib.call('vpn_prepare_images', rgba_u8, tables, ksh, ksv, max_rows, factors, order, angles, seed_host, seed_ptr,
               int(sample_base), B, Hs, Ws, H, W, flags, ws, ws.numel() * 8, inter, rgb, sil, out_angles, _lib.stream())
     return (rgb, sil, out_angles, inter) if return_intermediate else (rgb, sil, out_angles)
+
+
+# ---- the ground-truth stage (csrc/gtpoints.hip): dataset.py:161-165 for a ragged batch of meshes.  Data: no
+# autograd node.
+
+RAGGED_MAX_SETS = 16         # VPN_RAGGED_MAX_SETS
+RAGGED_LAUNCHES = 3          # chunk scan, chunk bases, sampling: whatever the number of meshes
+
+
+@torch.no_grad()
+def ragged_sample(verts, faces, vert_offset, face_offset, chunk_offset, chunks, n, *, sets=1, xforms=None, xform_mask=None, u=None,
+                  seed=0, seed_dev=None, mesh_base=0, return_faces=False):
+    """vpn_ragged_sample: the packed meshes of a MeshBatch (verts [sumP,3] fp32, faces [sumF,3] int32 mesh-local, vert_offset /
+    face_offset / chunk_offset [S+1] int32, chunks [C,3] int32, all on the device) -> points [S,sets,n,3]; return_faces adds
+    face [S,sets,n] int32 (mesh-local) and bary [S,sets,n,3].  xforms [S,sets,3,4]: the affine map of every (mesh, set), applied
+    in the sets whose bit of xform_mask is set (default: all); u [S,sets,n,3]: explicit uniforms instead of the Philox draws of
+    (seed + *seed_dev, mesh_base + s, set).  RAGGED_LAUNCHES launches on the current stream, no host synchronisation;
+    everything is validated (ValueError) before the launch."""
+    for name, t, dt in (('verts', verts, torch.float32), ('faces', faces, torch.int32), ('vert_offset', vert_offset, torch.int32),
+                        ('face_offset', face_offset, torch.int32), ('chunk_offset', chunk_offset, torch.int32),
+                        ('chunks', chunks, torch.int32)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == dt):
+            raise ValueError('%s must be a %s tensor' % (name, dt))
+        if not t.is_cuda:
+            raise RuntimeError('vpn_amd operators run on the GPU only (got a %s tensor); there is no CPU path' % t.device.type)
+        if not t.is_contiguous():
+            raise ValueError('%s must be contiguous' % name)
+    _augment_is_data(verts)
+    S, T, n = vert_offset.numel() - 1, int(sets), int(n)
+    sumP, sumF, C = verts.size(0), faces.size(0), chunks.size(0)
+    if S < 1 or face_offset.numel() != S + 1 or chunk_offset.numel() != S + 1:
+        raise ValueError('the three offset tables must have S + 1 entries for S >= 1 meshes')
+    if verts.dim() != 2 or verts.size(1) != 3 or faces.dim() != 2 or faces.size(1) != 3 or chunks.dim() != 2 or chunks.size(1) != 3:
+        raise ValueError('verts [sumP,3], faces [sumF,3] and chunks [C,3] expected')
+    if sumP < 1 or sumF < 1 or C < 1 or C > sumF:
+        raise ValueError('an empty batch: %d vertices, %d faces, %d chunks' % (sumP, sumF, C))
+    if not 1 <= T <= RAGGED_MAX_SETS:
+        raise ValueError('sets must be 1 .. %d, got %d' % (RAGGED_MAX_SETS, T))
+    if n < 1:
+        raise ValueError('n must be positive, got %d' % n)
+    dev = verts.device
+    if xforms is not None:
+        xforms = _draw_tensor('xforms', xforms, (S, T, 3, 4), torch.float32, dev)
+    mask = (1 << T) - 1 if xform_mask is None else int(xform_mask) & ((1 << T) - 1)
+    if u is not None:
+        u = _draw_tensor('u', u, (S, T, n, 3), torch.float32, dev)
+    seed_host, seed_ptr = int(seed) & 0xFFFFFFFFFFFFFFFF, None
+    if seed_dev is not None:
+        _, seed_ptr = _seed_args(seed_dev)
+    ws = _workspace('vpn_ragged_sample_workspace', sumF, C, S, dev=dev, dtype=torch.float64, floor=1)
+    points = torch.empty((S, T, n, 3), dtype=torch.float32, device=dev)
+    fidx = torch.empty((S, T, n), dtype=torch.int32, device=dev) if return_faces else None
+    bary = torch.empty((S, T, n, 3), dtype=torch.float32, device=dev) if return_faces else None
+    _lib.call('vpn_ragged_sample', verts, faces, vert_offset, face_offset, chunk_offset, chunks, xforms, mask, u, seed_host, seed_ptr,
+              int(mesh_base), S, T, n, sumP, sumF, C, ws, ws.numel() * 8, points, fidx, bary, _lib.stream())
+    return (points, fidx, bary) if return_faces else points
