@@ -1,8 +1,9 @@
 """The refinement step of the reference's train_gcn.py (:119-138) on the drop-in surface, with synthetic inputs.
 
-    python examples/train_gcn_step.py [--steps 5] [--batch 8]
+    python examples/train_gcn_step.py [--steps 5] [--batch 8] [--net standin|vpnet_oneres] [--vpn CKPT]
 
-VPNetOneRes (a ResNet-18 with MLP heads) is out of scope and torchvision is absent, so a stand-in
+--net vpnet_oneres runs the reference's frozen VPNetOneRes (modules/network.py; --vpn CKPT loads a reference checkpoint
+into it as train_gcn.py:100-102 does, otherwise it is randomly initialised).  By default a stand-in
 produces what train_gcn.py:126 takes from it: 16 sphere primitives (volumes, rotates, translates) and the ResNet-18
 feature maps of a 128 x 128 image (64@32², 128@16², 256@8², 512@4²) plus a 512-wide global feature.  The rest is the
 reference's step:
@@ -67,10 +68,18 @@ def main(argv=None):
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--lr', type=float, default=1e-5)
+    ap.add_argument('--net', default='standin', choices=('standin', 'vpnet_oneres'))
+    ap.add_argument('--vpn', default=None, help='a VPNetOneRes state_dict saved by the reference (implies --net vpnet_oneres)')
     args = ap.parse_args(argv)
     dev = torch.device('cuda')
     torch.manual_seed(1234)
-    vpn = StandInVPN().to(dev).eval()
+    if args.vpn or args.net == 'vpnet_oneres':
+        vpn = vpn_amd.VPNetOneRes(vp_num=VP_NUM)
+        if args.vpn:
+            vpn.load_state_dict(torch.load(args.vpn, map_location='cpu'))
+        vpn = vpn.to(dev).eval()
+    else:
+        vpn = StandInVPN().to(dev).eval()
     gcn = GCNModel().to(dev)
     optimizer = torch.optim.Adam(params=gcn.parameters(), lr=args.lr, betas=(0.9, 0.99), weight_decay=1e-6)
     cd_loss_func = vpn_amd.ChamferDistanceLoss()

@@ -1,9 +1,10 @@
 """A training step of the reference's train_sphere.py (:104-134) on the drop-in surface, with a stand-in network.
 
-    python examples/train_sphere_step.py [--steps 20] [--obj path/to/386.obj]
+    python examples/train_sphere_step.py [--steps 20] [--obj path/to/386.obj] [--net standin|sdnet]
 
-train_sphere.py deforms a template sphere mesh instead of predicting primitives: SDNet (a ResNet-18, out of scope:
-DESIGN.md 7) outputs one offset per vertex, the 386-vertex sphere of `386.obj` is deformed IN PLACE, sampled, compared
+train_sphere.py deforms a template sphere mesh instead of predicting primitives: SDNet (--net sdnet: modules/network.py,
+a ResNet-18 and the deform stack of csrc/fcstack.hip, fed the ground-truth silhouette as its image; by default a small
+stand-in on random features) outputs one offset per vertex, the 386-vertex sphere of `386.obj` is deformed IN PLACE, sampled, compared
 with the ground-truth cloud and rendered against the ground-truth silhouette.  The lines below are the reference's,
 on vpn_amd's mirror of kaolin's TriangleMesh and of its loss modules:
 
@@ -53,7 +54,10 @@ def load_sphere_meshes(B, dev, obj=None, radius=0.25):
 def training_losses(net, feats, gt_points, gt_sil, dists, elevs, azims, sample_num, l_sil, obj=None):
     B = feats.shape[0]
     sphere_meshes = load_sphere_meshes(B, feats.device, obj)
-    vertices_offset = net(feats)                                       # train_sphere.py:111
+    if isinstance(net, vpn_amd.SDNet):
+        vertices_offset = 0.1 * net(gt_sil.expand(-1, 3, -1, -1).contiguous())
+    else:
+        vertices_offset = net(feats)                                   # train_sphere.py:111
     for b in range(B):
         sphere_meshes[b].vertices += vertices_offset[b]                # :66, in place
     predict_points = torch.cat([sphere_meshes[b].sample(sample_num)[0][None] for b in range(B)], dim=0)   # :75-79
@@ -83,12 +87,13 @@ if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--obj', default=None)
+    ap.add_argument('--net', default='standin', choices=('standin', 'sdnet'))
     args = ap.parse_args()
     dev = torch.device('cuda')
     torch.manual_seed(0)
     batch = make_batch(4, 2048, 64, dev)                              # BASELINE config C1: batch 4, 64 x 64
     P = vpn_amd.load_obj(args.obj)[0].shape[0] if args.obj else 288
-    net = Offsets(64, P).to(dev)
+    net = (vpn_amd.SDNet(vertex_num=P) if args.net == 'sdnet' else Offsets(64, P)).to(dev)
     opt = torch.optim.Adam(net.parameters(), lr=2e-3)
     for it in range(args.steps):
         opt.zero_grad()

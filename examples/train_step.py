@@ -1,9 +1,11 @@
 """A training step of the reference (train.py:221-268) on the drop-in surface, with a stand-in network.
 
-    python examples/train_step.py [--steps 20]
+    python examples/train_step.py [--steps 20] [--net standin|vpnet_oneres|vpnet_twores]
 
-The reference's ResNet-18 trunk is out of scope: a two-layer MLP on a random feature vector
-produces the three head outputs (volumes [B,3K], rotates [B,4K], translates [B,3K]).  Everything after that is the
+By default a two-layer MLP on a random feature vector produces the three head outputs (volumes [B,3K], rotates [B,4K],
+translates [B,3K]); --net vpnet_oneres / vpnet_twores trains the reference's network instead (modules/network.py: a
+ResNet-18 trunk, randomly initialised here, and the FC heads of csrc/fcstack.hip) on the ground-truth
+silhouette repeated over three channels as the image.  Everything after that is the
 code path of the reference, through vpn_amd's mirror of its modules:
 
     head post-processing     vpnet_one_resnet.py:34-41   pack_head_outputs
@@ -38,10 +40,18 @@ class Heads(nn.Module):
         return self.volume_fc(h), self.rotate_fc(h), self.translate_fc(h)
 
 
+def head_params(net, feats, gt_sil):
+    """[B,K,10] from the stand-in (features) or from the reference's network (images)."""
+    if isinstance(net, Heads):
+        return vpn_amd.pack_head_outputs(*net(feats))
+    out = net.forward_packed(gt_sil.expand(-1, 3, -1, -1).contiguous())
+    return out[0] if isinstance(out, tuple) else out
+
+
 def training_losses(net, feats, gt_points, gt_sil, dists, elevs, azims, angles, kinds, sample_num, weights, seed):
     """total loss of train.py:243-262 (w = (L_VIEW_CD, L_CAN_CD, L_SIL, L_VP_DIV, L_EMD)) and its parts."""
     K = len(kinds)
-    params = vpn_amd.pack_head_outputs(*net(feats))                               # [B,K,10]
+    params = head_params(net, feats, gt_sil)                                      # [B,K,10]
     volumes, rotates, translates = vpn_amd.split_primitives(params)
     pred = vpn_amd.Sampling.sample_primitives(params, kinds, sample_num, seed=seed)   # [B, K*n, 3], view-centred
     cd = vpn_amd.ChamferDistanceLoss()
@@ -60,7 +70,7 @@ def training_losses(net, feats, gt_points, gt_sil, dists, elevs, azims, angles, 
 def training_losses_fused(net, feats, gt_points, gt_sil, dists, elevs, azims, angles, kinds, sample_num, weights, seed):
     """The same loss as ONE autograd node (vpn_amd.TrainStepLossFunction: 9 launches forward with the auction on a second
     stream, 1 backward).  Needs K * sample_num >= 512 sampled points against as many GT points."""
-    params = vpn_amd.pack_head_outputs(*net(feats))                               # [B,K,10]
+    params = head_params(net, feats, gt_sil)                                      # [B,K,10]
     size = gt_sil.shape[-1]
     gt_canon = vpn_amd.view_to_obj_points(gt_points, dists, elevs, azims, angles)
     view_cd, obj_cd, sil, div, emd, total = vpn_amd.TrainStepLossFunction.apply(
@@ -128,6 +138,7 @@ def main():
     ap.add_argument('--prims', type=int, default=16)         # config.py:34
     ap.add_argument('--sample-num', type=int, default=128)   # config.py:8
     ap.add_argument('--size', type=int, default=128)         # config.py:49
+    ap.add_argument('--net', default='standin', choices=('standin', 'vpnet_oneres', 'vpnet_twores'))
     ap.add_argument('--fused', action='store_true', help='the whole loss as one autograd node (TrainStepLossFunction)')
     ap.add_argument('--augment', default='', help='comma-separated subset of rotate,cutmix,mixup,pointmixup,acdmix (config.py AUGMENT_3D; default: none)')
     args = ap.parse_args()
@@ -137,7 +148,8 @@ def main():
     dev = torch.device('cuda')
     torch.manual_seed(1234)
     batch = make_batch(args.batch, args.prims, args.sample_num, args.size, dev)
-    net = Heads(64, args.prims).to(dev)
+    net = {'standin': lambda: Heads(64, args.prims), 'vpnet_oneres': lambda: vpn_amd.VPNetOneRes(vp_num=args.prims),
+           'vpnet_twores': lambda: vpn_amd.VPNetTwoRes(vp_num=args.prims)}[args.net]().to(dev)
     opt = torch.optim.Adam(net.parameters(), lr=1e-3)
     weights = (1.0, 1.0, 1.0, 0.1, 1.0)
     for it in range(args.steps):

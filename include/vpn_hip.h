@@ -765,6 +765,66 @@ int vpn_ragged_sample(const float* verts, const int32_t* faces, const int32_t* v
                       uint64_t seed, const uint64_t* seed_dev, uint64_t mesh_base, int S, int T, int n, int sumP, int sumF, int C,
                       void* workspace, size_t workspace_bytes, float* points, int32_t* face_idx, float* bary, void* stream);
 
+/* ---- the network stage: the FC heads (csrc/fcstack.hip; modules/network/vpnet_one_resnet.py:31-41, :67-107,
+ * vpnet_two_resnet.py:34-44, :70-110 and sdnet.py:19, :24-25, :41-50 of the reference): G groups of L
+ * nn.Linear layers (the reference: 3 heads or SDNet's deform, 5 layers, 512 -> 1024 x 4 -> 3K | 4K | 3K) with nothing
+ * between them but nn.Dropout, forward and backward.  Group g, layer l: y[b,o] = bias[o] + sum_i x[b,i] W[o,i], W in
+ * nn.Linear's own [out,in] row-major layout; fp32 in, fp32 accumulate, summation order unspecified but fixed: outputs and
+ * gradients are bit-equal from run to run (no float atomics).  One launch per layer forward, at most two per layer
+ * backward, each covering all groups; plain launches on `stream`, nothing is allocated, no host synchronisation.
+ * Added without a change of VPN_ABI_VERSION.
+ *   VpnFcStack, passed BY VALUE (no device table): slot g * L + l belongs to layer l of group g, slot g alone to group g.
+ *     x[g] [B,in0[g]]: the group's input (groups may share one); w / bias: the layer's parameters [out,in] / [out], where
+ *     in = in0[g] for l = 0 and out[g * L + l - 1] otherwise; keep: uint8 [B,out] keep masks of layers 0..L-2 (read under
+ *     VPN_FC_DROPOUT_MASK only); act [B,out]: WRITTEN by the forward, the layer's output after dropout (what the next
+ *     layer reads; the backward reads it again), for l = L-1 the raw output before the epilogue.
+ *   dropout (training mode; the caller passes VPN_FC_DROPOUT_OFF in eval mode): after layers 0..L-2, y = keep ? y / (1 - p)
+ *     : 0.  VPN_FC_DROPOUT_PHILOX: keep = u >= p, u = (word0 >> 8) 2^-24 of Philox4x32-10 with key seed + *seed_dev
+ *     (seed_dev NULL or a DEVICE uint64, as vpn_sample_fwd: a step counter, so that replays of a captured graph draw anew)
+ *     and counter (o, b, l, g); never stored, the backward draws it again from the same arguments, so *seed_dev must
+ *     not change between a forward and its backward.
+ *   epilogue of the last layer: VPN_FC_NONE (the outputs are act of layer L-1); VPN_FC_TANH (G = 1): final [B,out] =
+ *     tanh(raw); VPN_FC_VP_PACK (G = 3, outs 3K | 4K | 3K): final = the packed [B,K,10] rows that vpn_head_pack_fwd
+ *     makes of the three raw outputs, same rule and same arguments.
+ *   backward, VpnFcGrad: gout = dL/d(outputs): gout[g] [B,out] per group under VPN_FC_NONE, gout[0] = dL/dfinal otherwise;
+ *     dw / db per slot, NULL = skipped (a frozen group costs nothing); dx[g] [B,in0[g]] per group, NULL = skipped (groups
+ *     that share an input get separate gradients, the caller adds them).  workspace: vpn_fc_stack_workspace(G, B, the
+ *     largest in / out of any layer) bytes, 16-byte aligned.
+ *   L <= VPN_FC_MAX_LAYERS, G L <= VPN_FC_MAX_SLOTS, B (largest width) <= INT32_MAX / 4: VPN_E_TOOBIG beyond; null
+ *   pointers and non-positive sizes: VPN_E_BADARG; all before any HIP call. */
+#define VPN_FC_MAX_LAYERS 8
+#define VPN_FC_MAX_SLOTS 24
+#define VPN_FC_SLICE 32                /* weight rows per partial sum of the backward's dX */
+#define VPN_FC_NONE 0
+#define VPN_FC_TANH 1
+#define VPN_FC_VP_PACK 2
+#define VPN_FC_DROPOUT_OFF 0
+#define VPN_FC_DROPOUT_MASK 1
+#define VPN_FC_DROPOUT_PHILOX 2
+typedef struct VpnFcStack {
+    int32_t G, L, B, reserved;
+    int32_t in0[VPN_FC_MAX_SLOTS];
+    int32_t out[VPN_FC_MAX_SLOTS];
+    const float* x[VPN_FC_MAX_SLOTS];
+    const float* w[VPN_FC_MAX_SLOTS];
+    const float* bias[VPN_FC_MAX_SLOTS];
+    const uint8_t* keep[VPN_FC_MAX_SLOTS];
+    float* act[VPN_FC_MAX_SLOTS];
+} VpnFcStack;
+typedef struct VpnFcGrad {
+    const float* gout[VPN_FC_MAX_SLOTS];
+    float* dw[VPN_FC_MAX_SLOTS];
+    float* db[VPN_FC_MAX_SLOTS];
+    float* dx[VPN_FC_MAX_SLOTS];
+} VpnFcGrad;
+size_t vpn_fc_stack_workspace(int G, int B, int max_width);
+int vpn_fc_stack_fwd(VpnFcStack stack, int dropout, float p, uint64_t seed, const uint64_t* seed_dev, int epilogue, int K,
+                     int is_sigmoid, float clamp_min, float clamp_max, float restrict0, float restrict1, float restrict2, float* final,
+                     void* stream);
+int vpn_fc_stack_bwd(VpnFcStack stack, VpnFcGrad grad, int dropout, float p, uint64_t seed, const uint64_t* seed_dev,
+                     int epilogue, int K, int is_sigmoid, float clamp_min, float clamp_max, float restrict0, float restrict1, float restrict2,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

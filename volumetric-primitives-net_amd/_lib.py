@@ -14,6 +14,26 @@ ABI_VERSION = 9
 _c_f = ctypes.c_void_p      # device pointers travel as void*
 _i, _f, _u64, _sz = ctypes.c_int, ctypes.c_float, ctypes.c_uint64, ctypes.c_size_t
 
+FC_MAX_LAYERS, FC_MAX_SLOTS = 8, 24      # VPN_FC_MAX_LAYERS, VPN_FC_MAX_SLOTS
+FC_NONE, FC_TANH, FC_VP_PACK = 0, 1, 2
+FC_DROPOUT_OFF, FC_DROPOUT_MASK, FC_DROPOUT_PHILOX = 0, 1, 2
+
+
+class FcStack(ctypes.Structure):
+    """VpnFcStack of include/vpn_hip.h, passed by value: slot g * L + l is layer l of group g."""
+    _fields_ = [('G', ctypes.c_int32), ('L', ctypes.c_int32), ('B', ctypes.c_int32), ('reserved', ctypes.c_int32),
+                ('in0', ctypes.c_int32 * FC_MAX_SLOTS), ('out', ctypes.c_int32 * FC_MAX_SLOTS),
+                ('x', ctypes.c_void_p * FC_MAX_SLOTS), ('w', ctypes.c_void_p * FC_MAX_SLOTS),
+                ('bias', ctypes.c_void_p * FC_MAX_SLOTS), ('keep', ctypes.c_void_p * FC_MAX_SLOTS),
+                ('act', ctypes.c_void_p * FC_MAX_SLOTS)]
+
+
+class FcGrad(ctypes.Structure):
+    """VpnFcGrad of include/vpn_hip.h, passed by value."""
+    _fields_ = [('gout', ctypes.c_void_p * FC_MAX_SLOTS), ('dw', ctypes.c_void_p * FC_MAX_SLOTS),
+                ('db', ctypes.c_void_p * FC_MAX_SLOTS), ('dx', ctypes.c_void_p * FC_MAX_SLOTS)]
+
+
 SIGNATURES = {
     'vpn_abi_version': (ctypes.c_int, []),
     'vpn_error_string': (ctypes.c_char_p, [_i]),
@@ -104,6 +124,9 @@ SIGNATURES = {
     'vpn_prepare_images': (_i, [_c_f, _c_f, _i, _i, _i, _c_f, _c_f, _c_f, _u64, _c_f, _u64] + [_i] * 6 + [_c_f, _sz] + [_c_f] * 5),
     'vpn_ragged_sample_workspace': (_sz, [_i, _i, _i]),
     'vpn_ragged_sample': (_i, [_c_f] * 7 + [ctypes.c_uint, _c_f, _u64, _c_f, _u64] + [_i] * 6 + [_c_f, _sz] + [_c_f] * 4),
+    'vpn_fc_stack_workspace': (_sz, [_i, _i, _i]),
+    'vpn_fc_stack_fwd': (_i, [FcStack, _i, _f, _u64, _c_f, _i, _i, _i, _f, _f, _f, _f, _f, _c_f, _c_f]),
+    'vpn_fc_stack_bwd': (_i, [FcStack, FcGrad, _i, _f, _u64, _c_f, _i, _i, _i, _f, _f, _f, _f, _f, _c_f, _sz, _c_f]),
 }
 
 _lib = None

@@ -11,6 +11,7 @@ L_EMD = 1.0
 MANUAL_SEED = 1234          # config.py:20
 VP_CLAMP_MIN = 0.01         # config.py:22
 VP_CLAMP_MAX = 0.8          # config.py:23
+IS_DROPOUT = False          # config.py:24
 IS_SIGMOID = True           # config.py:25
 VOLUME_RESTRICT = [8, 10, 10]   # config.py:26
 SILHOUETTE_LOSS_FUNC = 'L1'  # config.py:27

@@ -9,15 +9,9 @@
 // (v0 v1 v2 q0 q1 q2 q3 t0 t1 t2) that the sampler, the raster and their backward kernels read directly.
 // (restrict_volumes writes in place into views of a split, which current PyTorch refuses under autograd —
 // SURVEY.md Appendix C; the fused op has no such problem.)
-#include "vpn_common.h"
+#include "vpn_head_rule.h"
 
 namespace vpn {
-
-__device__ inline float sigmoidf(float x) {                     // overflow-free on both sides
-    const float e = __expf(-fabsf(x));
-    const float s = 1.0f / (1.0f + e);
-    return x >= 0.0f ? s : e * s;
-}
 
 // one thread per packed element; BACKWARD: out = dL/draw given g = dL/dparams
 template <bool BACKWARD>
@@ -40,15 +34,7 @@ __global__ __launch_bounds__(256) void head_pack_kernel(const float* __restrict_
     else { src = translates; gdst = grad_translates; idx = b * 3 * K + k * 3 + (f - 7); }
     const float x = src[idx];
     float y, dy;
-    if (is_sigmoid) {
-        if (f < 7) { const float s = sigmoidf(x); y = f < 3 ? s + 0.1f : s; dy = s * (1.0f - s); }     // :70-71
-        else { y = tanhf(x); dy = 1.0f - y * y; }                                                        // :72
-    } else {
-        const float lo = f < 3 ? cmin + 1e-8f : -1.0f, hi = f < 3 ? cmax : 1.0f;                          // :74-76
-        y = fminf(fmaxf(x, lo), hi);
-        dy = (x >= lo && x <= hi) ? 1.0f : 0.0f;                 // torch.clamp passes the gradient on the closed interval
-    }
-    if (f < 3) { const float r = f == 0 ? r0 : (f == 1 ? r1 : r2); y = y / r; dy = dy / r; }              // :81-84
+    head_field(HeadRule{is_sigmoid, cmin, cmax, r0, r1, r2}, f, x, y, dy);      // vpn_head_rule.h
     if (BACKWARD) { if (gdst) gdst[idx] = grad_params[e] * dy; }
     else params[e] = y;
 }

@@ -1,11 +1,16 @@
-"""The one piece of modules/network of the reference that sits on the hot path: the post-processing of the three
-head outputs (vpnet_one_resnet.py:34-41, :67-85; identical in vpnet_two_resnet.py and sdnet.py).  The networks
-themselves (ResNet-18 trunk, MLP heads) are out of scope.  GCNModel (gcn.py, the refinement stage of
-train_gcn.py / test_gcn.py) is re-exported from modules/gcn.py, so that `from modules.network import GCNModel` resolves."""
+"""modules/network of the reference: VPNetOneRes, VPNetTwoRes and SDNet (vpnet_one_resnet.py, vpnet_two_resnet.py,
+sdnet.py), with the same attribute and `state_dict` names, so that a reference checkpoint loads with strict=True
+(train_gcn.py:100-102, every test*.py).  The trunk is a ResNet-18 in plain torch.nn (convolutions and batch norm are
+ATen's); the FC heads, the one part of the networks that is nothing but weight traffic, run on csrc/fcstack.hip: their
+nn.Linear modules only HOLD the parameters, the forward hands the tensors to FcStackFunction, which also applies what
+follows the last layer (restrict_range + split + restrict_volumes into packed rows, or SDNet's tanh).  GCNModel (gcn.py,
+the refinement stage of train_gcn.py / test_gcn.py) is re-exported from modules/gcn.py, so that
+`from modules.network import GCNModel` resolves."""
 import torch
+import torch.nn as nn
 
 from .. import config
-from ..ops import HeadPackFunction
+from ..ops import HeadPackFunction, FcStackFunction
 from .gcn import GCNModel, GCNConv  # noqa: F401
 
 
@@ -23,3 +28,234 @@ def split_primitives(params: torch.Tensor):
     K = params.shape[1]
     return ([params[:, k, 0:3] for k in range(K)], [params[:, k, 3:7] for k in range(K)],
             [params[:, k, 7:10] for k in range(K)])
+
+
+# ---- the trunk: torchvision's resnet18 by its parameter and buffer names (torchvision itself is not a dependency)
+
+class BasicBlock(nn.Module):
+    def __init__(self, inplanes, planes, stride=1):
+        super().__init__()
+        self.conv1 = nn.Conv2d(inplanes, planes, 3, stride, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.relu = nn.ReLU(inplace=True)
+        self.conv2 = nn.Conv2d(planes, planes, 3, 1, 1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.downsample = None
+        if stride != 1 or inplanes != planes:
+            self.downsample = nn.Sequential(nn.Conv2d(inplanes, planes, 1, stride, bias=False), nn.BatchNorm2d(planes))
+
+    def forward(self, x):
+        out = self.relu(self.bn1(self.conv1(x)))
+        out = self.bn2(self.conv2(out))
+        return self.relu(out + (x if self.downsample is None else self.downsample(x)))
+
+
+class ResNet18(nn.Module):
+    """ResNet-18 (He et al. 2016) laid out as torchvision.models.resnet18: 122 state_dict entries, 11 689 512
+    parameters, the `fc` 512 -> 1000 that the reference's models never call included.  Weights come from
+    load_state_dict alone: nothing is ever downloaded."""
+
+    def __init__(self, num_classes=1000):
+        super().__init__()
+        self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
+        self.bn1 = nn.BatchNorm2d(64)
+        self.relu = nn.ReLU(inplace=True)
+        self.maxpool = nn.MaxPool2d(3, 2, 1)
+        self.layer1 = nn.Sequential(BasicBlock(64, 64), BasicBlock(64, 64))
+        self.layer2 = nn.Sequential(BasicBlock(64, 128, 2), BasicBlock(128, 128))
+        self.layer3 = nn.Sequential(BasicBlock(128, 256, 2), BasicBlock(256, 256))
+        self.layer4 = nn.Sequential(BasicBlock(256, 512, 2), BasicBlock(512, 512))
+        self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
+        self.fc = nn.Linear(512, num_classes)
+        for m in self.modules():                       # torchvision's initialisation
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
+
+    def forward(self, x):
+        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
+        return self.fc(torch.flatten(self.avgpool(x), 1))
+
+
+def _trunk_maps(model, imgs):
+    """conv1 .. layer4 of a trunk (extract_feature of the three models): the four residual stages' outputs."""
+    out = model.maxpool(model.relu(model.bn1(model.conv1(imgs))))
+    l1 = model.layer1(out)
+    l2 = model.layer2(l1)
+    l3 = model.layer3(l2)
+    return [l1, l2, l3, model.layer4(l3)]
+
+
+# ---- the heads
+
+def make_linear(output_dim, is_dropout=config.IS_DROPOUT, feat=512, hidden=1024):
+    """_make_linear of the reference (vpnet_one_resnet.py:87-107): five nn.Linear, an nn.Dropout() after each of the
+    first four when is_dropout (so the Linear indices are 0,2,4,6,8)."""
+    mods, width = [], feat
+    for l in range(5):
+        mods.append(nn.Linear(width, hidden if l < 4 else output_dim))
+        width = hidden
+        if is_dropout and l < 4:
+            mods.append(nn.Dropout())
+    return nn.Sequential(*mods)
+
+
+class FcHeads(nn.Module):
+    """Owner of one or more FC heads.  The heads are nn.Sequential of nn.Linear (and nn.Dropout) exactly as the
+    reference lays them out, registered under the reference's names, so state_dict keys match; run_heads never calls
+    those modules: it hands their tensors to FcStackFunction (one launch per layer for all heads).  Used directly
+    (`FcHeads({'volume_fc': 48, ...})`) or as the base of the three models."""
+
+    def __init__(self, heads=None, is_dropout=config.IS_DROPOUT, feat=512, hidden=1024, seed=0):
+        super().__init__()
+        self._head_paths = []
+        self._is_dropout = bool(is_dropout)
+        self._fc_seed, self._fc_calls = int(seed), 0
+        for name, out in (heads or {}).items():
+            setattr(self, name, make_linear(out, is_dropout, feat, hidden))
+            self._head_paths.append(name)
+
+    def head_linears(self):
+        """Per head, its nn.Linear modules in order."""
+        return [[m for m in self.get_submodule(p) if isinstance(m, nn.Linear)] for p in self._head_paths]
+
+    def run_heads(self, inputs, epilogue='none', masks=None, seed=None, **rule):
+        """inputs: one tensor (B,feat) per head (the same tensor may be given several times).  Dropout applies in
+        training mode where the heads were built with it: `masks` (per head, per layer 0..L-2, uint8 (B,out)) selects
+        explicit keep masks, otherwise Philox draws them from `seed`: an int (default: the module's seed plus the number
+        of calls so far, so every eager step draws anew), or a CUDA int64 tensor of one element that the kernels read, the
+        form for a captured graph: bump it on the stream between steps (`seed.add_(1)` inside the capture, after the
+        backward) and every replay draws anew.  It must not change between a forward and its backward."""
+        lin = self.head_linears()
+        G, L = len(lin), len(lin[0])
+        assert len(inputs) == G and all(len(h) == L for h in lin)
+        cfg = dict(G=G, L=L, epilogue=epilogue, dropout=None, **rule)
+        extra = []
+        if self._is_dropout and self.training and L > 1:
+            cfg['p'] = next(m.p for m in self.get_submodule(self._head_paths[0]) if isinstance(m, nn.Dropout))
+            if masks is not None:
+                cfg['dropout'] = 'mask'
+                extra = [m for head in masks for m in head]
+            else:
+                cfg['dropout'] = 'philox'
+                if seed is None:
+                    seed = self._fc_seed + self._fc_calls
+                    self._fc_calls += 1
+                cfg['seed'] = seed
+        params = [t for head in lin for m in head for t in (m.weight, m.bias)]
+        return FcStackFunction.apply(cfg, *inputs, *params, *extra)
+
+
+class _VPNet(FcHeads):
+    """What VPNetOneRes and VPNetTwoRes share: the three heads and the range rules.  The constructor arguments stand in
+    for the reference's config constants (config.py:22-26, :36)."""
+
+    def __init__(self, vp_num, is_sigmoid, is_dropout, clamp_min, clamp_max, volume_restrict, hidden, feat, seed):
+        super().__init__(None, is_dropout, feat, hidden, seed)
+        self._vp_num = int(vp_num)
+        self._rule = dict(is_sigmoid=bool(is_sigmoid), clamp_min=float(clamp_min), clamp_max=float(clamp_max),
+                          volume_restrict=tuple(float(r) for r in volume_restrict))
+        self.avgpool = nn.AdaptiveAvgPool2d(output_size=(1, 1))
+        self.volume_fc = make_linear(3 * self._vp_num, is_dropout, feat, hidden)
+        self.rotate_fc = make_linear(4 * self._vp_num, is_dropout, feat, hidden)
+        self.translate_fc = make_linear(3 * self._vp_num, is_dropout, feat, hidden)
+        self._head_paths = ['volume_fc', 'rotate_fc', 'translate_fc']
+
+    @staticmethod
+    def restrict_range(volumes, rotates, translates, is_sigmoid=config.IS_SIGMOID, clamp_min=config.VP_CLAMP_MIN,
+                       clamp_max=config.VP_CLAMP_MAX):
+        """:67-77 on raw head outputs (B,3K), (B,4K), (B,3K), through the head kernel (GPU only).  A staticmethod as in
+        the reference, which reads the config constants; here they are the defaults of the keyword arguments."""
+        p = pack_head_outputs(volumes, rotates, translates, is_sigmoid, clamp_min, clamp_max, (1.0, 1.0, 1.0))
+        B = p.shape[0]
+        return p[:, :, 0:3].reshape(B, -1), p[:, :, 3:7].reshape(B, -1), p[:, :, 7:10].reshape(B, -1)
+
+    @staticmethod
+    def restrict_volumes(volumes, volume_restrict=config.VOLUME_RESTRICT):
+        """:79-85 on a list of (B,3) tensors, out of place (the reference writes into views of a split, which autograd
+        refuses).  The model's own forward does this inside the heads' last launch instead."""
+        r = volumes[0].new_tensor([float(v) for v in volume_restrict])
+        return [v / r for v in volumes]
+
+
+class VPNetOneRes(_VPNet):
+    """vpnet_one_resnet.py: one ResNet-18, three heads.  forward(imgs) -> (volumes, rotates, translates,
+    perceptual_features, features) as the reference; forward_packed(imgs) -> (params (B,K,10), perceptual_features,
+    features), the form the sampler, the raster and the losses of this package read."""
+
+    def __init__(self, vp_num=config.VP_NUM, is_sigmoid=config.IS_SIGMOID, is_dropout=config.IS_DROPOUT,
+                 clamp_min=config.VP_CLAMP_MIN, clamp_max=config.VP_CLAMP_MAX, volume_restrict=config.VOLUME_RESTRICT,
+                 hidden=1024, feat=512, trunk=None, seed=0):
+        super().__init__(vp_num, is_sigmoid, is_dropout, clamp_min, clamp_max, volume_restrict, hidden, feat, seed)
+        self.resnet = ResNet18() if trunk is None else trunk
+
+    def extract_feature(self, imgs):
+        maps = _trunk_maps(self.resnet, imgs)
+        out = self.avgpool(maps[3])
+        return out.view(out.size(0), -1), maps
+
+    def fix_volume_weight(self):
+        for p in self.volume_fc.parameters():
+            p.requires_grad = False
+
+    def forward_packed(self, imgs, masks=None, seed=None):
+        features, perceptual_features = self.extract_feature(imgs)
+        params = self.run_heads([features, features, features], 'vp_pack', masks, seed, **self._rule)
+        return params, perceptual_features, features
+
+    def forward(self, imgs):
+        params, perceptual_features, features = self.forward_packed(imgs)
+        volumes, rotates, translates = split_primitives(params)
+        return volumes, rotates, translates, perceptual_features, features
+
+
+class VPNetTwoRes(_VPNet):
+    """vpnet_two_resnet.py: one ResNet-18 for the volumes, one for rotation and translation."""
+
+    def __init__(self, vp_num=config.VP_NUM, is_sigmoid=config.IS_SIGMOID, is_dropout=config.IS_DROPOUT,
+                 clamp_min=config.VP_CLAMP_MIN, clamp_max=config.VP_CLAMP_MAX, volume_restrict=config.VOLUME_RESTRICT,
+                 hidden=1024, feat=512, trunk=None, seed=0):
+        super().__init__(vp_num, is_sigmoid, is_dropout, clamp_min, clamp_max, volume_restrict, hidden, feat, seed)
+        vt, tt = (ResNet18(), ResNet18()) if trunk is None else trunk          # trunk: a pair (volume, transform)
+        self.volume_resnet = vt
+        self.transform_resnet = tt
+
+    def extract_feature(self, model, imgs):
+        out = self.avgpool(_trunk_maps(model, imgs)[3])
+        return out.view(out.size(0), -1)
+
+    def fix_volume_weight(self):
+        for p in self.volume_resnet.parameters():
+            p.requires_grad = False
+        for p in self.volume_fc.parameters():
+            p.requires_grad = False
+
+    def forward_packed(self, imgs, masks=None, seed=None):
+        vf = self.extract_feature(self.volume_resnet, imgs)
+        tf = self.extract_feature(self.transform_resnet, imgs)
+        return self.run_heads([vf, tf, tf], 'vp_pack', masks, seed, **self._rule)
+
+    def forward(self, imgs):
+        return split_primitives(self.forward_packed(imgs))
+
+
+class SDNet(FcHeads):
+    """sdnet.py: the offsets of the 386 sphere vertices, tanh-bounded.  `_model` is the trunk with `avgpool` replaced
+    and `deform` attached, as the reference does; `deform.5` is the nn.Tanh it ends in (no parameters): the heads'
+    last launch applies it."""
+
+    def __init__(self, vertex_num=386, hidden=1024, feat=512, trunk=None):
+        super().__init__()
+        self._vertex_num = int(vertex_num)
+        self._model = ResNet18() if trunk is None else trunk
+        self._model.avgpool = nn.Sequential(nn.AdaptiveAvgPool2d(output_size=(1, 1)))
+        self._model.deform = nn.Sequential(*make_linear(self._vertex_num * 3, False, feat, hidden), nn.Tanh())
+        self._head_paths = ['_model.deform']
+
+    def extract_feature(self, imgs):
+        out = self._model.avgpool(_trunk_maps(self._model, imgs)[3])
+        return out.view(out.size(0), -1)
+
+    def forward(self, imgs):
+        offsets = self.run_heads([self.extract_feature(imgs)], 'tanh')
+        return offsets.view(imgs.size(0), self._vertex_num, 3)

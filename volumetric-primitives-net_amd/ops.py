@@ -337,6 +337,114 @@ class HeadPackFunction(Function):
         return gv, gq, gt, None, None, None, None
 
 
+class FcStackFunction(Function):
+    """G groups of L nn.Linear layers each, forward and backward on csrc/fcstack.hip: the FC heads of the reference's
+    networks (vpnet_one_resnet.py:31-41, :87-107; vpnet_two_resnet.py:34-44; sdnet.py:19, :24-25, :41-50), one launch per
+    layer for all groups.  apply(cfg, *tensors), tensors = the G inputs (B,in_g) -- one tensor may be passed for several
+    groups, autograd adds its gradients --, then weight, bias of every layer (group-major, layer-minor, nn.Linear's
+    layout), then, under cfg['dropout'] == 'mask', the uint8 keep masks (B,out) of layers 0..L-2 of every group.
+    cfg: G, L, epilogue 'none' | 'tanh' | 'vp_pack', dropout None | 'mask' | 'philox', p, seed (an int, or a CUDA int64
+    tensor of one element read by the kernels: bump it between steps, never between a forward and its backward), and for 'vp_pack'
+    is_sigmoid, clamp_min, clamp_max, volume_restrict.  Returns the G raw outputs ('none'), tanh of the one output
+    (B,out) ('tanh'), or the packed parameters (B,K,10) ('vp_pack')."""
+
+    EPILOGUES = {'none': _lib.FC_NONE, 'tanh': _lib.FC_TANH, 'vp_pack': _lib.FC_VP_PACK}
+    DROPOUTS = {None: _lib.FC_DROPOUT_OFF, 'mask': _lib.FC_DROPOUT_MASK, 'philox': _lib.FC_DROPOUT_PHILOX}
+
+    @staticmethod
+    def forward(ctx, cfg, *tensors):
+        G, L = int(cfg['G']), int(cfg['L'])
+        epi, drop = FcStackFunction.EPILOGUES[cfg.get('epilogue', 'none')], FcStackFunction.DROPOUTS[cfg.get('dropout')]
+        if not (1 <= L <= _lib.FC_MAX_LAYERS and 1 <= G and G * L <= _lib.FC_MAX_SLOTS):
+            raise ValueError('FcStackFunction: 1 <= L <= %d and G * L <= %d' % (_lib.FC_MAX_LAYERS, _lib.FC_MAX_SLOTS))
+        n_masks = G * (L - 1) if drop == _lib.FC_DROPOUT_MASK else 0
+        assert len(tensors) == G + 2 * G * L + n_masks, 'FcStackFunction: G inputs, G L (weight, bias) pairs, then the masks'
+        xs = [_f32c(t) for t in tensors[:G]]
+        wb = [_f32c(t) for t in tensors[G:G + 2 * G * L]]
+        masks = list(tensors[G + 2 * G * L:])
+        dev, B = xs[0].device, xs[0].shape[0]
+        st = _lib.FcStack()
+        st.G, st.L, st.B = G, L, B
+        acts, hold = [], []
+        for g in range(G):
+            assert xs[g].dim() == 2 and xs[g].shape[0] == B
+            st.in0[g], st.x[g] = xs[g].shape[1], xs[g].data_ptr()
+            width = xs[g].shape[1]
+            for l in range(L):
+                i = g * L + l
+                w, b = wb[2 * i], wb[2 * i + 1]
+                assert w.dim() == 2 and w.shape[1] == width and b.shape == (w.shape[0],), 'layer %d of group %d: shapes' % (l, g)
+                width = w.shape[0]
+                st.out[i], st.w[i], st.bias[i] = width, w.data_ptr(), b.data_ptr()
+                acts.append(torch.empty((B, width), dtype=torch.float32, device=dev))
+                st.act[i] = acts[-1].data_ptr()
+                if n_masks and l < L - 1:
+                    m = masks[g * (L - 1) + l]
+                    if not m.is_cuda:
+                        raise RuntimeError('vpn_amd operators run on the GPU only (got a %s tensor); there is no CPU path' % m.device.type)
+                    assert m.dtype == torch.uint8 and m.shape == (B, width) and m.is_contiguous()
+                    st.keep[i] = m.data_ptr()
+                    hold.append(m)
+        K, final = 0, None
+        if epi == _lib.FC_TANH:
+            assert G == 1
+            final = torch.empty((B, st.out[L - 1]), dtype=torch.float32, device=dev)
+        elif epi == _lib.FC_VP_PACK:
+            assert G == 3 and st.out[L - 1] % 3 == 0
+            K = st.out[L - 1] // 3
+            assert st.out[2 * L - 1] == 4 * K and st.out[3 * L - 1] == 3 * K, 'vp_pack: the heads end in 3K | 4K | 3K'
+            final = torch.empty((B, K, PARAM_STRIDE), dtype=torch.float32, device=dev)
+        r = [float(v) for v in cfg.get('volume_restrict', (1.0, 1.0, 1.0))]
+        seed_host, seed_dev = _seed_args(cfg.get('seed', 0))     # an int, or a device int64 step counter
+        tail = (drop, float(cfg.get('p', 0.5)), seed_host & 0xFFFFFFFFFFFFFFFF, seed_dev, epi, K,
+                int(bool(cfg.get('is_sigmoid', True))), float(cfg.get('clamp_min', 0.0)), float(cfg.get('clamp_max', 1.0)),
+                r[0], r[1], r[2])
+        _lib.call('vpn_fc_stack_fwd', st, *tail, final, _lib.stream())
+        ctx.save_for_backward(*xs, *wb, *acts, *hold)
+        ctx.meta = (G, L, B, n_masks, tail, max([st.in0[g] for g in range(G)] + [st.out[i] for i in range(G * L)]))
+        ctx.n_inputs = len(tensors)
+        if epi == _lib.FC_NONE:
+            outs = tuple(acts[g * L + L - 1] for g in range(G))
+            return outs if G > 1 else outs[0]
+        return final
+
+    @staticmethod
+    def backward(ctx, *grads):
+        G, L, B, n_masks, tail, maxw = ctx.meta
+        saved = ctx.saved_tensors
+        xs, wb = saved[:G], saved[G:G + 2 * G * L]
+        acts, hold = saved[G + 2 * G * L:G + 3 * G * L], saved[G + 3 * G * L:]
+        dev = xs[0].device
+        st, gr = _lib.FcStack(), _lib.FcGrad()
+        st.G, st.L, st.B = G, L, B
+        need = ctx.needs_input_grad[1:]
+        out = [None] * ctx.n_inputs
+        gouts = []
+        for g in range(G if tail[4] == _lib.FC_NONE else 1):
+            go = grads[g]
+            gouts.append(_f32c(go) if go is not None else torch.zeros_like(acts[g * L + L - 1]))
+            gr.gout[g] = gouts[-1].data_ptr()
+        for g in range(G):
+            st.in0[g], st.x[g] = xs[g].shape[1], xs[g].data_ptr()
+            if need[g]:
+                out[g] = torch.empty_like(xs[g])
+                gr.dx[g] = out[g].data_ptr()
+            for l in range(L):
+                i = g * L + l
+                st.out[i], st.w[i], st.bias[i], st.act[i] = wb[2 * i].shape[0], wb[2 * i].data_ptr(), wb[2 * i + 1].data_ptr(), acts[i].data_ptr()
+                if n_masks and l < L - 1:
+                    st.keep[i] = hold[g * (L - 1) + l].data_ptr()
+                if need[G + 2 * i]:
+                    out[G + 2 * i] = torch.empty_like(wb[2 * i])
+                    gr.dw[i] = out[G + 2 * i].data_ptr()
+                if need[G + 2 * i + 1]:
+                    out[G + 2 * i + 1] = torch.empty_like(wb[2 * i + 1])
+                    gr.db[i] = out[G + 2 * i + 1].data_ptr()
+        ws = _workspace('vpn_fc_stack_workspace', G, B, maxw, dev=dev, floor=4)
+        _lib.call('vpn_fc_stack_bwd', st, gr, *tail, ws, ws.numel() * 4, _lib.stream())
+        return (None, *out)
+
+
 class CameraTransformFunction(Function):
     """view_to_obj_points / obj_to_view_points (modules/transform/transform.py:21-73) in one launch.
     dists, elevs, azims, angles are dataset values (dataset.py:145-165): constants for autograd."""
