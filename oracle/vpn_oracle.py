@@ -631,32 +631,57 @@ def head_post_process(volumes, rotates, translates, is_sigmoid=True, clamp_min=0
 
 
 def train_step(params, gt_view, gt_canon, gt_sil, dists, elevs, azims, angles, kinds, n, H, W, weights, seed,
-               eps=0.005, iters=50, sigma=0.05, gamma=0.1, z_far=2.0):
+               eps=0.005, iters=50, sigma=0.05, gamma=0.1, z_far=2.0, sample_base=0, cd_w1=1.0, cd_w2=1.0, sil_mse=False,
+               grad_scale=1.0, return_decisions=False, emd_points=None):
     """One training iteration's loss of the reference (train.py:243-262) and its gradient w.r.t. the packed primitive
     parameters, fp32 on the CPU: sampler (Philox replay of the kernel's draws) -> view-centred Chamfer (train.py:160) +
     object-centred Chamfer through view_to_obj_points (:158-161) + L1 silhouette loss with the view-centred camera
     (:169-176, silhouette.py:13-23) + VP-diversity (:185, vp_diverse.py:15-17) + sqrt(EMD dist).mean() (:193-195; the
     assignment is a constant of the graph, as in emdFunction, emd_module.py:58-70).  weights = (L_VIEW_CD, L_CAN_CD, L_SIL,
-    L_VP_DIV, L_EMD).  Returns ([6] = the five weighted terms and their sum, d total / d params)."""
+    L_VP_DIV, L_EMD).  Returns ([6] = the five weighted terms and their sum, d total / d params).
+    sample_base: the global index of sample 0 in the Philox counter; cd_w1 / cd_w2: the direction weights of BOTH Chamfer
+    terms (config.CD_W1 / CD_W2, chamfer_distance.py:10; VP-diversity keeps its own 0.5 / 1.0); sil_mse: MSELoss instead of
+    L1Loss (silhouette.py:13-23); grad_scale: the upstream gradient of the total (the losses are returned unscaled).
+    return_decisions: also return the discrete choices this evaluation made, a dict of `view_nn`, `canon_nn`, `vpdiv_nn`
+    (each (idx1, idx2) of chamfer_nn on the same fp32 inputs), `emd_assign` ([B,N] or None when the term is off) and
+    `face_counts` ([B,K,6] int32, zero rows for spheres) -- what a float64 restatement must be handed, not recompute.
+    emd_points: the cloud [B,N,3] the auction assigns instead of this function's own sample.  The auction is chaotic in its
+    input: one ulp in one coordinate (another CPU's sin / cos suffices) can re-route hundreds of the 50 rounds' bids, so a
+    comparison with a kernel hands over the cloud THAT kernel's sampler drew (itself pinned to the oracle's sampler
+    elsewhere); the assignment is still this file's auction's, the term and its gradient still use this function's sample."""
     B, K = params.shape[0], params.shape[1]
     w = [float(x) for x in weights]
     p = params.detach().clone().requires_grad_(True)
-    u = philox_uniforms(seed, 0, B, K, n)
+    u = philox_uniforms(seed, sample_base, B, K, n)
     pred = sample_primitives(p, kinds, u)
     zero = torch.zeros(())
-    view_cd = chamfer_loss(pred, gt_view) * w[0]
-    obj_cd = chamfer_loss(view_to_obj_points(pred, dists, elevs, azims, angles), gt_canon) * w[1]
+    view_cd = chamfer_loss(pred, gt_view, w1=cd_w1, w2=cd_w2) * w[0]
+    canon = view_to_obj_points(pred, dists, elevs, azims, angles)
+    obj_cd = chamfer_loss(canon, gt_canon, w1=cd_w1, w2=cd_w2) * w[1]
     sil = zero
     if w[2]:
         cam = torch.tensor([[1.0, 0.0, 0.0]]).expand(B, 3)                        # train.py:172-174
         alpha, _ = raster(p, kinds, cam, H, W, sigma, gamma, z_far)
-        sil = (alpha - gt_sil.reshape(B, H, W)).abs().mean() * w[2]
+        d = alpha - gt_sil.reshape(B, H, W)
+        sil = ((d * d).mean() if sil_mse else d.abs().mean()) * w[2]
     div = chamfer_loss(p[:, :, 7:10], gt_view, w1=0.5, w2=1.0) * w[3] if w[3] else zero
     emd = zero
+    assign = None
     if w[4]:
-        _, assign = emd_auction(pred.detach(), gt_view, eps, iters)
+        _, assign = emd_auction(pred.detach() if emd_points is None else emd_points, gt_view, eps, iters)
         picked = torch.gather(gt_view, 1, assign.long()[..., None].expand(-1, -1, 3))
         emd = torch.sqrt(((pred - picked) ** 2).sum(-1)).mean() * w[4]
     total = view_cd + obj_cd + sil + div + emd
-    total.backward()
-    return torch.stack([view_cd, obj_cd, sil, div, emd, total]).detach(), p.grad
+    total.backward(torch.tensor(float(grad_scale)))
+    losses = torch.stack([view_cd, obj_cd, sil, div, emd, total]).detach()
+    if not return_decisions:
+        return losses, p.grad
+    with torch.no_grad():
+        nn = [chamfer_nn(a, b) for a, b in ((pred, gt_view), (canon, gt_canon), (p[:, :, 7:10], gt_view))]
+        counts = torch.zeros(B, K, 6, dtype=torch.int32)
+        for k in range(K):
+            if kinds[k] == CUBOID:
+                counts[:, k] = cuboid_face_counts(p[:, k, 0:3], n)
+    decisions = dict(view_nn=(nn[0][1], nn[0][3]), canon_nn=(nn[1][1], nn[1][3]), vpdiv_nn=(nn[2][1], nn[2][3]),
+                     emd_assign=assign, face_counts=counts)
+    return losses, p.grad, decisions

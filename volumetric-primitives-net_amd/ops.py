@@ -991,6 +991,9 @@ class TrainStepLossFunction(Function):
             raise ValueError('advance_seed needs a device seed (a CUDA int64 tensor of one element)')
         if w_emd and N != M:
             raise ValueError('the EMD term needs as many predicted as ground-truth points (emd_module.py:36): %d vs %d' % (N, M))
+        if M > FUSED_BWD_MAX_GT:           # the one-launch backward would refuse it, after the whole forward has run
+            raise ValueError('TrainStepLossFunction takes at most %d ground-truth points (the match lists of its backward launch), '
+                             'got %d' % (FUSED_BWD_MAX_GT, M))
         if not _lib.lib().vpn_hotpath_fused_features(B, K, n, M):
             raise ValueError('TrainStepLossFunction needs a shape the fused sampler / Chamfer path takes (K <= 64, large clouds)')
         f32 = dict(dtype=torch.float32, device=dev)
