@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-/* Still 9 with the visualisation stage (vpn_vis_primitives, vpn_vis_mesh, vpn_vis_mesh_workspace): entries were added, none
+/* Still 9 with vpn_hotpath_tile_rider_fits (the host-side answer to "would vpn_hotpath_chamfer_fwd take the rider?") and
+ * with the visualisation stage (vpn_vis_primitives, vpn_vis_mesh, vpn_vis_mesh_workspace): entries were added, none
  * changed, and the binding resolves every symbol by name when it loads the library, so a library without them is refused
  * there.  9: the evaluation stage (vpn_eval_state_size, vpn_eval_accumulate).  8: the batch augmentation stage (vpn_cutmix_*, vpn_mixup_*).  7: the GCN refinement stage (vpn_gcn_*).  6: vpn_emd_fwd_ex, vpn_emd_recovered_samples, vpn_emd_last_group.
  * 5 (round 4): vpn_vpdiv_fwd, vpn_camera_matrix, vpn_trainstep_finalize, vpn_trainstep_bwd (the reference's whole training
@@ -112,7 +113,9 @@ int vpn_sample_bwd(const float* params, const int32_t* kinds, const float* u,
  * none) followed by vpn_sample_bwd, without the [B,K*n,3] point gradient in between and in a fixed summation
  * order.  points [B,K*n,3] = what vpn_sample_fwd produced from the same (params, kinds, u | seed, sample_base);
  * dist/idx from vpn_chamfer_fwd*(points, gt_points); grad_loss_b [B] as in vpn_chamfer_bwd.
- * M <= 7680 (VPN_E_TOOBIG beyond: use the two separate calls). */
+ * M <= VPN_FUSED_BWD_MAX_GT (VPN_E_TOOBIG beyond: use the two separate calls): the kernel keeps per-wave match lists of the
+ * GT points in LDS, 8 bytes a point in 60 KB. */
+#define VPN_FUSED_BWD_MAX_GT 7680
 int vpn_sample_chamfer_bwd(const float* params, const int32_t* kinds, const float* u,
                            uint64_t seed, const uint64_t* seed_dev, uint64_t sample_base, int B, int K, int n,
                            const float* points, const float* gt_points, int M,
@@ -292,8 +295,11 @@ int vpn_hotpath_fused_features(int B, int K, int n, int M);
  * (tile, number of visible primitives, their mask, four quadrant masks), the tiles of every image sorted by visible
  * primitives, heaviest first -- what a tile wave of vpn_raster_total_fwd_fin needs to know, in one load (the second half
  * of the buffer is the rider's scratch: the same entries by tile).  tile_order == NULL: exactly vpn_chamfer_fwd_ws.
- * VPN_E_TOOBIG if K > 64 or the image has more than 16384 tiles (the caller then runs without it). */
+ * VPN_E_TOOBIG if K > 64, the image has more than 16384 tiles or the rider's scratch (84 K + 4 (K + 2) + tiles bytes) does
+ * not fit the scan's 24 KB of LDS (the caller then runs without it).  vpn_hotpath_tile_rider_fits: 1 if the rider is taken
+ * for (K, H, W), 0 if that is the answer; host arithmetic only, no HIP call. */
 size_t vpn_raster_order_size(int B, int H, int W);
+int vpn_hotpath_tile_rider_fits(int K, int H, int W);
 int vpn_hotpath_chamfer_fwd(const float* p1, const float* p2, int B, int N, int M, float* dist1, int32_t* idx1,
                             float* dist2, int32_t* idx2, void* workspace, size_t workspace_bytes, int mode,
                             void* records, int K, int H, int W, void* tile_order, void* stream);
@@ -716,8 +722,8 @@ int vpn_union_surface(const float* verts, const int32_t* keep, const float* dirs
  *     rotation; angles_out [B] fp32 degrees, the angle each image was rotated by (0 without VPN_INPUT_ROTATE).
  *   tables: int32, hb [W,2] | hk [W,ksh] | vb [H,2] | vk [H,ksv]: for every output column / row the first source tap and
  *     the tap count, and the taps' coefficients round(k 2^22), built by the host in float64 as PIL's precompute_coeffs does.
- *     max_rows: the most source rows the vertical support of 8 consecutive output rows spans (the LDS of one tile: 128
- *     max_rows bytes <= 64 KB, VPN_E_TOOBIG beyond).  Entries that point outside the source are clamped on the device.
+ *     max_rows: the most source rows the vertical support of the VPN_INPUT_TILE_ROWS consecutive output rows of one tile
+ *     spans (the LDS of one tile: 128 max_rows bytes <= 64 KB, VPN_E_TOOBIG beyond).  Entries that point outside the source are clamped on the device.
  *   flags: VPN_INPUT_JITTER | VPN_INPUT_ROTATE | VPN_INPUT_NORMALIZE (ImageNet mean / std, also on the rotation's zero fill).
  *   factors [B,3] fp32 (brightness, contrast, saturation), order [B,3] int32 (the operation of each turn: 0 brightness,
  *     1 contrast, 2 saturation), angles [B] fp32 degrees: the draws, each NULL or given.  A NULL one is drawn from
@@ -729,6 +735,7 @@ int vpn_union_surface(const float* verts, const int32_t* keep, const float* dirs
 #define VPN_INPUT_JITTER 1
 #define VPN_INPUT_ROTATE 2
 #define VPN_INPUT_NORMALIZE 4
+#define VPN_INPUT_TILE_ROWS 8
 size_t vpn_input_ws(int B);
 int vpn_prepare_images(const uint8_t* rgba, const int32_t* tables, int ksh, int ksv, int max_rows, const float* factors,
                        const int32_t* order, const float* angles, uint64_t seed, const uint64_t* seed_dev,

@@ -116,3 +116,116 @@ def test_reference_surface_is_mirrored():
     t = [torch.rand(2, 3) for _ in range(3)]
     p = vpn_amd.pack_primitives(v, q, t)
     assert p.shape == (2, 3, 10) and torch.equal(p[:, 1, 3:7], q[1])
+
+
+# ---- the binding is derived from include/vpn_hip.h (_lib._header_constants / _header_signatures)
+
+def test_derived_signatures_equal_the_frozen_rows():
+    """Rows of the hand-written table the reader replaced, kept as they stood: between them every type kind the header uses
+    and the longest parameter lists (vpn_profile_read with all pointers as void*, the reader's uniform rule)."""
+    import vpn_amd._lib as lib
+    _c_f = ctypes.c_void_p
+    _i, _f, _u64, _sz = ctypes.c_int, ctypes.c_float, ctypes.c_uint64, ctypes.c_size_t
+    FcStack, FcGrad = lib.FcStack, lib.FcGrad
+    frozen = {
+        'vpn_trainstep_bwd': (_i, [_c_f, _c_f, _u64, _c_f, _u64, _i, _i, _i, _c_f, _c_f, _i, _c_f, _c_f, _c_f, _c_f, _f, _f, _c_f, _i, _i,
+                                   _c_f, _c_f, _c_f, _c_f, _c_f, _f, _c_f, _c_f, _c_f, _c_f, _f, _f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,
+                                   _f, _f, _i, _c_f, _c_f]),
+        'vpn_raster_total_fwd_fin': (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _i, _f, _f, _f, _c_f, _c_f, _i, _f, _f, _c_f, _c_f, _c_f, _i,
+                                          _c_f, _sz, _i, _i, _f, _f, _f, _c_f, _c_f, _c_f, _c_f, _c_f]),
+        'vpn_gcn_input_fwd': (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _i, _i] + [_c_f] * 4 + [_i] * 12 + [_c_f] * 6),
+        'vpn_fc_stack_bwd': (_i, [FcStack, FcGrad, _i, _f, _u64, _c_f, _i, _i, _i, _f, _f, _f, _f, _f, _c_f, _sz, _c_f]),
+        'vpn_ragged_sample': (_i, [_c_f] * 7 + [ctypes.c_uint, _c_f, _u64, _c_f, _u64] + [_i] * 6 + [_c_f, _sz] + [_c_f] * 4),
+        'vpn_prepare_images': (_i, [_c_f, _c_f, _i, _i, _i, _c_f, _c_f, _c_f, _u64, _c_f, _u64] + [_i] * 6 + [_c_f, _sz] + [_c_f] * 5),
+        'vpn_vis_mesh': (_i, [_c_f, _c_f, _c_f, _c_f, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _c_f, _c_f, _sz, ctypes.c_longlong, _c_f, _c_f]),
+        'vpn_emd_fwd_ex': (_i, [_c_f, _c_f, _i, _i, _f, _i, _c_f, _c_f, _c_f, _i, _c_f, ctypes.c_uint]),
+        'vpn_emd_recovered_samples': (ctypes.c_longlong, []),
+        'vpn_error_string': (ctypes.c_char_p, [_i]),
+        'vpn_chamfer_workspace': (_sz, [_i, _i, _i]),
+        'vpn_profile_read': (_i, [_c_f, _i, _c_f, _c_f, _i]),
+    }
+    assert len(frozen['vpn_trainstep_bwd'][1]) == 44 and len(frozen['vpn_raster_total_fwd_fin'][1]) == 31
+    for name, (res, args) in frozen.items():
+        got_res, got_args = lib.SIGNATURES[name]
+        assert got_res is res, name
+        assert [t.__name__ for t in got_args] == [t.__name__ for t in args], name
+        assert all(a is b for a, b in zip(got_args, args)), name
+
+
+def test_header_reader_on_its_own_text():
+    import vpn_amd._lib as lib
+    sig = lambda text: lib._header_signatures(text, lib.BY_VALUE)
+    with pytest.raises(RuntimeError, match='vpn_x.*double'):              # a type outside the map is an error that names the place
+        sig('int vpn_x(double y);')
+    with pytest.raises(RuntimeError, match='vpn_x.*double'):
+        sig('double vpn_x(int y);')
+    with pytest.raises(RuntimeError, match='vpn_x'):                      # ... and so is a pointer result that is no C string
+        sig('float* vpn_x(int y);')
+    split = '''#define VPN_LIMIT 4
+    size_t vpn_two_lines(const float* a,   /* first [B,3] */
+                         int n, /* a block comment
+                         over two lines, with a (parenthesis) and a vpn_name( in it */ uint64_t seed,
+                         const long long* offsets, unsigned mask,   // a line comment; with a semicolon
+                         long long pitch, VpnFcStack stack,
+                         void* stream);
+    int vpn_none(void);
+    const char* vpn_text(int code);'''
+    got = sig(split)
+    assert got == {'vpn_two_lines': (ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint,
+                                                       ctypes.c_longlong, lib.FcStack, ctypes.c_void_p]),
+                   'vpn_none': (ctypes.c_int, []),
+                   'vpn_text': (ctypes.c_char_p, [ctypes.c_int])}
+    assert sig('int vpn_empty();') == {'vpn_empty': (ctypes.c_int, [])}
+    consts = lib._header_constants('#define VPN_E_BADARG (-1)\n#define VPN_E_TOOBIG  ( -2 )   /* too big */\n#define VPN_N 12 // twelve\n'
+                                   '#define VPN_HIP_H\n#define VPN_RATIO 0.5f\n/* #define VPN_GONE 3 */\n#define OTHER 7\n')
+    assert consts == {'VPN_E_BADARG': -1, 'VPN_E_TOOBIG': -2, 'VPN_N': 12}
+
+
+def test_python_constants_are_the_headers():
+    """Every limit and flag the package names is the header's #define (read here with this test's own pattern); the two that
+    are properties of the kernels, and from which other tests build shapes, are pinned as numbers too."""
+    import vpn_amd._lib as lib
+    from vpn_amd import ops
+    from vpn_amd.modules import dataset
+    hdr = open(os.path.join(ROOT, 'include', 'vpn_hip.h')).read()
+
+    def define(name):
+        found = re.findall(r'^#define %s +\(?(-?\d+)\)?' % name, hdr, flags=re.M)
+        assert len(found) == 1, name
+        return int(found[0])
+
+    pairs = [(lib.ABI_VERSION, 'VPN_ABI_VERSION'), (lib.FC_MAX_LAYERS, 'VPN_FC_MAX_LAYERS'), (lib.FC_MAX_SLOTS, 'VPN_FC_MAX_SLOTS'),
+             (lib.FC_NONE, 'VPN_FC_NONE'), (lib.FC_TANH, 'VPN_FC_TANH'), (lib.FC_VP_PACK, 'VPN_FC_VP_PACK'),
+             (lib.FC_DROPOUT_OFF, 'VPN_FC_DROPOUT_OFF'), (lib.FC_DROPOUT_MASK, 'VPN_FC_DROPOUT_MASK'),
+             (lib.FC_DROPOUT_PHILOX, 'VPN_FC_DROPOUT_PHILOX'), (ops.SPHERE, 'VPN_SPHERE'), (ops.CUBOID, 'VPN_CUBOID'),
+             (ops.PARAM_STRIDE, 'VPN_PARAM_STRIDE'), (ops.RAGGED_MAX_SETS, 'VPN_RAGGED_MAX_SETS'), (ops.INPUT_JITTER, 'VPN_INPUT_JITTER'),
+             (ops.INPUT_ROTATE, 'VPN_INPUT_ROTATE'), (ops.INPUT_NORMALIZE, 'VPN_INPUT_NORMALIZE'),
+             (ops.FUSED_BWD_MAX_GT, 'VPN_FUSED_BWD_MAX_GT'), (ops.INPUT_TILE_ROWS, 'VPN_INPUT_TILE_ROWS'),
+             (dataset.CHUNK, 'VPN_RAGGED_CHUNK')]
+    for value, name in pairs:
+        assert type(value) is int and value == define(name), name
+    assert lib.CONSTANTS['VPN_E_BADARG'] == define('VPN_E_BADARG') == -1 and lib.CONSTANTS['VPN_E_TOOBIG'] == define('VPN_E_TOOBIG') == -2
+    assert ops.FUSED_BWD_MAX_GT == 7680 and ops.INPUT_TILE_ROWS == 8
+    assert ctypes.sizeof(lib.FcStack) == 4 * 4 + define('VPN_FC_MAX_SLOTS') * (2 * 4 + 5 * 8)
+
+
+def test_tile_rider_fits_is_the_old_arithmetic():
+    """vpn_hotpath_tile_rider_fits (host arithmetic, no GPU) against the Python expression it replaced."""
+    import vpn_amd._lib as lib
+    from vpn_amd import ops
+
+    def lds(K, H, W):
+        return K * 84 + (K + 2) * 4 + ((W + 15) // 16) * ((H + 15) // 16)
+
+    def old(K, H, W):
+        return K <= 64 and ((W + 15) // 16) * ((H + 15) // 16) <= 16384 and lds(K, H, W) <= 24576
+
+    k_lds = next(K for K in range(1, 1 << 12) if lds(K, 128, 128) > 24576)      # the first K whose scratch outgrows the scan's LDS
+    cases = [(16, 128, 128), (64, 128, 128), (65, 128, 128), (1, 2048, 2048), (64, 2048, 2048), (1, 1808, 2320), (1, 2048, 2049),
+             (k_lds - 1, 128, 128), (k_lds, 128, 128), (16, 127, 129), (16, 1, 1)]
+    assert (2048 // 16) ** 2 == 16384 and (1808 // 16) * (2320 // 16) == 16385 and lds(k_lds - 1, 128, 128) <= 24576
+    assert old(16, 128, 128) and old(64, 2048, 2048) and not old(65, 128, 128) and not old(1, 1808, 2320)
+    L = lib.lib()
+    for K, H, W in cases:
+        assert L.vpn_hotpath_tile_rider_fits(K, H, W) == int(old(K, H, W)), (K, H, W)
+        assert bool(ops._tile_rider_fits(K, H, W)) == (ops.TILE_ORDER and old(K, H, W)), (K, H, W)

@@ -4,19 +4,59 @@ There is no CPU or PyTorch fallback: if the library is missing or a call fails t
 binding raises.  PyTorch is used only for device memory and the current HIP stream."""
 import ctypes
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('VPN_HIP_LIB') or os.path.join(_HERE, 'libvpn_hip.so')     # VPN_HIP_LIB: the sanitizer build of the tests
-ABI_VERSION = 9
+HEADER_PATH = os.path.join(_HERE, '..', 'include', 'vpn_hip.h')
 
-_c_f = ctypes.c_void_p      # device pointers travel as void*
-_i, _f, _u64, _sz = ctypes.c_int, ctypes.c_float, ctypes.c_uint64, ctypes.c_size_t
 
-FC_MAX_LAYERS, FC_MAX_SLOTS = 8, 24      # VPN_FC_MAX_LAYERS, VPN_FC_MAX_SLOTS
-FC_NONE, FC_TANH, FC_VP_PACK = 0, 1, 2
-FC_DROPOUT_OFF, FC_DROPOUT_MASK, FC_DROPOUT_PHILOX = 0, 1, 2
+# ---- include/vpn_hip.h is the one place a limit, a flag or a signature of the C ABI is written: the binding reads it
+
+def _header_code(text):
+    """Header text without its comments."""
+    return re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+
+
+def _header_constants(text):
+    """{name: value} of the integer `#define VPN_*` of header `text` (a negative one stands in parentheses)."""
+    pattern = r'^[ \t]*#[ \t]*define[ \t]+(VPN_\w+)[ \t]+(?:(\d+)|\([ \t]*(-?\d+)[ \t]*\))[ \t]*$'
+    return {m.group(1): int(m.group(2) or m.group(3)) for m in re.finditer(pattern, _header_code(text), flags=re.M)}
+
+
+def _header_signatures(text, by_value):
+    """{name: (restype, [argtypes])} of every `vpn_*` prototype of header `text`.  A pointer parameter travels as void*
+    whatever it points to (device pointers, and ctypes arrays and buffers convert to it), a `const char*` result is a C
+    string, every other type is looked up in `by_value`; one that is not there is an error, never a guess."""
+    code = ';' + re.sub(r'^[ \t]*#.*$', '', _header_code(text), flags=re.M)
+
+    def ctype(c_type, table, where):
+        if c_type not in table:
+            raise RuntimeError('vpn_hip.h: %s has type %r, which the binding cannot pass' % (where, c_type))
+        return table[c_type]
+
+    out = {}
+    for m in re.finditer(r'(?<=[;{}])([\w\s*]+?)\b(vpn_\w+)\s*\(([^()]*)\)\s*;', code):
+        res, name, params = ' '.join(m.group(1).replace('*', ' * ').split()), m.group(2), m.group(3).strip()
+        args = []
+        for param in ([] if params in ('', 'void') else params.split(',')):
+            words = [w for w in param.split() if w != 'const']                      # the type, then the parameter's name
+            args.append(ctypes.c_void_p if '*' in param else
+                        ctype(' '.join(words[:-1]), by_value, '%s: parameter %r' % (name, ' '.join(param.split()))))
+        out[name] = (ctype(res, dict(by_value, **{'const char *': ctypes.c_char_p}), name + ': the result'), args)
+    return out
+
+
+with open(HEADER_PATH) as _f:
+    _HEADER = _f.read()
+CONSTANTS = _header_constants(_HEADER)
+ABI_VERSION = CONSTANTS['VPN_ABI_VERSION']
+FC_MAX_LAYERS, FC_MAX_SLOTS = CONSTANTS['VPN_FC_MAX_LAYERS'], CONSTANTS['VPN_FC_MAX_SLOTS']
+FC_NONE, FC_TANH, FC_VP_PACK = CONSTANTS['VPN_FC_NONE'], CONSTANTS['VPN_FC_TANH'], CONSTANTS['VPN_FC_VP_PACK']
+FC_DROPOUT_OFF, FC_DROPOUT_MASK, FC_DROPOUT_PHILOX = (CONSTANTS['VPN_FC_DROPOUT_OFF'], CONSTANTS['VPN_FC_DROPOUT_MASK'],
+                                                      CONSTANTS['VPN_FC_DROPOUT_PHILOX'])
 
 
 class FcStack(ctypes.Structure):
@@ -34,100 +74,10 @@ class FcGrad(ctypes.Structure):
                 ('db', ctypes.c_void_p * FC_MAX_SLOTS), ('dx', ctypes.c_void_p * FC_MAX_SLOTS)]
 
 
-SIGNATURES = {
-    'vpn_abi_version': (ctypes.c_int, []),
-    'vpn_error_string': (ctypes.c_char_p, [_i]),
-    'vpn_profile_enable': (_i, [_i]),
-    'vpn_profile_read': (_i, [ctypes.c_char_p, _i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int), _i]),
-    'vpn_sample_fwd': (_i, [_c_f, _c_f, _c_f, _u64, _c_f, _u64, _i, _i, _i, _c_f, _c_f]),
-    'vpn_sample_bwd': (_i, [_c_f, _c_f, _c_f, _u64, _c_f, _u64, _i, _i, _i, _c_f, _c_f, _c_f]),
-    'vpn_sample_chamfer_bwd': (_i, [_c_f, _c_f, _c_f, _u64, _c_f, _u64, _i, _i, _i, _c_f, _c_f, _i, _c_f, _c_f, _c_f, _c_f, _c_f,
-                                    _f, _f, _c_f, _c_f]),
-    'vpn_transform_fwd': (_i, [_c_f, _c_f, _c_f, _i, _i, _c_f, _c_f]),
-    'vpn_transform_bwd': (_i, [_c_f, _c_f, _c_f, _i, _i, _c_f, _c_f, _c_f, _c_f]),
-    'vpn_chamfer_fwd': (_i, [_c_f, _c_f, _i, _i, _i, _c_f, _c_f, _c_f, _c_f, _c_f]),
-    'vpn_chamfer_nn': (_i, [_c_f, _c_f, _i, _i, _i, _c_f, _c_f, _c_f]),
-    'vpn_chamfer_workspace': (_sz, [_i, _i, _i]),
-    'vpn_chamfer_fwd_ws': (_i, [_c_f, _c_f, _i, _i, _i, _c_f, _c_f, _c_f, _c_f, _c_f, _sz, _i, _c_f]),
-    'vpn_chamfer_loss': (_i, [_c_f, _c_f, _i, _i, _i, _f, _f, _c_f, _c_f]),
-    'vpn_chamfer_bwd': (_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _i, _i, _i, _f, _f, _c_f, _c_f, _c_f]),
-    'vpn_raster_records_size': (_sz, [_i, _i, _i, _i]),
-    'vpn_raster_fwd': (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _i, _f, _f, _f, _c_f, _c_f, _c_f, _c_f, _c_f]),
-    'vpn_raster_bwd_workspace': (_sz, [_i, _i, _i, _i]),
-    'vpn_raster_bwd': (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _i, _f, _f, _f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
-    'vpn_raster_loss_workspace': (_sz, [_i, _i, _i]),
-    'vpn_raster_loss_fwd': (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _i, _f, _f, _f, _c_f, _c_f, _i, _c_f, _c_f, _c_f, _c_f, _c_f]),
-    'vpn_raster_total_fwd': (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _i, _f, _f, _f, _c_f, _c_f, _i, _f, _f, _c_f, _c_f, _c_f, _i, _c_f]),
-    'vpn_raster_total_fwd_fin': (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _i, _f, _f, _f, _c_f, _c_f, _i, _f, _f, _c_f, _c_f, _c_f, _i,
-                                      _c_f, _sz, _i, _i, _f, _f, _f, _c_f, _c_f, _c_f, _c_f, _c_f]),
-    'vpn_hotpath_sample_fwd': (_i, [_c_f, _c_f, _c_f, _u64, _c_f, _u64, _i, _i, _i, _c_f, _c_f, _i, _i, _f, _c_f, _c_f,
-                                    _c_f, _i, _c_f, _sz, _c_f]),
-    'vpn_hotpath_fused_features': (_i, [_i, _i, _i, _i]),
-    'vpn_raster_order_size': (_sz, [_i, _i, _i]),
-    'vpn_hotpath_chamfer_fwd': (_i, [_c_f, _c_f, _i, _i, _i, _c_f, _c_f, _c_f, _c_f, _c_f, _sz, _i, _c_f, _i, _i, _i, _c_f, _c_f]),
-    'vpn_loss_finalize': (_i, [_c_f, _i, _i, _i, _c_f, _c_f, _i, _i, _f, _f, _f, _f, _f, _c_f, _c_f, _c_f]),
-    'vpn_raster_total_bwd': (_i, [_c_f, _c_f, _i, _i, _i, _i, _c_f, _c_f, _c_f, _c_f, _i, _c_f]),
-    'vpn_hotpath_bwd': (_i, [_c_f, _c_f, _c_f, _u64, _c_f, _u64, _i, _i, _i, _c_f, _c_f, _i, _c_f, _c_f, _c_f, _c_f, _c_f,
-                             _f, _f, _c_f, _i, _i, _c_f, _c_f, _c_f, _c_f, _c_f]),
-    'vpn_raster_loss_bwd': (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _i, _f, _f, _f, _c_f, _c_f, _c_f, _c_f, _i, _c_f, _c_f, _c_f,
-                                 _i, _c_f]),
-    'vpn_camera_transform_fwd': (_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _i, _i, _i, _c_f, _c_f]),
-    'vpn_camera_transform_bwd': (_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _i, _i, _i, _c_f, _c_f]),
-    'vpn_mesh_fwd': (_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _i, _i, _i, _c_f, _c_f]),
-    'vpn_mesh_bwd': (_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _i, _i, _i, _c_f, _c_f, _c_f]),
-    'vpn_mesh_raster_workspace': (_sz, [_i, _i]),
-    'vpn_mesh_raster_fwd': (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _i, _i, _f, _c_f, _c_f, _c_f]),
-    'vpn_mesh_raster_bwd': (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _i, _i, _f, _c_f, _c_f, _c_f, _c_f, _c_f]),
-    'vpn_mesh_sample_fwd': (_i, [_c_f, _c_f, _c_f, _u64, _u64, _i, _i, _i, _i, _c_f, _c_f, _c_f, _c_f, _c_f]),
-    'vpn_mesh_sample_bwd': (_i, [_c_f, _c_f, _c_f, _c_f, _i, _i, _i, _i, _c_f, _c_f]),
-    'vpn_head_pack_fwd': (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _f, _f, _f, _f, _f, _c_f, _c_f]),
-    'vpn_head_pack_bwd': (_i, [_c_f, _c_f, _c_f, _c_f, _i, _i, _i, _f, _f, _f, _f, _f, _c_f, _c_f, _c_f, _c_f]),
-    'vpn_vpdiv_workspace': (_sz, [_i, _i]),
-    'vpn_vpdiv_fwd': (_i, [_c_f, _c_f, _i, _i, _i, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
-    'vpn_trainstep_workspace': (_sz, [_i]),
-    'vpn_camera_matrix': (_i, [_c_f, _c_f, _c_f, _c_f, _i, _i, _c_f, _c_f]),
-    'vpn_trainstep_finalize': (_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
-    'vpn_trainstep_bwd': (_i, [_c_f, _c_f, _u64, _c_f, _u64, _i, _i, _i, _c_f, _c_f, _i, _c_f, _c_f, _c_f, _c_f, _f, _f, _c_f, _i, _i,
-                               _c_f, _c_f, _c_f, _c_f, _c_f, _f, _c_f, _c_f, _c_f, _c_f, _f, _f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,
-                               _f, _f, _i, _c_f, _c_f]),
-    'vpn_emd_workspace': (_sz, [_i, _i]),
-    'vpn_emd_fwd': (_i, [_c_f, _c_f, _i, _i, _f, _i, _c_f, _c_f, _c_f, _i, _c_f]),
-    'vpn_emd_fwd_ex': (_i, [_c_f, _c_f, _i, _i, _f, _i, _c_f, _c_f, _c_f, _i, _c_f, ctypes.c_uint]),
-    'vpn_emd_recovered_samples': (ctypes.c_longlong, []),
-    'vpn_emd_last_group': (_i, []),
-    'vpn_emd_bwd': (_i, [_c_f, _c_f, _c_f, _c_f, _i, _i, _c_f, _c_f]),
-    'vpn_gcn_aggregate': (_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _i, _i, _i, _i, _c_f, _c_f]),
-    'vpn_gcn_colsum_workspace': (_sz, [_i, _i, _i]),
-    'vpn_gcn_colsum': (_i, [_c_f, _c_f, _i, _i, _i, _i, _i, _c_f, _c_f, _c_f]),
-    'vpn_gcn_bounds': (_i, [_c_f, _i, _i, _i, _i, _c_f, _c_f]),
-    'vpn_gcn_maps_workspace': (_sz, [_i, _i] + [_i] * 12),
-    'vpn_gcn_input_fwd': (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _i, _i] + [_c_f] * 4 + [_i] * 12 + [_c_f] * 6),
-    'vpn_gcn_input_bwd_workspace': (_sz, [_i, _i, _i] + [_i] * 12),
-    'vpn_gcn_input_bwd': (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _i, _i] + [_i] * 12 + [_c_f] * 11),
-    'vpn_cutmix_points_lds': (_sz, [_i]),
-    'vpn_cutmix_points': (_i, [_c_f, _c_f, _c_f, _f, _u64, _u64, _i, _i, _i, _c_f, _c_f, _c_f, _c_f]),
-    'vpn_cutmix_images': (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _i, _i, _i, _c_f, _c_f, _c_f]),
-    'vpn_mixup_gather': (_i, [_c_f, _c_f, _i, _i, _c_f, _c_f]),
-    'vpn_mixup_lerp': (_i, [_c_f, _c_f, _c_f, _i, _i, _f, _f, _c_f, _c_f]),
-    'vpn_eval_state_size': (_sz, [_i]),
-    'vpn_eval_accumulate': (_i, [_c_f, _c_f, _c_f, _c_f, _i, _i, _i, _i, _f, _f, _f, _c_f, _c_f, _c_f, _c_f]),
-    'vpn_vis_primitives': (_i, [_c_f, _c_f, _c_f, _c_f, _i, _i, _i, _i, _i, _f, _f, _f, _f, _c_f, _sz, ctypes.c_longlong, _c_f, _c_f]),
-    'vpn_vis_mesh_workspace': (_sz, [_i, _i, _i]),
-    'vpn_vis_mesh': (_i, [_c_f, _c_f, _c_f, _c_f, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _c_f, _c_f, _sz, ctypes.c_longlong, _c_f, _c_f]),
-    'vpn_phong_mesh_workspace': (_sz, [_i, _i, _i]),
-    'vpn_phong_mesh': (_i, [_c_f] * 7 + [_f] + [_i] * 8 + [_c_f, _c_f, _c_f]),
-    'vpn_cluster_points': (_i, [_c_f, _i, _i, _i, _i, _c_f, _c_f, _c_f, _c_f]),
-    'vpn_support_hulls': (_i, [_c_f, _c_f, _c_f, _c_f, _i, _i, _i, _i, _c_f, _c_f, _c_f]),
-    'vpn_hull_augment': (_i, [_c_f] * 8 + [_i] * 4 + [_c_f, _c_f, _c_f]),
-    'vpn_union_surface': (_i, [_c_f] * 5 + [_i] * 5 + [_f] + [_c_f] * 6),
-    'vpn_input_ws': (_sz, [_i]),
-    'vpn_prepare_images': (_i, [_c_f, _c_f, _i, _i, _i, _c_f, _c_f, _c_f, _u64, _c_f, _u64] + [_i] * 6 + [_c_f, _sz] + [_c_f] * 5),
-    'vpn_ragged_sample_workspace': (_sz, [_i, _i, _i]),
-    'vpn_ragged_sample': (_i, [_c_f] * 7 + [ctypes.c_uint, _c_f, _u64, _c_f, _u64] + [_i] * 6 + [_c_f, _sz] + [_c_f] * 4),
-    'vpn_fc_stack_workspace': (_sz, [_i, _i, _i]),
-    'vpn_fc_stack_fwd': (_i, [FcStack, _i, _f, _u64, _c_f, _i, _i, _i, _f, _f, _f, _f, _f, _c_f, _c_f]),
-    'vpn_fc_stack_bwd': (_i, [FcStack, FcGrad, _i, _f, _u64, _c_f, _i, _i, _i, _f, _f, _f, _f, _f, _c_f, _sz, _c_f]),
-}
+# every type the header passes by value (parameters and results)
+BY_VALUE = {'int': ctypes.c_int, 'unsigned': ctypes.c_uint, 'long long': ctypes.c_longlong, 'float': ctypes.c_float,
+            'uint64_t': ctypes.c_uint64, 'size_t': ctypes.c_size_t, 'VpnFcStack': FcStack, 'VpnFcGrad': FcGrad}
+SIGNATURES = _header_signatures(_HEADER, BY_VALUE)
 
 _lib = None
 

@@ -2177,6 +2177,17 @@ extern "C" size_t vpn_raster_order_size(int B, int H, int W) {
     return 2 * (size_t)B * ntile * sizeof(TileEntry);              // entries by launch rank + the same by tile (scratch of the rider)
 }
 
+// whether the scan's launch can carry the rider for K primitives and ntile tiles: one mask word per tile and the rider's
+// scratch inside the scan's own LDS
+static bool tile_rider_fits(int K, long long ntile) {
+    return K <= R_ORDER_MAX_PRIMS && ntile <= R_ORDER_MAX_TILES && raster_order_scratch(K, (int)ntile) <= 2 * CM_TILE16 * CM_ROWB;
+}
+
+extern "C" int vpn_hotpath_tile_rider_fits(int K, int H, int W) {
+    if (K <= 0 || H <= 0 || W <= 0) return 0;
+    return tile_rider_fits(K, (long long)((W - 1) / R_TW + 1) * ((H - 1) / R_TH + 1)) ? 1 : 0;
+}
+
 extern "C" int vpn_hotpath_chamfer_fwd(const float* p1, const float* p2, int B, int N, int M, float* dist1, int32_t* idx1,
                                        float* dist2, int32_t* idx2, void* workspace, size_t workspace_bytes, int mode,
                                        void* records, int K, int H, int W, void* tile_order, void* stream) {
@@ -2198,7 +2209,7 @@ extern "C" int vpn_hotpath_chamfer_fwd(const float* p1, const float* p2, int B, 
         oj.masks = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(records) + (size_t)B * K * R_REC * sizeof(float4));
         oj.entries = (TileEntry*)tile_order;
         if (((uintptr_t)tile_order & 15) != 0) return VPN_E_BADARG;
-        if (K > R_ORDER_MAX_PRIMS || oj.ntile > R_ORDER_MAX_TILES || raster_order_scratch(K, oj.ntile) > 2 * CM_TILE16 * CM_ROWB) return VPN_E_TOOBIG;
+        if (!tile_rider_fits(K, oj.ntile)) return VPN_E_TOOBIG;
         rider = &oj;
     }
     return mfma_both(p1, p2, B, N, M, (float*)workspace, dist1, idx1, dist2, idx2, 2, (hipStream_t)stream, mode == 7, rider);

@@ -19,7 +19,7 @@ namespace {
 #pragma clang fp contract(off)
 
 constexpr int IN_THREADS = 256;
-constexpr int IN_TW = 32, IN_TH = 8;             // output tile of the resize: one pixel per thread in the vertical pass
+constexpr int IN_TW = 32, IN_TH = VPN_INPUT_TILE_ROWS;      // output tile of the resize: one pixel per thread in the vertical pass
 constexpr int IN_BITS = 22;                      // PIL's PRECISION_BITS for 8-bit channels
 constexpr uint32_t IN_STREAM = 0x80000001u;      // Philox counter word 1 (augment.hip: 0x80000000; the sampler: < 1024)
 constexpr int IN_MAX_SIDE = 8192;                // 16.16 coordinates stay far inside int32

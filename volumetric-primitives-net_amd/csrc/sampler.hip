@@ -956,6 +956,14 @@ extern "C" int vpn_camera_transform_bwd(const float* grad_out, const float* dist
     return camera_launch(grad_out, dists, elevs, azims, angles, B, N, to_object, 1, grad_points, stream);
 }
 
+// dynamic LDS of sample_chamfer_bwd_kernel: the per-wave match lists, 8 B per GT point
+static constexpr size_t SCB_MAX_LDS = 60 * 1024;
+static constexpr size_t scb_match_lds(int M) {
+    return (size_t)((M + SCB_BLOCK - 1) / SCB_BLOCK) * 64 * (SCB_BLOCK / 64) * sizeof(int2);
+}
+static_assert(scb_match_lds(VPN_FUSED_BWD_MAX_GT) <= SCB_MAX_LDS && scb_match_lds(VPN_FUSED_BWD_MAX_GT + 1) > SCB_MAX_LDS,
+              "VPN_FUSED_BWD_MAX_GT is the largest M whose match lists fit");
+
 static int launch_scb(const float* params, const int32_t* kinds, const float* u, uint64_t seed,
                       const uint64_t* seed_dev, uint64_t sample_base, int B, int K, int n, const float* points,
                       const float* gt_points, int M, const float* dist1, const int32_t* idx1,
@@ -967,8 +975,8 @@ static int launch_scb(const float* params, const int32_t* kinds, const float* u,
     if (B <= 0 || K <= 0 || n <= 0 || M <= 0) return VPN_E_BADARG;
     if (B > 65535 || (long long)K * n > 0x7fffffffLL / 3) return VPN_E_TOOBIG;
     constexpr int BLK = SCB_BLOCK;
-    const size_t lds = (size_t)((M + BLK - 1) / BLK) * 64 * (BLK / 64) * sizeof(int2);  // = 8 B per GT point
-    if (lds > 60 * 1024) return VPN_E_TOOBIG;                           // 7680 GT points; beyond: vpn_chamfer_bwd + vpn_sample_bwd
+    const size_t lds = scb_match_lds(M);
+    if (lds > SCB_MAX_LDS) return VPN_E_TOOBIG;                         // M > VPN_FUSED_BWD_MAX_GT; beyond: vpn_chamfer_bwd + vpn_sample_bwd
     if (ex)
         VPN_LAUNCH_AS("sample_chamfer_bwd_kernel<step>", sample_chamfer_bwd_kernel<true>, dim3(K, B), dim3(BLK), lds, (hipStream_t)stream, params, kinds, u, seed,
                       seed_dev, sample_base, K, n, points, gt_points, M, dist1, idx1, dist2, idx2, grad_loss_b, w1, w2, grad_params, rf, *ex);

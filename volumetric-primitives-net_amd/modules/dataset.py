@@ -7,12 +7,9 @@ half (_load_sample_points, dataset.py:42-46,161-165, and genre.py:66-74): a ragg
 canonical and view-centred GT point sets in three launches (csrc/gtpoints.hip).  The dataset class itself
 (file discovery, OBJ parsing, PNG decoding) is out of scope; the device-side augmentations are in
 modules/augmentation.py."""
-import os
-import re
-
 import torch
 
-from .. import config, ops
+from .. import _lib, config, ops
 
 DIST_SCALE = 1.754                       # dataset.py:147: the stored camera distance is scaled by this factor
 IMAGENET_MEAN = (0.485, 0.456, 0.406)    # dataset.py:126
@@ -96,16 +93,7 @@ def prepare_images(rgba_u8: torch.Tensor, *, size=None, jitter=True, rotate=Fals
 
 # ---- the point half of __getitem__ (dataset.py:42-46,161-165; genre.py:66-74; csrc/gtpoints.hip)
 
-def _header_constant(name):
-    """An integer #define of include/vpn_hip.h: the one place a constant shared with the kernels is written."""
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..', 'include', 'vpn_hip.h')
-    m = re.search(r'^#define\s+%s\s+(\d+)\s*$' % name, open(path).read(), flags=re.M)
-    if m is None:
-        raise RuntimeError('%s is not defined in include/vpn_hip.h' % name)
-    return int(m.group(1))
-
-
-CHUNK = _header_constant('VPN_RAGGED_CHUNK')      # faces per chunk: one workgroup of ragged_chunk_kernel
+CHUNK = _lib.CONSTANTS['VPN_RAGGED_CHUNK']        # faces per chunk: one workgroup of ragged_chunk_kernel
 GT_POINT_NUM = 2048                               # dataset.py:165, genre.py:74
 INDEX_LIMIT = 0x7fffffff // 3                     # the kernels index 3 * (a vertex or face number) in int32
 

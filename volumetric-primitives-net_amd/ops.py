@@ -14,8 +14,8 @@ from torch.autograd import Function
 
 from . import _lib
 
-SPHERE, CUBOID = 0, 1
-PARAM_STRIDE = 10
+_H = _lib.CONSTANTS            # the #define VPN_* of include/vpn_hip.h: limits and flags are written there only
+SPHERE, CUBOID, PARAM_STRIDE = _H['VPN_SPHERE'], _H['VPN_CUBOID'], _H['VPN_PARAM_STRIDE']
 
 
 def _f32c(t):
@@ -732,7 +732,8 @@ class RasterTotalFunction(Function):
 
 TILE_ORDER = os.environ.get('VPN_TILE_ORDER', '1') != '0'     # 0: position-based launch order of the tile waves (A/B switch)
 _PATTERNS = {}
-FUSED_BWD_MAX_GT = 7680       # vpn_sample_chamfer_bwd keeps per-wave match lists of the GT points in LDS (include/vpn_hip.h)
+_RIDER_FITS = {}
+FUSED_BWD_MAX_GT = _H['VPN_FUSED_BWD_MAX_GT']      # vpn_sample_chamfer_bwd keeps per-wave match lists of the GT points in LDS
 _SIDE = {}
 # optionally run the raster branch of HotPathLossFunction on a second HIP stream (VPN_CONCURRENT=1)
 # TrainStepLossFunction: the auction on a second stream, beside the scans and the raster (measured at C5: 1.10 -> 0.94 ms per
@@ -767,12 +768,11 @@ def _grad_pattern(B, w_cd, dev):
 
 def _tile_rider_fits(K, H, W):
     """Whether the Chamfer scan's launch can carry the rider that tests the raster's 16 x 16 pixel tiles (R_TW, R_TH) against
-    the K primitives and sorts them by weight.  Restates the check of vpn_hotpath_chamfer_fwd in csrc/chamfer.hip, which
-    answers VPN_E_TOOBIG otherwise: K <= R_ORDER_MAX_PRIMS, tiles <= R_ORDER_MAX_TILES and raster_order_scratch(K, tiles)
-    (csrc/vpn_raster_common.h: K * (R_CULL * 16 + 4) + (K + 2) * 4 + tiles bytes) within the scan's 2 * CM_TILE16 * CM_ROWB bytes
-    of LDS.  TILE_ORDER = False (VPN_TILE_ORDER=0) turns the rider off."""
-    ntile = ((W + 15) // 16) * ((H + 15) // 16)
-    return TILE_ORDER and K <= 64 and ntile <= 16384 and K * 84 + (K + 2) * 4 + ntile <= 24576
+    the K primitives and sorts them by weight: the library's own answer (vpn_hotpath_chamfer_fwd returns VPN_E_TOOBIG where
+    this is False), asked once per shape.  TILE_ORDER = False (VPN_TILE_ORDER=0) turns the rider off."""
+    if (K, H, W) not in _RIDER_FITS:
+        _RIDER_FITS[K, H, W] = _lib.lib().vpn_hotpath_tile_rider_fits(K, H, W) == 1
+    return TILE_ORDER and _RIDER_FITS[K, H, W]
 
 
 def _hotpath_sample(params, kinds, cam, gt_points, n, seed_host, seed_dev, sample_base, Hr, Wr, sigma, features, s):
@@ -1707,8 +1707,8 @@ def vis_primitives(params, kinds, cams, palette, H, W, *, ambient=1.0, backgroun
     params = _vis_f32('params', params, lambda t: t.dim() == 3 and t.size(2) == PARAM_STRIDE and t.size(0) > 0 and t.size(1) > 0, '[S,K,10]')
     S, K, _ = params.shape
     dev = params.device
-    if K > 512:
-        raise ValueError('K = %d primitives: the renderer stages at most 512 (VPN_VIS_MAX_PRIMS)' % K)
+    if K > _H['VPN_VIS_MAX_PRIMS']:
+        raise ValueError('K = %d primitives: the renderer stages at most %d (VPN_VIS_MAX_PRIMS)' % (K, _H['VPN_VIS_MAX_PRIMS']))
     if len(kinds) != K:
         raise ValueError('%d kinds for K = %d primitives' % (len(kinds), K))
     palette = _vis_f32('palette', palette, lambda t: t.dim() == 2 and t.size(1) == 3, '[>= K,3]')
@@ -1807,8 +1807,8 @@ def phong_mesh(verts, faces, uv, texture, cams, H, W, *, light, material, shinin
 # ---- the image input stage (csrc/input.hip): dataset.py:15-19,115-139 of the reference -- Resize,
 # ColorJitter, ToTensor, the rotation, the rgb / silhouette split, Normalize -- bit-exact to PIL.  Data, no backward.
 
-INPUT_JITTER, INPUT_ROTATE, INPUT_NORMALIZE = 1, 2, 4
-INPUT_TILE_ROWS = 8                       # IN_TH of csrc/input.hip
+INPUT_JITTER, INPUT_ROTATE, INPUT_NORMALIZE = _H['VPN_INPUT_JITTER'], _H['VPN_INPUT_ROTATE'], _H['VPN_INPUT_NORMALIZE']
+INPUT_TILE_ROWS = _H['VPN_INPUT_TILE_ROWS']         # output rows per tile of the resize kernel
 _INPUT_TABLES = {}
 
 
@@ -1911,7 +1911,7 @@ def prepare_images(rgba_u8, H, W, *, jitter=True, rotate=False, normalize=False,
 # ---- the ground-truth stage (csrc/gtpoints.hip): dataset.py:161-165 for a ragged batch of meshes.  Data: no
 # autograd node.
 
-RAGGED_MAX_SETS = 16         # VPN_RAGGED_MAX_SETS
+RAGGED_MAX_SETS = _H['VPN_RAGGED_MAX_SETS']
 RAGGED_LAUNCHES = 3          # chunk scan, chunk bases, sampling: whatever the number of meshes
 
 
