@@ -154,6 +154,8 @@ def main():
     ap.add_argument('--cuboids', type=int, default=0)         # the first C primitives are cuboids (config.py:33)
     ap.add_argument('--sample-num', type=int, default=128)    # config.py:8
     ap.add_argument('--size', type=int, default=None)         # hip_loss: 256; trainstep: 128 (config.py:49)
+    ap.add_argument('--optimizer', default='torch', choices=('torch', 'hip'),
+                    help='hip: vpn_amd.Adam (one launch per step, csrc/optim.hip) with the reference\'s betas (0.9, 0.99)')
     args = ap.parse_args()
     trainstep = args.loss == 'trainstep'
     K = args.prims or (16 if trainstep else 64)
@@ -175,12 +177,17 @@ def main():
         else:
             dist.init_process_group('nccl', rank=rank, world_size=world, device_id=dev)    # RCCL over xGMI
 
+    def hip_adam(params):
+        import vpn_amd
+        return vpn_amd.Adam(params, lr=1e-3, betas=(0.9, 0.99))                     # train.py:83
+
     def log(it, loss):
         if rank == 0:
             print('step %3d  local loss %.5f' % (it, float(loss.detach())), flush=True)
     run(rank, world, dev, trainstep_loss if trainstep else hip_loss, steps=args.steps, global_batch=args.global_batch, K=K,
         feat=64, sample_num=args.sample_num, M=K * args.sample_num if trainstep else 2048, size=size, lr=1e-3, log=log,
-        batch_fn=make_trainstep_batch if trainstep else None, cuboids=args.cuboids)
+        batch_fn=make_trainstep_batch if trainstep else None, cuboids=args.cuboids,
+        make_optimizer=hip_adam if args.optimizer == 'hip' else None)
     if trainstep and rank == 0:
         import vpn_amd
         print('EMD samples recomputed by the auction (workgroups not co-resident): %d' % vpn_amd.emd_recovered_samples(),

@@ -70,6 +70,8 @@ def main(argv=None):
     ap.add_argument('--lr', type=float, default=1e-5)
     ap.add_argument('--net', default='standin', choices=('standin', 'vpnet_oneres'))
     ap.add_argument('--vpn', default=None, help='a VPNetOneRes state_dict saved by the reference (implies --net vpnet_oneres)')
+    ap.add_argument('--optimizer', default='torch', choices=('torch', 'hip'),
+                    help='hip: vpn_amd.Adam (one launch per step, csrc/optim.hip) with the reference\'s betas (0.9, 0.99)')
     args = ap.parse_args(argv)
     dev = torch.device('cuda')
     torch.manual_seed(1234)
@@ -81,7 +83,8 @@ def main(argv=None):
     else:
         vpn = StandInVPN().to(dev).eval()
     gcn = GCNModel().to(dev)
-    optimizer = torch.optim.Adam(params=gcn.parameters(), lr=args.lr, betas=(0.9, 0.99), weight_decay=1e-6)
+    adam = vpn_amd.Adam if args.optimizer == 'hip' else torch.optim.Adam
+    optimizer = adam(params=gcn.parameters(), lr=args.lr, betas=(0.9, 0.99), weight_decay=1e-6)      # train_gcn.py:105
     cd_loss_func = vpn_amd.ChamferDistanceLoss()
     B = args.batch
     losses = []

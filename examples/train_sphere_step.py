@@ -88,13 +88,18 @@ if __name__ == '__main__':
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--obj', default=None)
     ap.add_argument('--net', default='standin', choices=('standin', 'sdnet'))
+    ap.add_argument('--optimizer', default='torch', choices=('torch', 'hip'),
+                    help='hip: vpn_amd.Adam (one launch per step, csrc/optim.hip) with the reference\'s betas (0.9, 0.99)')
     args = ap.parse_args()
     dev = torch.device('cuda')
     torch.manual_seed(0)
     batch = make_batch(4, 2048, 64, dev)                              # BASELINE config C1: batch 4, 64 x 64
     P = vpn_amd.load_obj(args.obj)[0].shape[0] if args.obj else 288
     net = (vpn_amd.SDNet(vertex_num=P) if args.net == 'sdnet' else Offsets(64, P)).to(dev)
-    opt = torch.optim.Adam(net.parameters(), lr=2e-3)
+    if args.optimizer == 'hip':
+        opt = vpn_amd.Adam(net.parameters(), lr=2e-3, betas=(0.9, 0.99))            # train_sphere.py:92
+    else:
+        opt = torch.optim.Adam(net.parameters(), lr=2e-3)
     for it in range(args.steps):
         opt.zero_grad()
         total, parts = training_losses(net, *batch, 1024, 1.0, args.obj)

@@ -1,6 +1,6 @@
 """A training step of the reference (train.py:221-268) on the drop-in surface, with a stand-in network.
 
-    python examples/train_step.py [--steps 20] [--net standin|vpnet_oneres|vpnet_twores]
+    python examples/train_step.py [--steps 20] [--net standin|vpnet_oneres|vpnet_twores] [--optimizer torch|hip]
 
 By default a two-layer MLP on a random feature vector produces the three head outputs (volumes [B,3K], rotates [B,4K],
 translates [B,3K]); --net vpnet_oneres / vpnet_twores trains the reference's network instead (modules/network.py: a
@@ -141,6 +141,8 @@ def main():
     ap.add_argument('--net', default='standin', choices=('standin', 'vpnet_oneres', 'vpnet_twores'))
     ap.add_argument('--fused', action='store_true', help='the whole loss as one autograd node (TrainStepLossFunction)')
     ap.add_argument('--augment', default='', help='comma-separated subset of rotate,cutmix,mixup,pointmixup,acdmix (config.py AUGMENT_3D; default: none)')
+    ap.add_argument('--optimizer', default='torch', choices=('torch', 'hip'),
+                    help='hip: vpn_amd.Adam (one launch per step, csrc/optim.hip) with the reference\'s betas (0.9, 0.99)')
     args = ap.parse_args()
     augment = [a for a in args.augment.split(',') if a]
     assert set(augment) <= {'rotate', 'cutmix', 'mixup', 'pointmixup', 'acdmix'}, augment
@@ -150,7 +152,10 @@ def main():
     batch = make_batch(args.batch, args.prims, args.sample_num, args.size, dev)
     net = {'standin': lambda: Heads(64, args.prims), 'vpnet_oneres': lambda: vpn_amd.VPNetOneRes(vp_num=args.prims),
            'vpnet_twores': lambda: vpn_amd.VPNetTwoRes(vp_num=args.prims)}[args.net]().to(dev)
-    opt = torch.optim.Adam(net.parameters(), lr=1e-3)
+    if args.optimizer == 'hip':
+        opt = vpn_amd.Adam(net.parameters(), lr=1e-3, betas=(0.9, 0.99))                # train.py:83
+    else:
+        opt = torch.optim.Adam(net.parameters(), lr=1e-3)
     weights = (1.0, 1.0, 1.0, 0.1, 1.0)
     for it in range(args.steps):
         opt.zero_grad()

@@ -832,6 +832,47 @@ int vpn_fc_stack_bwd(VpnFcStack stack, VpnFcGrad grad, int dropout, float p, uin
                      int epilogue, int K, int is_sigmoid, float clamp_min, float clamp_max, float restrict0, float restrict1, float restrict2,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the optimiser stage (csrc/optim.hip; train.py:83-102 `Adam(params, lr, betas=(0.9, 0.99), weight_decay=W_DECAY)` and
+ * train.py:264 `optimizer.step()` of the reference, the same two lines at train_sphere.py:92 / :134 and train_gcn.py:105 /
+ * :138): Adam with torch's L2 weight decay over all parameters of one group in ONE plain launch, the step
+ * counter and the bias-correction products on the device, gradient zeroing (optimizer.zero_grad(), train.py:262) folded into
+ * the same pass.  No host synchronisation, nothing allocated, no second launch, no pow on the device; replayed from a
+ * captured graph every replay is a fresh step.  Added without a change of VPN_ABI_VERSION.
+ *   segments [S] VpnAdamSegment (DEVICE): one row per parameter that has a gradient: p, g, m, v [n] fp32 each; vec != 0:
+ *     the four pointers are 16-byte aligned and the kernel uses 16-byte accesses (the caller decides, as below).
+ *   chunks [C,2] int64 (DEVICE) = (segment, first element): one row per workgroup, which updates the elements [first,
+ *     min(first + VPN_ADAM_CHUNK, n)) of that segment; first is a multiple of VPN_ADAM_CHUNK.  Both are clamped into the
+ *     tables on the device (a bad row updates nothing and still arrives).
+ *   state (DEVICE, VPN_ADAM_STATE_BYTES, 8-byte aligned) = {int64 step, double b1pow, double b2pow, uint32 arrivals, pad},
+ *     {0, 1.0, 1.0, 0} before the first step.  Every workgroup reads it; the one that arrives last writes {step + 1,
+ *     b1pow * beta1, b2pow * beta2, 0}.
+ *   hyper (HOST, read before the call returns) = {lr, beta1, beta2, eps, weight_decay} as doubles (a pointer, because the
+ *     binding passes no double by value); lr_dev: NULL, or a DEVICE float that the kernel reads INSTEAD of hyper[0]: a
+ *     schedule written on the device, which a captured graph follows.
+ *   arithmetic (the specification; tests/optim_ref.py restates it bit for bit): in double B1 = b1pow * beta1, B2 = b2pow *
+ *     beta2, c1 = (float)(1 - beta1), c2 = (float)(1 - beta2), b2f = (float)beta2, wdf = (float)wd, epsf = (float)eps,
+ *     bc2s = (float)sqrt(1 - B2), nss = (float)(-(lr / (1 - B1))); per element, fp32, every operation rounded by itself,
+ *     IEEE sqrt and divide: g1 = wd != 0 ? g + wdf * p : g; m' = m + c1 * (g1 - m); v' = v * b2f + c2 * (g1 * g1);
+ *     den = sqrt(v') / bc2s + epsf; p' = p + nss * (m' / den); zero_grads != 0: g = 0.  Non-finite values propagate.
+ *   num_segments == 0: success, nothing is launched, the state does not advance.  Null pointers, num_chunks <= 0,
+ *   misaligned tables or state, betas outside [0, 1), a negative or non-finite eps / weight_decay / lr: VPN_E_BADARG, before
+ *   any HIP call. */
+#define VPN_ADAM_CHUNK 4096            /* elements per workgroup: 256 lanes x 4 accesses of 16 bytes per array */
+#define VPN_ADAM_STATE_BYTES 32
+typedef struct VpnAdamSegment {
+    float* p;
+    float* g;
+    float* m;
+    float* v;
+    long long n;
+    long long vec;
+} VpnAdamSegment;
+/* bytes of a table for `segments` rows and `elements` parameters in all: segments * sizeof(VpnAdamSegment) + 16 * (elements /
+ * VPN_ADAM_CHUNK + segments), the most chunk rows they can have; 0 for a negative argument */
+size_t vpn_adam_table_bytes(int segments, long long elements);
+int vpn_adam_step(const VpnAdamSegment* segments, int num_segments, const long long* chunks, int num_chunks, void* state,
+                  const double* hyper, const float* lr_dev, int zero_grads, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,3 +18,5 @@ from . import evaluation
 from .evaluation import EvaluationMeter
 from . import visualize
 from .visualize import Visualizer
+from . import optim
+from .optim import Adam

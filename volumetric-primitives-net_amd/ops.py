@@ -1962,3 +1962,35 @@ def ragged_sample(verts, faces, vert_offset, face_offset, chunk_offset, chunks, 
     _lib.call('vpn_ragged_sample', verts, faces, vert_offset, face_offset, chunk_offset, chunks, xforms, mask, u, seed_host, seed_ptr,
               int(mesh_base), S, T, n, sumP, sumF, C, ws, ws.numel() * 8, points, fidx, bary, _lib.stream())
     return (points, fidx, bary) if return_faces else points
+
+
+# ---- the optimiser stage (csrc/optim.hip): train.py:83-102 Adam(...) and :264 optimizer.step().  The
+# parameters are updated in place: no autograd node.
+
+ADAM_CHUNK = _H['VPN_ADAM_CHUNK']        # elements per workgroup of adam_step_kernel; the chunk table is cut with it
+
+
+def adam_tables(entries):
+    """The two tables of vpn_adam_step from `entries` = (p, g, m, v, n) per parameter, the first four as addresses (ints);
+    an entry whose g is None (a parameter without a gradient) gets no rows.  Returns (segments, chunks): segments rows
+    (p, g, m, v, n, vec) with vec = 1 where the four addresses are 16-byte aligned (the kernel then uses 16-byte accesses:
+    a chunk starts a multiple of ADAM_CHUNK elements into the segment, so the alignment holds at every chunk's start),
+    chunks rows (segment, first element), every segment tiled in order by chunks of ADAM_CHUNK elements; an empty segment
+    keeps its row and gets no chunk.  Host arithmetic only: no GPU needed."""
+    segments, chunks = [], []
+    for p, g, m, v, n in entries:
+        if g is None:
+            continue
+        vec = int(all(a % 16 == 0 for a in (p, g, m, v)))
+        chunks.extend((len(segments), first) for first in range(0, int(n), ADAM_CHUNK))
+        segments.append((int(p), int(g), int(m), int(v), int(n), vec))
+    return segments, chunks
+
+
+def adam_step(segments, num_segments, chunks, num_chunks, state, lr, lr_dev, beta1, beta2, eps, weight_decay, zero_grads=False):
+    """vpn_adam_step on the current stream: segments / chunks are the DEVICE int64 tables of adam_tables (6 and 2 words a
+    row), state the group's device block (VPN_ADAM_STATE_BYTES), lr_dev None or a one-element fp32 device tensor read
+    instead of lr.  One launch, no host synchronisation; zero segments: nothing is launched."""
+    hyper = (ctypes.c_double * 5)(lr, beta1, beta2, eps, weight_decay)
+    _lib.call('vpn_adam_step', segments, int(num_segments), chunks, int(num_chunks), state, hyper, lr_dev, int(bool(zero_grads)),
+              _lib.stream())
