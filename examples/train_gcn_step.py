@@ -72,11 +72,13 @@ def main(argv=None):
     ap.add_argument('--vpn', default=None, help='a VPNetOneRes state_dict saved by the reference (implies --net vpnet_oneres)')
     ap.add_argument('--optimizer', default='torch', choices=('torch', 'hip'),
                     help='hip: vpn_amd.Adam (one launch per step, csrc/optim.hip) with the reference\'s betas (0.9, 0.99)')
+    ap.add_argument('--trunk-norm', default='torch', choices=('torch', 'hip'),
+                    help='hip: the ResNet-18 trunk runs each batch norm with its residual add and ReLU as one op (csrc/trunknorm.hip)')
     args = ap.parse_args(argv)
     dev = torch.device('cuda')
     torch.manual_seed(1234)
     if args.vpn or args.net == 'vpnet_oneres':
-        vpn = vpn_amd.VPNetOneRes(vp_num=VP_NUM)
+        vpn = vpn_amd.VPNetOneRes(vp_num=VP_NUM, trunk=vpn_amd.ResNet18(fused_norm=True) if args.trunk_norm == 'hip' else None)
         if args.vpn:
             vpn.load_state_dict(torch.load(args.vpn, map_location='cpu'))
         vpn = vpn.to(dev).eval()

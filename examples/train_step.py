@@ -1,6 +1,6 @@
 """A training step of the reference (train.py:221-268) on the drop-in surface, with a stand-in network.
 
-    python examples/train_step.py [--steps 20] [--net standin|vpnet_oneres|vpnet_twores] [--optimizer torch|hip]
+    python examples/train_step.py [--steps 20] [--net standin|vpnet_oneres|vpnet_twores] [--optimizer torch|hip] [--trunk-norm torch|hip]
 
 By default a two-layer MLP on a random feature vector produces the three head outputs (volumes [B,3K], rotates [B,4K],
 translates [B,3K]); --net vpnet_oneres / vpnet_twores trains the reference's network instead (modules/network.py: a
@@ -143,6 +143,8 @@ def main():
     ap.add_argument('--augment', default='', help='comma-separated subset of rotate,cutmix,mixup,pointmixup,acdmix (config.py AUGMENT_3D; default: none)')
     ap.add_argument('--optimizer', default='torch', choices=('torch', 'hip'),
                     help='hip: vpn_amd.Adam (one launch per step, csrc/optim.hip) with the reference\'s betas (0.9, 0.99)')
+    ap.add_argument('--trunk-norm', default='torch', choices=('torch', 'hip'),
+                    help='hip: the ResNet-18 trunk runs each batch norm with its residual add and ReLU as one op (csrc/trunknorm.hip)')
     args = ap.parse_args()
     augment = [a for a in args.augment.split(',') if a]
     assert set(augment) <= {'rotate', 'cutmix', 'mixup', 'pointmixup', 'acdmix'}, augment
@@ -150,8 +152,11 @@ def main():
     dev = torch.device('cuda')
     torch.manual_seed(1234)
     batch = make_batch(args.batch, args.prims, args.sample_num, args.size, dev)
-    net = {'standin': lambda: Heads(64, args.prims), 'vpnet_oneres': lambda: vpn_amd.VPNetOneRes(vp_num=args.prims),
-           'vpnet_twores': lambda: vpn_amd.VPNetTwoRes(vp_num=args.prims)}[args.net]().to(dev)
+
+    def trunk():           # None: the model builds its own plain trunk, as it always did
+        return vpn_amd.ResNet18(fused_norm=True) if args.trunk_norm == 'hip' else None
+    net = {'standin': lambda: Heads(64, args.prims), 'vpnet_oneres': lambda: vpn_amd.VPNetOneRes(vp_num=args.prims, trunk=trunk()),
+           'vpnet_twores': lambda: vpn_amd.VPNetTwoRes(vp_num=args.prims, trunk=(trunk(), trunk()) if args.trunk_norm == 'hip' else None)}[args.net]().to(dev)
     if args.optimizer == 'hip':
         opt = vpn_amd.Adam(net.parameters(), lr=1e-3, betas=(0.9, 0.99))                # train.py:83
     else:

@@ -873,6 +873,44 @@ size_t vpn_adam_table_bytes(int segments, long long elements);
 int vpn_adam_step(const VpnAdamSegment* segments, int num_segments, const long long* chunks, int num_chunks, void* state,
                   const double* hyper, const float* lr_dev, int zero_grads, void* stream);
 
+/* ---- the trunk's norm / add / ReLU ring (csrc/trunknorm.hip; the torchvision ResNet-18 of vpnet_one_resnet.py:21,
+ * vpnet_two_resnet.py:21-22 and sdnet.py:13 of the reference): batch norm over (B, H, W) per channel, then
+ * `+ residual`, then ReLU, as ONE op forward and backward.  All tensors DEVICE fp32, NCHW contiguous, 4-byte aligned; the
+ * kernels use 16-byte accesses when H * W is a multiple of 4 and every [B,C,H,W] pointer of the call is 16-byte aligned,
+ * element accesses otherwise (decided per call, no error).  N = B * H * W elements per channel.  No host synchronisation,
+ * nothing allocated, no atomics: bit-equal from run to run, capturable.  Added without a change of VPN_ABI_VERSION
+ * (DESIGN.md 4.10).
+ *   N <= VPN_BN_ONE_PASS_MAX: one launch per call, no workspace (workspace may be NULL).  Larger N: two launches over
+ *   slices of VPN_BN_SLICE elements and a workspace of vpn_bn_act_workspace(B, C, H, W) bytes (4-byte aligned,
+ *   uninitialised: C * ceil(N / VPN_BN_SLICE) * 2 floats), 0 bytes in the one-launch case.
+ * vpn_bn_act_fwd, training != 0: mean, biased var, invstd = 1 / sqrt(var + eps) per channel (exact-mean second pass, Chan's
+ *   merge of the slices: no E[x^2] - E[x]^2); y = (x - mean) * invstd * weight + bias, + residual when residual != NULL,
+ *   max(., 0) when relu != 0; save_mean [C], save_invstd [C] written; running_mean / running_var [C] (each may be NULL)
+ *   updated in place as (1 - momentum) * r + momentum * stat, the variance unbiased by N / (N - 1); num_batches_tracked
+ *   (int64, may be NULL) incremented by one.  training == 0: the running statistics are read, one elementwise launch,
+ *   save_mean / save_invstd / num_batches_tracked / workspace are not touched (may be NULL).
+ *   weight, bias: [C] or NULL (1 and 0).  y must not alias x or residual.
+ * vpn_bn_act_bwd: g = dy * [y > 0] when relu != 0 (y: the forward's output; NULL allowed when relu == 0), else g = dy.
+ *   training != 0: stat_mean / stat_var = save_mean / save_invstd of the forward; d_bias = sum g, d_weight = sum g * xhat,
+ *   dx = weight * invstd * (g - d_bias / N - xhat * d_weight / N).  training == 0: stat_mean / stat_var = running_mean /
+ *   running_var, dx = g * weight / sqrt(running_var + eps), the two sums only when d_weight or d_bias is wanted.
+ *   d_residual = g.  dx, d_residual, d_weight, d_bias: each may be NULL and is then neither computed nor written (dx still
+ *   uses both sums); all four NULL: nothing is launched.  The workspace is needed when N > VPN_BN_ONE_PASS_MAX unless
+ *   training == 0 and d_residual, d_weight and d_bias are all NULL.
+ * Non-positive sizes, a required pointer that is NULL, N == 1 in training, eps < 0, momentum outside [0, 1], a workspace
+ * that is missing, too small or misaligned: VPN_E_BADARG.  N >= 2^31 or more than 65535 slices: VPN_E_TOOBIG.  Both before
+ * any HIP call. */
+#define VPN_BN_ONE_PASS_MAX 8192       /* floats of a channel held in LDS: 32 KB forward, 64 KB backward (g and xhat) */
+#define VPN_BN_SLICE 2048              /* elements per workgroup in the two-launch regime: 256 lanes x 8 */
+size_t vpn_bn_act_workspace(int B, int C, int H, int W);
+int vpn_bn_act_fwd(const float* x, const float* residual, const float* weight, const float* bias, float* running_mean,
+                   float* running_var, long long* num_batches_tracked, int B, int C, int H, int W, int training, float momentum,
+                   float eps, int relu, float* y, float* save_mean, float* save_invstd, void* workspace, size_t workspace_bytes,
+                   void* stream);
+int vpn_bn_act_bwd(const float* dy, const float* x, const float* y, const float* weight, const float* stat_mean,
+                   const float* stat_var, int B, int C, int H, int W, int training, float eps, int relu, float* dx,
+                   float* d_residual, float* d_weight, float* d_bias, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

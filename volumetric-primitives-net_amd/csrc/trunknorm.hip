@@ -1,0 +1,510 @@
+// trunknorm.hip — the trunk's norm / add / ReLU ring (gfx950): batch norm, the residual add and the ReLU of a ResNet-18
+// site as ONE op, forward and backward.
+//
+// Replaces, around the convolutions of the reference's torchvision trunk (vpnet_one_resnet.py:21, vpnet_two_resnet.py:21-22,
+// sdnet.py:13), `relu(bn1(.))`, `bn2(.)`, `out += identity; relu(out)` and the downsample branch's norm: 20 training-mode
+// batch norms, 17 ReLUs and 8 adds, each its own ATen kernel forward and again backward.  NCHW contiguous, fp32.
+//   * statistics by an exact-mean second pass over values kept on chip (LDS in the one-pass regime, registers in a slice of
+//     the split regime), slices merged by Chan's (count, mean, M2) rule around their exact mean: never E[x^2] - E[x]^2;
+//   * two regimes chosen on the host from N = B H W.  N <= VPN_BN_ONE_PASS_MAX: one workgroup owns a channel, its slab
+//     stays in LDS between the statistics and the normalisation, ONE launch, x read once.  Larger N: grid (C, S) with S
+//     slices of VPN_BN_SLICE elements per channel; launch 1 writes per-slice partials, in launch 2 the first wave of every
+//     workgroup of a channel merges the S partials in the same order (the same value everywhere: no atomics, no grid
+//     barrier) and the workgroup normalises its slice;
+//   * an element is addressed as (channel, batch row, offset): one division per work-item, then additions; 16-byte accesses
+//     where the host found H W a multiple of 4 and every pointer 16-byte aligned, element accesses with the same indexing
+//     otherwise;
+//   * one summation order (per work-item in index order, then the wave's butterfly, then the waves in order; the
+//     slices lane-strided, then the butterfly): bit-equal from run to run; no float atomics, no host synchronisation, nothing allocated;
+//   * save_mean / save_invstd, the running statistics and the int64 batch counter are written by ONE work-item per channel
+//     of the launch that knows the statistics.
+#include "vpn_common.h"
+
+namespace vpn {
+
+constexpr int TN_MAX = VPN_BN_ONE_PASS_MAX;     // floats of a channel's slab held in LDS by the one-pass kernels
+constexpr int TN_SLICE = VPN_BN_SLICE;          // elements of a slice of the split regime
+constexpr int TN_BLOCK = 256;
+constexpr int TN_PER = TN_SLICE / TN_BLOCK;     // elements a work-item holds in registers in tn_stats_kernel
+constexpr int TN_SMALL = 512;                   // N up to here: one wave owns the channel
+static_assert(TN_PER * TN_BLOCK == TN_SLICE && TN_PER % 4 == 0 && TN_MAX % 4 == 0 && TN_SMALL % 4 == 0 && TN_SMALL <= TN_MAX, "a slice is TN_PER elements per work-item");
+
+// N = B HW elements per channel; in units of V floats (V = 4: 16-byte accesses, V = 1: elements): RU units per batch row,
+// NU units per channel; step_b / step_i: the block size in units as (rows, units) = divmod(block, RU), formed on the host
+struct TnShape { int C, HW, N, RU, NU, step_b, step_i, S; };
+
+struct TnFwd {
+    const float *x, *res, *w, *b;
+    float *rm, *rv; long long* nbt;
+    float *y, *save_mean, *save_invstd;
+    float* ws;                     // split regime: [C, S, 2] (mean, M2) of every slice; NULL in tn_fwd_apply_kernel: eval
+    float momentum, eps; int relu;
+};
+
+struct TnBwd {
+    const float *dy, *x, *y, *w, *stat_a, *stat_b;       // y: NULL without ReLU; stat_b: invstd, or the running variance (eval)
+    float *dx, *dres, *dw, *db;                          // each may be NULL: not wanted
+    float* ws;                                           // split regime: [C, S, 2] (sum g, sum g xhat) of every slice
+    float eps; int eval, sums;                           // sums: the apply kernel merges the partials
+};
+
+template <int V> struct Vec { float v[V]; };
+template <int V> __device__ inline Vec<V> ldv(const float* p);
+template <> __device__ inline Vec<1> ldv<1>(const float* p) { Vec<1> r; r.v[0] = p[0]; return r; }
+template <> __device__ inline Vec<4> ldv<4>(const float* p) {
+    const float4 q = *reinterpret_cast<const float4*>(p);
+    Vec<4> r; r.v[0] = q.x; r.v[1] = q.y; r.v[2] = q.z; r.v[3] = q.w; return r;
+}
+template <int V> __device__ inline void stv(float* p, const Vec<V>& r);
+template <> __device__ inline void stv<1>(float* p, const Vec<1>& r) { p[0] = r.v[0]; }
+template <> __device__ inline void stv<4>(float* p, const Vec<4>& r) {
+    float4 q; q.x = r.v[0]; q.y = r.v[1]; q.z = r.v[2]; q.w = r.v[3];
+    *reinterpret_cast<float4*>(p) = q;
+}
+
+// (batch row, unit in the row) of a unit of a channel, advanced by a fixed stride without a division
+struct TnWalk {
+    int b, i;
+    __device__ inline TnWalk(int u, int RU) { b = u / RU; i = u - b * RU; }
+    __device__ inline void step(const TnShape& s) { b += s.step_b; i += s.step_i; if (i >= s.RU) { i -= s.RU; ++b; } }
+    template <int V> __device__ inline size_t at(const TnShape& s) const { return (size_t)b * s.C * s.HW + (size_t)i * V; }
+};
+
+// the sums of a and b over the workgroup, in every work-item: butterfly in the wave, then the waves in order
+template <int BLOCK> __device__ inline void block_sum2(float& a, float& b, float* red) {
+    a = wave_sum(a); b = wave_sum(b);
+    if (BLOCK > 64) {
+        const int w = threadIdx.x >> 6;
+        __syncthreads();                      // the previous reduction's values have been read
+        if ((threadIdx.x & 63) == 0) { red[2 * w] = a; red[2 * w + 1] = b; }
+        __syncthreads();
+        a = 0.0f; b = 0.0f;
+#pragma unroll
+        for (int i = 0; i < BLOCK / 64; ++i) { a += red[2 * i]; b += red[2 * i + 1]; }
+    }
+}
+
+__device__ inline double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// what one work-item per channel writes once the statistics are known
+__device__ inline void tn_publish(const TnFwd& a, int c, int N, float mean, float var, float invstd) {
+    a.save_mean[c] = mean;
+    a.save_invstd[c] = invstd;
+    if (a.rm) a.rm[c] = (1.0f - a.momentum) * a.rm[c] + a.momentum * mean;
+    if (a.rv) a.rv[c] = (1.0f - a.momentum) * a.rv[c] + a.momentum * (var * ((float)N / (float)(N - 1)));
+    if (a.nbt && c == 0) a.nbt[0] += 1;
+}
+
+__device__ inline float tn_act(float x, float mean, float invstd, float gamma, float beta) {
+    return (x - mean) * invstd * gamma + beta;
+}
+
+// ---- forward, one-pass regime: grid C, one workgroup (BLOCK = 64: one wave) per channel.  A work-item reads back from
+// LDS only what it wrote itself, so the slab needs no barrier.
+template <int BLOCK, int V>
+__global__ __launch_bounds__(BLOCK) void tn_fwd_onepass_kernel(TnShape s, TnFwd a) {
+    constexpr int SLAB = BLOCK == 64 ? TN_SMALL : TN_MAX;      // the one-wave form leaves the CU's LDS to other workgroups
+    __shared__ __attribute__((aligned(16))) float slab[SLAB];
+    __shared__ float red[2 * (TN_BLOCK / 64)];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    if (s.N > SLAB) return;                         // the host never asks: nothing outside the slab either way
+    const size_t chan = (size_t)c * s.HW;
+    float sum = 0.0f, m2 = 0.0f;
+    {
+        TnWalk k(tid, s.RU);
+        for (int u = tid; u < s.NU; u += BLOCK, k.step(s)) {
+            const Vec<V> r = ldv<V>(a.x + chan + k.at<V>(s));
+            stv<V>(slab + (size_t)u * V, r);
+#pragma unroll
+            for (int j = 0; j < V; ++j) sum += r.v[j];
+        }
+    }
+    block_sum2<BLOCK>(sum, m2, red);
+    // second pass around the first mean: the sum of the differences corrects the mean's own rounding (and M2 with it)
+    const float mean0 = sum / (float)s.N;
+    float rs = 0.0f;
+    m2 = 0.0f;
+    for (int u = tid; u < s.NU; u += BLOCK) {
+        const Vec<V> r = ldv<V>(slab + (size_t)u * V);
+#pragma unroll
+        for (int j = 0; j < V; ++j) { const float d = r.v[j] - mean0; rs += d; m2 += d * d; }
+    }
+    block_sum2<BLOCK>(rs, m2, red);
+    const float dm = rs / (float)s.N;
+    const float mean = mean0 + dm;
+    const float var = fmaxf(m2 - rs * dm, 0.0f) / (float)s.N;
+    const float invstd = 1.0f / sqrtf(var + a.eps);
+    if (tid == 0) tn_publish(a, c, s.N, mean, var, invstd);
+    const float gamma = a.w ? a.w[c] : 1.0f, beta = a.b ? a.b[c] : 0.0f;
+    TnWalk k(tid, s.RU);
+    for (int u = tid; u < s.NU; u += BLOCK, k.step(s)) {
+        const size_t e = chan + k.at<V>(s);
+        Vec<V> r = ldv<V>(slab + (size_t)u * V);
+        Vec<V> q = {};
+        if (a.res) q = ldv<V>(a.res + e);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            float y = tn_act(r.v[j], mean, invstd, gamma, beta);
+            if (a.res) y += q.v[j];
+            r.v[j] = a.relu ? fmaxf(y, 0.0f) : y;
+        }
+        stv<V>(a.y + e, r);
+    }
+}
+
+// ---- forward, split regime, launch 1: grid (C, S); the slice stays in registers between its mean and its M2
+template <int V>
+__global__ __launch_bounds__(TN_BLOCK) void tn_stats_kernel(TnShape s, TnFwd a) {
+    __shared__ float red[2 * (TN_BLOCK / 64)];
+    const int c = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
+    constexpr int SU = TN_SLICE / V, PER = TN_PER / V;
+    const int u0 = sl * SU, u1 = u0 + SU < s.NU ? u0 + SU : s.NU;
+    if (sl >= s.S || u0 >= s.NU) return;
+    const size_t chan = (size_t)c * s.HW;
+    float r[TN_PER];
+    float sum = 0.0f, m2 = 0.0f;
+    TnWalk k(u0 + tid, s.RU);
+#pragma unroll
+    for (int p = 0; p < PER; ++p, k.step(s)) {
+        const bool in = u0 + tid + p * TN_BLOCK < u1;
+        Vec<V> q = {};
+        if (in) q = ldv<V>(a.x + chan + k.at<V>(s));
+#pragma unroll
+        for (int j = 0; j < V; ++j) { r[p * V + j] = in ? q.v[j] : 0.0f; sum += r[p * V + j]; }
+    }
+    block_sum2<TN_BLOCK>(sum, m2, red);
+    const float cnt = (float)((u1 - u0) * V);
+    const float mean0 = sum / cnt;
+    float rs = 0.0f;
+    m2 = 0.0f;
+#pragma unroll
+    for (int p = 0; p < PER; ++p) {
+        const bool in = u0 + tid + p * TN_BLOCK < u1;
+#pragma unroll
+        for (int j = 0; j < V; ++j) { const float d = in ? r[p * V + j] - mean0 : 0.0f; rs += d; m2 += d * d; }
+    }
+    block_sum2<TN_BLOCK>(rs, m2, red);
+    if (tid == 0) {
+        const float dm = rs / cnt;
+        a.ws[((size_t)c * s.S + sl) * 2] = mean0 + dm;
+        a.ws[((size_t)c * s.S + sl) * 2 + 1] = fmaxf(m2 - rs * dm, 0.0f);
+    }
+}
+
+// ---- forward, split regime launch 2 (a.ws: merge the partials) and the eval forward (a.ws == NULL: running statistics):
+// grid (C, S), every workgroup normalises its slice
+template <int V>
+__global__ __launch_bounds__(TN_BLOCK) void tn_fwd_apply_kernel(TnShape s, TnFwd a) {
+    const int c = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
+    constexpr int SU = TN_SLICE / V, PER = TN_PER / V;
+    const int u0 = sl * SU, u1 = u0 + SU < s.NU ? u0 + SU : s.NU;
+    if (sl >= s.S || u0 >= s.NU) return;
+    float mean, invstd;
+    if (a.ws) {
+        // the S partials (count, mean, M2) merged by the first wave, in double: lane l takes the slices l, l + 64, ... in
+        // order, then the wave's butterfly; first the mean, then M2 around it (Chan's rule with the exact mean: M2 =
+        // sum M2_i + n_i (mean_i - mean)^2).  The same order, so the same value, in every workgroup of the channel.
+        __shared__ double mrg[2];
+        if (tid < 64) {
+            const float* part = a.ws + (size_t)c * s.S * 2;
+            const double last = (double)(s.N - (s.S - 1) * TN_SLICE);
+            double A = 0.0;
+            for (int i = tid; i < s.S; i += 64) A += (i + 1 < s.S ? (double)TN_SLICE : last) * (double)part[2 * i];
+            const double m = wave_sum_d(A) / (double)s.N;
+            double Q = 0.0;
+            for (int i = tid; i < s.S; i += 64) {
+                const double d = (double)part[2 * i] - m;
+                Q += (double)part[2 * i + 1] + (i + 1 < s.S ? (double)TN_SLICE : last) * d * d;
+            }
+            Q = wave_sum_d(Q);
+            if (tid == 0) { mrg[0] = m; mrg[1] = Q; }
+        }
+        __syncthreads();
+        const double mu = mrg[0], M2 = mrg[1];
+        mean = (float)mu;
+        const float var = (float)(M2 / (double)s.N);
+        invstd = 1.0f / sqrtf(var + a.eps);
+        if (sl == 0 && tid == 0) tn_publish(a, c, s.N, mean, var, invstd);
+    } else {
+        mean = a.rm[c];
+        invstd = 1.0f / sqrtf(a.rv[c] + a.eps);
+    }
+    const float gamma = a.w ? a.w[c] : 1.0f, beta = a.b ? a.b[c] : 0.0f;
+    const size_t chan = (size_t)c * s.HW;
+    TnWalk k(u0 + tid, s.RU);
+    for (int p = 0; p < PER; ++p, k.step(s)) {
+        if (u0 + tid + p * TN_BLOCK >= u1) break;
+        const size_t e = chan + k.at<V>(s);
+        Vec<V> r = ldv<V>(a.x + e);
+        Vec<V> q = {};
+        if (a.res) q = ldv<V>(a.res + e);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            float y = tn_act(r.v[j], mean, invstd, gamma, beta);
+            if (a.res) y += q.v[j];
+            r.v[j] = a.relu ? fmaxf(y, 0.0f) : y;
+        }
+        stv<V>(a.y + e, r);
+    }
+}
+
+// g = dy [y > 0] (the mask from the saved output, ATen's threshold backward) and xhat of V elements
+template <int V>
+__device__ inline void tn_bwd_load(const TnBwd& a, size_t e, float mean, float invstd, Vec<V>& g, Vec<V>& xh) {
+    g = ldv<V>(a.dy + e);
+    xh = ldv<V>(a.x + e);
+    if (a.y) {
+        const Vec<V> y = ldv<V>(a.y + e);
+#pragma unroll
+        for (int j = 0; j < V; ++j) g.v[j] = y.v[j] <= 0.0f ? 0.0f : g.v[j];
+    }
+#pragma unroll
+    for (int j = 0; j < V; ++j) xh.v[j] = (xh.v[j] - mean) * invstd;
+}
+
+__device__ inline void tn_bwd_stats(const TnBwd& a, int c, float& mean, float& invstd) {
+    mean = a.stat_a[c];
+    invstd = a.eval ? 1.0f / sqrtf(a.stat_b[c] + a.eps) : a.stat_b[c];
+}
+
+// ---- backward, one-pass regime: grid C; g and xhat of the channel stay in LDS between the two sums and dx
+template <int BLOCK, int V>
+__global__ __launch_bounds__(BLOCK) void tn_bwd_onepass_kernel(TnShape s, TnBwd a) {
+    constexpr int SLAB = BLOCK == 64 ? TN_SMALL : TN_MAX;
+    __shared__ __attribute__((aligned(16))) float gs[SLAB];
+    __shared__ __attribute__((aligned(16))) float xs[SLAB];
+    __shared__ float red[2 * (TN_BLOCK / 64)];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    if (s.N > SLAB) return;
+    float mean, invstd;
+    tn_bwd_stats(a, c, mean, invstd);
+    const size_t chan = (size_t)c * s.HW;
+    float sg = 0.0f, sgx = 0.0f;
+    {
+        TnWalk k(tid, s.RU);
+        for (int u = tid; u < s.NU; u += BLOCK, k.step(s)) {
+            const size_t e = chan + k.at<V>(s);
+            Vec<V> g, xh;
+            tn_bwd_load<V>(a, e, mean, invstd, g, xh);
+            stv<V>(gs + (size_t)u * V, g);
+            stv<V>(xs + (size_t)u * V, xh);
+            if (a.dres) stv<V>(a.dres + e, g);
+#pragma unroll
+            for (int j = 0; j < V; ++j) { sg += g.v[j]; sgx += g.v[j] * xh.v[j]; }
+        }
+    }
+    block_sum2<BLOCK>(sg, sgx, red);
+    if (tid == 0) {
+        if (a.db) a.db[c] = sg;
+        if (a.dw) a.dw[c] = sgx;
+    }
+    if (!a.dx) return;
+    const float kk = (a.w ? a.w[c] : 1.0f) * invstd;
+    const float mg = a.eval ? 0.0f : sg / (float)s.N, mgx = a.eval ? 0.0f : sgx / (float)s.N;
+    TnWalk k(tid, s.RU);
+    for (int u = tid; u < s.NU; u += BLOCK, k.step(s)) {
+        Vec<V> g = ldv<V>(gs + (size_t)u * V);
+        const Vec<V> xh = ldv<V>(xs + (size_t)u * V);
+#pragma unroll
+        for (int j = 0; j < V; ++j) g.v[j] = kk * (g.v[j] - mg - xh.v[j] * mgx);
+        stv<V>(a.dx + chan + k.at<V>(s), g);
+    }
+}
+
+// ---- backward, split regime launch 1: grid (C, S); the two sums of a slice, and d_residual = g
+template <int V>
+__global__ __launch_bounds__(TN_BLOCK) void tn_bwd_partial_kernel(TnShape s, TnBwd a) {
+    __shared__ float red[2 * (TN_BLOCK / 64)];
+    const int c = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
+    constexpr int SU = TN_SLICE / V, PER = TN_PER / V;
+    const int u0 = sl * SU, u1 = u0 + SU < s.NU ? u0 + SU : s.NU;
+    if (sl >= s.S || u0 >= s.NU) return;
+    float mean, invstd;
+    tn_bwd_stats(a, c, mean, invstd);
+    const size_t chan = (size_t)c * s.HW;
+    float sg = 0.0f, sgx = 0.0f;
+    TnWalk k(u0 + tid, s.RU);
+    for (int p = 0; p < PER; ++p, k.step(s)) {
+        if (u0 + tid + p * TN_BLOCK >= u1) break;
+        const size_t e = chan + k.at<V>(s);
+        Vec<V> g, xh;
+        tn_bwd_load<V>(a, e, mean, invstd, g, xh);
+        if (a.dres) stv<V>(a.dres + e, g);
+#pragma unroll
+        for (int j = 0; j < V; ++j) { sg += g.v[j]; sgx += g.v[j] * xh.v[j]; }
+    }
+    block_sum2<TN_BLOCK>(sg, sgx, red);
+    if (tid == 0) {
+        a.ws[((size_t)c * s.S + sl) * 2] = sg;
+        a.ws[((size_t)c * s.S + sl) * 2 + 1] = sgx;
+    }
+}
+
+// ---- backward, split regime launch 2, and the eval backward without affine gradients (a.sums == 0): grid (C, S), or
+// (C, 1) when only the affine gradients are wanted (a.dx == NULL)
+template <int V>
+__global__ __launch_bounds__(TN_BLOCK) void tn_bwd_apply_kernel(TnShape s, TnBwd a) {
+    const int c = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
+    constexpr int SU = TN_SLICE / V, PER = TN_PER / V;
+    const int u0 = sl * SU, u1 = u0 + SU < s.NU ? u0 + SU : s.NU;
+    if (sl >= s.S || u0 >= s.NU) return;
+    float sg = 0.0f, sgx = 0.0f;
+    if (a.sums) {
+        // the S partials added by the first wave, in double: lane l takes the slices l, l + 64, ... in order, then the
+        // wave's butterfly: the same order, so the same value, in every workgroup of the channel
+        __shared__ double mrg[2];
+        if (tid < 64) {
+            const float* part = a.ws + (size_t)c * s.S * 2;
+            double P = 0.0, Q = 0.0;
+            for (int i = tid; i < s.S; i += 64) { P += (double)part[2 * i]; Q += (double)part[2 * i + 1]; }
+            P = wave_sum_d(P); Q = wave_sum_d(Q);
+            if (tid == 0) { mrg[0] = P; mrg[1] = Q; }
+        }
+        __syncthreads();
+        const double A = mrg[0], Bx = mrg[1];
+        sg = (float)A; sgx = (float)Bx;
+        if (sl == 0 && tid == 0) {
+            if (a.db) a.db[c] = sg;
+            if (a.dw) a.dw[c] = sgx;
+        }
+    }
+    if (!a.dx) return;
+    float mean, invstd;
+    tn_bwd_stats(a, c, mean, invstd);
+    const float kk = (a.w ? a.w[c] : 1.0f) * invstd;
+    const float mg = a.eval ? 0.0f : sg / (float)s.N, mgx = a.eval ? 0.0f : sgx / (float)s.N;
+    const size_t chan = (size_t)c * s.HW;
+    TnWalk k(u0 + tid, s.RU);
+    for (int p = 0; p < PER; ++p, k.step(s)) {
+        if (u0 + tid + p * TN_BLOCK >= u1) break;
+        const size_t e = chan + k.at<V>(s);
+        Vec<V> g, xh;
+        tn_bwd_load<V>(a, e, mean, invstd, g, xh);
+#pragma unroll
+        for (int j = 0; j < V; ++j) g.v[j] = kk * (g.v[j] - mg - xh.v[j] * mgx);
+        stv<V>(a.dx + e, g);
+    }
+}
+
+static bool tn_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// shape checks shared by the entry points; fills `s` for accesses of V floats and workgroups of `block` work-items
+static int tn_shape(int B, int C, int H, int W, TnShape* s) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return VPN_E_BADARG;
+    const long long HW = (long long)H * W, N = HW * B;
+    if (N > 2147483647LL || (N + TN_SLICE - 1) / TN_SLICE > 65535) return VPN_E_TOOBIG;
+    s->C = C; s->HW = (int)HW; s->N = (int)N; s->S = (int)((N + TN_SLICE - 1) / TN_SLICE);
+    return 0;
+}
+
+static void tn_units(TnShape* s, int V, int block) {
+    s->RU = s->HW / V; s->NU = s->N / V;
+    s->step_b = block / s->RU; s->step_i = block % s->RU;
+}
+
+}  // namespace vpn
+
+using namespace vpn;
+
+extern "C" size_t vpn_bn_act_workspace(int B, int C, int H, int W) {
+    TnShape s;
+    if (tn_shape(B, C, H, W, &s) != 0 || s.N <= TN_MAX) return 0;
+    return (size_t)C * s.S * 2 * sizeof(float);
+}
+
+extern "C" int vpn_bn_act_fwd(const float* x, const float* residual, const float* weight, const float* bias, float* running_mean,
+                              float* running_var, long long* num_batches_tracked, int B, int C, int H, int W, int training,
+                              float momentum, float eps, int relu, float* y, float* save_mean, float* save_invstd, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    TnShape s;
+    const int rc = tn_shape(B, C, H, W, &s);
+    if (rc) return rc;
+    if (!x || !y || !(eps >= 0.0f)) return VPN_E_BADARG;
+    if (training ? (!save_mean || !save_invstd || s.N < 2 || !(momentum >= 0.0f && momentum <= 1.0f)) : (!running_mean || !running_var))
+        return VPN_E_BADARG;
+    const bool split = training && s.N > TN_MAX;
+    if (split && (!workspace || workspace_bytes < vpn_bn_act_workspace(B, C, H, W) || ((uintptr_t)workspace & 3))) return VPN_E_BADARG;
+    const bool vec = s.HW % 4 == 0 && tn_aligned16(x) && tn_aligned16(y) && tn_aligned16(residual);
+    hipStream_t st = (hipStream_t)stream;
+    TnFwd a{x, residual, weight, bias, running_mean, running_var, training ? num_batches_tracked : nullptr, y, save_mean,
+            save_invstd, split ? (float*)workspace : nullptr, momentum, eps, relu != 0};
+    if (training && !split) {
+        const int block = s.N <= TN_SMALL ? 64 : TN_BLOCK;
+        tn_units(&s, vec ? 4 : 1, block);
+        const dim3 grid((unsigned)C);
+        if (block == 64) {
+            if (vec) VPN_LAUNCH_AS("tn_fwd_onepass_kernel", (tn_fwd_onepass_kernel<64, 4>), grid, dim3(64), 0, st, s, a);
+            else VPN_LAUNCH_AS("tn_fwd_onepass_kernel", (tn_fwd_onepass_kernel<64, 1>), grid, dim3(64), 0, st, s, a);
+        } else {
+            if (vec) VPN_LAUNCH_AS("tn_fwd_onepass_kernel", (tn_fwd_onepass_kernel<TN_BLOCK, 4>), grid, dim3(TN_BLOCK), 0, st, s, a);
+            else VPN_LAUNCH_AS("tn_fwd_onepass_kernel", (tn_fwd_onepass_kernel<TN_BLOCK, 1>), grid, dim3(TN_BLOCK), 0, st, s, a);
+        }
+        VPN_LAUNCH_CHECK();
+        return 0;
+    }
+    tn_units(&s, vec ? 4 : 1, TN_BLOCK);
+    const dim3 grid((unsigned)C, (unsigned)s.S);
+    if (split) {
+        if (vec) VPN_LAUNCH_AS("tn_stats_kernel", (tn_stats_kernel<4>), grid, dim3(TN_BLOCK), 0, st, s, a);
+        else VPN_LAUNCH_AS("tn_stats_kernel", (tn_stats_kernel<1>), grid, dim3(TN_BLOCK), 0, st, s, a);
+        VPN_LAUNCH_CHECK();
+    }
+    if (vec) VPN_LAUNCH_AS("tn_fwd_apply_kernel", (tn_fwd_apply_kernel<4>), grid, dim3(TN_BLOCK), 0, st, s, a);
+    else VPN_LAUNCH_AS("tn_fwd_apply_kernel", (tn_fwd_apply_kernel<1>), grid, dim3(TN_BLOCK), 0, st, s, a);
+    VPN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vpn_bn_act_bwd(const float* dy, const float* x, const float* y, const float* weight, const float* stat_mean,
+                              const float* stat_var, int B, int C, int H, int W, int training, float eps, int relu, float* dx,
+                              float* d_residual, float* d_weight, float* d_bias, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+    TnShape s;
+    const int rc = tn_shape(B, C, H, W, &s);
+    if (rc) return rc;
+    if (!dy || !x || !stat_mean || !stat_var || (relu && !y) || !(eps >= 0.0f) || (training && s.N < 2)) return VPN_E_BADARG;
+    const bool affine = d_weight || d_bias;
+    if (!dx && !d_residual && !affine) return 0;                     // nothing is wanted
+    const bool sums = training || affine;                            // eval: dx needs no sum
+    const bool split = s.N > TN_MAX;
+    const bool partial = sums || d_residual;                         // split regime: launch 1 forms the sums and writes d_residual
+    if (split && partial && (!workspace || workspace_bytes < vpn_bn_act_workspace(B, C, H, W) || ((uintptr_t)workspace & 3)))
+        return VPN_E_BADARG;
+    const bool vec = s.HW % 4 == 0 && tn_aligned16(dy) && tn_aligned16(x) && tn_aligned16(relu ? y : nullptr) && tn_aligned16(dx) &&
+                     tn_aligned16(d_residual);
+    hipStream_t st = (hipStream_t)stream;
+    TnBwd a{dy, x, relu ? y : nullptr, weight, stat_mean, stat_var, dx, d_residual, d_weight, d_bias,
+            split && partial ? (float*)workspace : nullptr, eps, training ? 0 : 1, split && sums ? 1 : 0};
+    if (!split) {
+        const int block = s.N <= TN_SMALL ? 64 : TN_BLOCK;
+        tn_units(&s, vec ? 4 : 1, block);
+        const dim3 grid((unsigned)C);
+        if (block == 64) {
+            if (vec) VPN_LAUNCH_AS("tn_bwd_onepass_kernel", (tn_bwd_onepass_kernel<64, 4>), grid, dim3(64), 0, st, s, a);
+            else VPN_LAUNCH_AS("tn_bwd_onepass_kernel", (tn_bwd_onepass_kernel<64, 1>), grid, dim3(64), 0, st, s, a);
+        } else {
+            if (vec) VPN_LAUNCH_AS("tn_bwd_onepass_kernel", (tn_bwd_onepass_kernel<TN_BLOCK, 4>), grid, dim3(TN_BLOCK), 0, st, s, a);
+            else VPN_LAUNCH_AS("tn_bwd_onepass_kernel", (tn_bwd_onepass_kernel<TN_BLOCK, 1>), grid, dim3(TN_BLOCK), 0, st, s, a);
+        }
+        VPN_LAUNCH_CHECK();
+        return 0;
+    }
+    tn_units(&s, vec ? 4 : 1, TN_BLOCK);
+    const dim3 grid((unsigned)C, (unsigned)s.S);
+    if (partial) {
+        if (vec) VPN_LAUNCH_AS("tn_bwd_partial_kernel", (tn_bwd_partial_kernel<4>), grid, dim3(TN_BLOCK), 0, st, s, a);
+        else VPN_LAUNCH_AS("tn_bwd_partial_kernel", (tn_bwd_partial_kernel<1>), grid, dim3(TN_BLOCK), 0, st, s, a);
+        VPN_LAUNCH_CHECK();
+    }
+    if (dx || affine) {
+        const dim3 g2 = dx ? grid : dim3((unsigned)C, 1u);
+        if (vec) VPN_LAUNCH_AS("tn_bwd_apply_kernel", (tn_bwd_apply_kernel<4>), g2, dim3(TN_BLOCK), 0, st, s, a);
+        else VPN_LAUNCH_AS("tn_bwd_apply_kernel", (tn_bwd_apply_kernel<1>), g2, dim3(TN_BLOCK), 0, st, s, a);
+        VPN_LAUNCH_CHECK();
+    }
+    return 0;
+}

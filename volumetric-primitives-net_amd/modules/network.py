@@ -1,7 +1,8 @@
 """modules/network of the reference: VPNetOneRes, VPNetTwoRes and SDNet (vpnet_one_resnet.py, vpnet_two_resnet.py,
 sdnet.py), with the same attribute and `state_dict` names, so that a reference checkpoint loads with strict=True
-(train_gcn.py:100-102, every test*.py).  The trunk is a ResNet-18 in plain torch.nn (convolutions and batch norm are
-ATen's); the FC heads, the one part of the networks that is nothing but weight traffic, run on csrc/fcstack.hip: their
+(train_gcn.py:100-102, every test*.py).  The trunk is a ResNet-18: its convolutions are ATen's, and so is everything
+around them by default; with `fused_norm=True` each batch norm, with the residual add and the ReLU that follow it, is one
+op on csrc/trunknorm.hip (the nn.BatchNorm2d modules then only HOLD parameters and buffers); the FC heads, the one part of the networks that is nothing but weight traffic, run on csrc/fcstack.hip: their
 nn.Linear modules only HOLD the parameters, the forward hands the tensors to FcStackFunction, which also applies what
 follows the last layer (restrict_range + split + restrict_volumes into packed rows, or SDNet's tanh).  GCNModel (gcn.py,
 the refinement stage of train_gcn.py / test_gcn.py) is re-exported from modules/gcn.py, so that
@@ -10,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from .. import config
-from ..ops import HeadPackFunction, FcStackFunction
+from ..ops import HeadPackFunction, FcStackFunction, BatchNormActFunction
 from .gcn import GCNModel, GCNConv  # noqa: F401
 
 
@@ -32,9 +33,18 @@ def split_primitives(params: torch.Tensor):
 
 # ---- the trunk: torchvision's resnet18 by its parameter and buffer names (torchvision itself is not a dependency)
 
+def batch_norm_act(x, bn: nn.BatchNorm2d, residual=None, relu=True):
+    """relu?(bn(x) + residual?) in one op on csrc/trunknorm.hip, with the parameters, buffers, momentum, eps and mode of
+    `bn`, which is not called: in training mode its running statistics and num_batches_tracked are updated in place on the
+    device, as nn.BatchNorm2d does."""
+    return BatchNormActFunction.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
+                                      residual, bn.training, bn.momentum, bn.eps, relu)
+
+
 class BasicBlock(nn.Module):
-    def __init__(self, inplanes, planes, stride=1):
+    def __init__(self, inplanes, planes, stride=1, fused_norm=False):
         super().__init__()
+        self.fused_norm = bool(fused_norm)
         self.conv1 = nn.Conv2d(inplanes, planes, 3, stride, 1, bias=False)
         self.bn1 = nn.BatchNorm2d(planes)
         self.relu = nn.ReLU(inplace=True)
@@ -45,6 +55,10 @@ class BasicBlock(nn.Module):
             self.downsample = nn.Sequential(nn.Conv2d(inplanes, planes, 1, stride, bias=False), nn.BatchNorm2d(planes))
 
     def forward(self, x):
+        if self.fused_norm:
+            out = batch_norm_act(self.conv1(x), self.bn1, relu=True)
+            identity = x if self.downsample is None else batch_norm_act(self.downsample[0](x), self.downsample[1], relu=False)
+            return batch_norm_act(self.conv2(out), self.bn2, residual=identity, relu=True)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.bn2(self.conv2(out))
         return self.relu(out + (x if self.downsample is None else self.downsample(x)))
@@ -53,33 +67,43 @@ class BasicBlock(nn.Module):
 class ResNet18(nn.Module):
     """ResNet-18 (He et al. 2016) laid out as torchvision.models.resnet18: 122 state_dict entries, 11 689 512
     parameters, the `fc` 512 -> 1000 that the reference's models never call included.  Weights come from
-    load_state_dict alone: nothing is ever downloaded."""
+    load_state_dict alone: nothing is ever downloaded.  fused_norm=True: the same modules under the same names (the
+    same state_dict, loadable either way with strict=True), every norm / add / ReLU site on csrc/trunknorm.hip."""
 
-    def __init__(self, num_classes=1000):
+    def __init__(self, num_classes=1000, fused_norm=False):
         super().__init__()
+        f = self.fused_norm = bool(fused_norm)
         self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         self.relu = nn.ReLU(inplace=True)
         self.maxpool = nn.MaxPool2d(3, 2, 1)
-        self.layer1 = nn.Sequential(BasicBlock(64, 64), BasicBlock(64, 64))
-        self.layer2 = nn.Sequential(BasicBlock(64, 128, 2), BasicBlock(128, 128))
-        self.layer3 = nn.Sequential(BasicBlock(128, 256, 2), BasicBlock(256, 256))
-        self.layer4 = nn.Sequential(BasicBlock(256, 512, 2), BasicBlock(512, 512))
+        self.layer1 = nn.Sequential(BasicBlock(64, 64, fused_norm=f), BasicBlock(64, 64, fused_norm=f))
+        self.layer2 = nn.Sequential(BasicBlock(64, 128, 2, fused_norm=f), BasicBlock(128, 128, fused_norm=f))
+        self.layer3 = nn.Sequential(BasicBlock(128, 256, 2, fused_norm=f), BasicBlock(256, 256, fused_norm=f))
+        self.layer4 = nn.Sequential(BasicBlock(256, 512, 2, fused_norm=f), BasicBlock(512, 512, fused_norm=f))
         self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
         self.fc = nn.Linear(512, num_classes)
         for m in self.modules():                       # torchvision's initialisation
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
 
+    def _stem(self, x):
+        if self.fused_norm:
+            return self.maxpool(batch_norm_act(self.conv1(x), self.bn1, relu=True))
+        return self.maxpool(self.relu(self.bn1(self.conv1(x))))
+
     def forward(self, x):
-        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        x = self._stem(x)
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         return self.fc(torch.flatten(self.avgpool(x), 1))
 
 
 def _trunk_maps(model, imgs):
     """conv1 .. layer4 of a trunk (extract_feature of the three models): the four residual stages' outputs."""
-    out = model.maxpool(model.relu(model.bn1(model.conv1(imgs))))
+    if getattr(model, 'fused_norm', False):
+        out = model.maxpool(batch_norm_act(model.conv1(imgs), model.bn1, relu=True))
+    else:
+        out = model.maxpool(model.relu(model.bn1(model.conv1(imgs))))
     l1 = model.layer1(out)
     l2 = model.layer2(l1)
     l3 = model.layer3(l2)

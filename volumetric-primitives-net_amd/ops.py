@@ -1994,3 +1994,94 @@ def adam_step(segments, num_segments, chunks, num_chunks, state, lr, lr_dev, bet
     hyper = (ctypes.c_double * 5)(lr, beta1, beta2, eps, weight_decay)
     _lib.call('vpn_adam_step', segments, int(num_segments), chunks, int(num_chunks), state, hyper, lr_dev, int(bool(zero_grads)),
               _lib.stream())
+
+
+# ---- the trunk's norm / add / ReLU ring (csrc/trunknorm.hip): training-mode batch norm, the residual add
+# and the ReLU of a ResNet-18 site as one op
+
+TRUNKNORM_ONE_PASS_MAX = _H['VPN_BN_ONE_PASS_MAX']      # N = B H W up to here: one launch, the channel's slab stays in LDS
+TRUNKNORM_SLICE = _H['VPN_BN_SLICE']                    # above it: two launches over slices of this many elements
+
+
+def _bn_act_check(x, weight, bias, running_mean, running_var, num_batches_tracked, residual, training, momentum):
+    """Everything BatchNormActFunction refuses, before any launch (and before the library is loaded)."""
+    if x.dim() != 4:
+        raise ValueError('batch_norm_act: x must be (B, C, H, W), got %d dimensions' % x.dim())
+    C = x.shape[1]
+    tensors = dict(x=x, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var, residual=residual)
+    for name, t in tensors.items():
+        if t is not None and t.dtype != torch.float32:
+            raise NotImplementedError('batch_norm_act: fp32 only (%s is %s)' % (name, t.dtype))
+    if running_mean is None or running_var is None:
+        raise NotImplementedError('batch_norm_act: track_running_stats=False (no running statistics) is not supported')
+    if momentum is None:
+        raise NotImplementedError('batch_norm_act: momentum=None (cumulative moving average) is not supported')
+    if num_batches_tracked is not None and num_batches_tracked.dtype != torch.int64:
+        raise ValueError('batch_norm_act: num_batches_tracked must be int64')
+    for name in ('weight', 'bias', 'running_mean', 'running_var'):
+        if tensors[name] is not None and tuple(tensors[name].shape) != (C,):
+            raise ValueError('batch_norm_act: %s must have shape (%d,), got %s' % (name, C, tuple(tensors[name].shape)))
+    if residual is not None and residual.shape != x.shape:
+        raise ValueError('batch_norm_act: the residual has shape %s, x has %s' % (tuple(residual.shape), tuple(x.shape)))
+    if x.numel() == 0:
+        raise ValueError('batch_norm_act: empty input')
+    if training and x.numel() // C == 1:
+        raise ValueError('batch_norm_act: expected more than 1 value per channel when training, got input size %s'
+                         % (tuple(x.shape),))
+    for name, t in list(tensors.items()) + [('num_batches_tracked', num_batches_tracked)]:
+        if t is not None and not t.is_cuda:
+            raise ValueError('batch_norm_act runs on the GPU only (%s is a %s tensor); there is no CPU path' % (name, t.device.type))
+
+
+class BatchNormActFunction(Function):
+    """y = relu?(batch_norm(x) + residual?) on csrc/trunknorm.hip.  apply(x, weight, bias, running_mean, running_var,
+    num_batches_tracked, residual | None, training, momentum, eps, relu).  Training: batch statistics, the running statistics
+    and the counter are updated in place on the device by the same launch; eval: the running statistics.  Gradients for x,
+    weight, bias and residual; each is skipped when not needed."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, num_batches_tracked, residual, training, momentum, eps, relu):
+        training, relu = bool(training), bool(relu)
+        _bn_act_check(x, weight, bias, running_mean, running_var, num_batches_tracked, residual, training, momentum)
+        x = x.contiguous()                    # channels_last and other strided inputs: NCHW first
+        res = None if residual is None else residual.contiguous()
+        weight = None if weight is None else weight.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        B, C, H, W = x.shape
+        dev = x.device
+        y = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
+        save_mean = save_invstd = ws = None
+        if training:
+            save_mean = torch.empty((C,), dtype=torch.float32, device=dev)
+            save_invstd = torch.empty((C,), dtype=torch.float32, device=dev)
+            ws = _workspace('vpn_bn_act_workspace', B, C, H, W, dev=dev)
+        _lib.call('vpn_bn_act_fwd', x, res, weight, bias, running_mean, running_var, num_batches_tracked, B, C, H, W,
+                  int(training), float(momentum), float(eps), int(relu), y, save_mean, save_invstd,
+                  ws if ws is not None and ws.numel() else None, 0 if ws is None else ws.numel() * 4, _lib.stream())
+        stats = (save_mean, save_invstd) if training else (running_mean, running_var)
+        ctx.save_for_backward(x, y if relu else None, weight, *stats)
+        ctx.cfg = (training, float(eps), relu, residual is not None)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, y, weight, stat_a, stat_b = ctx.saved_tensors
+        training, eps, relu, has_res = ctx.cfg
+        need_x, need_w, need_b, need_r = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2],
+                                          has_res and ctx.needs_input_grad[6])
+        B, C, H, W = x.shape
+        dev = x.device
+        dy = grad_y.contiguous()
+        dx = torch.empty_like(x) if need_x else None
+        dw = torch.empty((C,), dtype=torch.float32, device=dev) if need_w else None
+        db = torch.empty((C,), dtype=torch.float32, device=dev) if need_b else None
+        # without a ReLU the residual's gradient IS dy: returned as it is, nothing written
+        dres = torch.empty_like(x) if need_r and relu else None
+        if dx is not None or dw is not None or db is not None or dres is not None:
+            ws = _workspace('vpn_bn_act_workspace', B, C, H, W, dev=dev)
+            _lib.call('vpn_bn_act_bwd', dy, x, y, weight, stat_a, stat_b, B, C, H, W, int(training), eps, int(relu), dx, dres,
+                      dw, db, ws if ws.numel() else None, ws.numel() * 4, _lib.stream())
+        if need_r and not relu:
+            dres = dy
+        return dx, dw, db, None, None, None, dres, None, None, None, None
