@@ -1,6 +1,6 @@
 """A training step of the reference (train.py:221-268) on the drop-in surface, with a stand-in network.
 
-    python examples/train_step.py [--steps 20] [--net standin|vpnet_oneres|vpnet_twores] [--optimizer torch|hip] [--trunk-norm torch|hip]
+    python examples/train_step.py [--steps 20] [--net standin|vpnet_oneres|vpnet_twores] [--optimizer torch|hip] [--trunk-norm torch|hip] [--trunk-conv torch|hip]
 
 By default a two-layer MLP on a random feature vector produces the three head outputs (volumes [B,3K], rotates [B,4K],
 translates [B,3K]); --net vpnet_oneres / vpnet_twores trains the reference's network instead (modules/network.py: a
@@ -145,6 +145,8 @@ def main():
                     help='hip: vpn_amd.Adam (one launch per step, csrc/optim.hip) with the reference\'s betas (0.9, 0.99)')
     ap.add_argument('--trunk-norm', default='torch', choices=('torch', 'hip'),
                     help='hip: the ResNet-18 trunk runs each batch norm with its residual add and ReLU as one op (csrc/trunknorm.hip)')
+    ap.add_argument('--trunk-conv', default='torch', choices=('torch', 'hip'),
+                    help='hip: the 13 stride-1 3x3 convolutions of the ResNet-18 trunk run on the f32-input MFMA (csrc/trunkconv.hip)')
     args = ap.parse_args()
     augment = [a for a in args.augment.split(',') if a]
     assert set(augment) <= {'rotate', 'cutmix', 'mixup', 'pointmixup', 'acdmix'}, augment
@@ -153,10 +155,12 @@ def main():
     torch.manual_seed(1234)
     batch = make_batch(args.batch, args.prims, args.sample_num, args.size, dev)
 
+    own_trunk = 'hip' in (args.trunk_norm, args.trunk_conv)
+
     def trunk():           # None: the model builds its own plain trunk, as it always did
-        return vpn_amd.ResNet18(fused_norm=True) if args.trunk_norm == 'hip' else None
+        return vpn_amd.ResNet18(fused_norm=args.trunk_norm == 'hip', hip_conv=args.trunk_conv == 'hip') if own_trunk else None
     net = {'standin': lambda: Heads(64, args.prims), 'vpnet_oneres': lambda: vpn_amd.VPNetOneRes(vp_num=args.prims, trunk=trunk()),
-           'vpnet_twores': lambda: vpn_amd.VPNetTwoRes(vp_num=args.prims, trunk=(trunk(), trunk()) if args.trunk_norm == 'hip' else None)}[args.net]().to(dev)
+           'vpnet_twores': lambda: vpn_amd.VPNetTwoRes(vp_num=args.prims, trunk=(trunk(), trunk()) if own_trunk else None)}[args.net]().to(dev)
     if args.optimizer == 'hip':
         opt = vpn_amd.Adam(net.parameters(), lr=1e-3, betas=(0.9, 0.99))                # train.py:83
     else:

@@ -911,6 +911,43 @@ int vpn_bn_act_bwd(const float* dy, const float* x, const float* y, const float*
                    const float* stat_var, int B, int C, int H, int W, int training, float eps, int relu, float* dx,
                    float* d_residual, float* d_weight, float* d_bias, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the trunk's 3x3 convolutions (csrc/trunkconv.hip): kernel 3x3, stride 1, padding 1, dilation 1,
+ * groups 1, no bias, as an implicit GEMM on the f32-input MFMA: exact fp32 products, one fixed summation order.  All tensors
+ * DEVICE fp32, contiguous, 4-byte aligned: x [B,C_in,H,W], w [C_out,C_in,3,3], y and dy [B,C_out,H,W], dx as x, dw as w.  Any
+ * positive sizes; padding and the tails of every tile are masked loads.  No host synchronisation, nothing allocated, no
+ * atomics: bit-equal from run to run, capturable.  Added without a change of VPN_ABI_VERSION.
+ *   A product is a GEMM of M x N outputs over K: forward M = C_out, N = B H W, K = 9 C_in; data gradient M = C_in,
+ *   N = B H W, K = 9 C_out; weight gradient M = C_out, N = 9 C_in, K = B H W.  A workgroup owns VPN_CONV_TILE x VPN_CONV_TILE
+ *   outputs and walks K in chunks of VPN_CONV_TILE_K.  With tiles = ceil(M / TILE) ceil(N / TILE) < VPN_CONV_SPLIT_TARGET the
+ *   chunks are split over S = min(ceil(VPN_CONV_SPLIT_TARGET / tiles), VPN_CONV_MAX_SPLIT, chunks) slices (vpn_conv3x3_splits
+ *   returns S, 1 when unsplit, or a negative VPN_E_* code), the partial results go to `workspace` ([S][outputs] floats, 16-byte
+ *   aligned, uninitialised) and a second launch adds them in the order 0 .. S - 1.
+ * vpn_conv3x3_workspace: the bytes a call needs for the products in `products` (VPN_CONV_FWD | VPN_CONV_DX | VPN_CONV_DW; a
+ *   backward call uses one workspace for both of its products in turn: the larger of the two); 0 when none is needed (or for
+ *   sizes the entries reject).
+ * vpn_conv3x3_fwd replaces the forward of nn.Conv2d inside torchvision's BasicBlock, reached through the reference's
+ *   vpnet_one_resnet.py:45-57:  y[b,co,h,w] = sum_{ci,r,s} x[b,ci,h+r-1,w+s-1] w[co,ci,r,s].
+ * vpn_conv3x3_bwd replaces that module's backward (ATen's convolution_backward under the same lines):
+ *   dx[b,ci,h,w] = sum_{co,r,s} dy[b,co,h+1-r,w+1-s] w[co,ci,r,s] (the forward's kernel reading w with the channel strides
+ *   swapped and the taps mirrored: no transposed copy), dw[co,ci,r,s] = sum_{b,h,w} dy[b,co,h,w] x[b,ci,h+r-1,w+s-1].  dx or dw
+ *   may be NULL: that product is neither computed nor stored; both NULL: nothing is launched.
+ * dy / x / w / y NULL or a non-positive size: VPN_E_BADARG; a workspace that is needed and missing, too small or not 16-byte
+ * aligned: VPN_E_BADARG; a tensor of 2^31 elements or more, or more than 65535 tiles along M: VPN_E_TOOBIG.  All before any
+ * HIP call. */
+#define VPN_CONV_TILE 64               /* outputs along M and along N of one workgroup: 2 x 2 waves of 32 x 32 MFMA tiles */
+#define VPN_CONV_TILE_K 16             /* reduction elements per LDS chunk: slices are whole chunks */
+#define VPN_CONV_SPLIT_TARGET 256      /* fewer tiles than this (the CUs of an MI355X): split K to reach it */
+#define VPN_CONV_MAX_SPLIT 32          /* most slices of one product */
+#define VPN_CONV_FWD 1                 /* the products, as bits of vpn_conv3x3_workspace's `products` */
+#define VPN_CONV_DX 2
+#define VPN_CONV_DW 4
+size_t vpn_conv3x3_workspace(int B, int C_in, int C_out, int H, int W, int products);
+int vpn_conv3x3_splits(int B, int C_in, int C_out, int H, int W, int product);
+int vpn_conv3x3_fwd(const float* x, const float* w, float* y, int B, int C_in, int C_out, int H, int W, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int vpn_conv3x3_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, int B, int C_in, int C_out, int H, int W,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,8 @@
 #pragma once
 // host shim: runs a HIP kernel block by block on std::threads (experiment only)
+#define VPN_HOST_SHIM 1
 #include <cmath>
+#include <type_traits>
 #include <cstdint>
 #include <cstring>
 #include <thread>
@@ -34,13 +36,38 @@ inline float __shfl_xor(float v, int o, int) {
     int w = threadIdx.x >> 6, l = threadIdx.x & 63;
     g_xch[w][l] = v; g_wave[w].wait(); float r = g_xch[w][l ^ o]; g_wave[w].wait(); return r;
 }
+// the f32-input MFMAs (tools/trunkconv_host): every lane publishes its A and B element through the per-wave exchange buffers
+// (g_xch, g_xch2), then forms its own results as the k-ordered fmaf chain of the instruction.  Operand and result maps of
+// gfx950: 32x32x2 A[l & 31][l >> 5], B[l >> 5][l & 31], D column l & 31, row (reg & 3) + 8 (reg >> 2) + 4 (l >> 5);
+// 16x16x4 A[l & 15][l >> 4], B[l >> 4][l & 15], D column l & 15, row 4 (l >> 4) + reg.
+extern float g_xch2[16][64];
+struct f32x16 { float v[16]; float& operator[](int i) { return v[i]; } const float& operator[](int i) const { return v[i]; } };
+struct f32x4 { float v[4]; float& operator[](int i) { return v[i]; } const float& operator[](int i) const { return v[i]; } };
+inline f32x16 __builtin_amdgcn_mfma_f32_32x32x2f32(float a, float b, f32x16 c, int, int, int) {
+    int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    g_xch[w][l] = a; g_xch2[w][l] = b; g_wave[w].wait();
+    for (int r = 0; r < 16; ++r) {
+        const int i = (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), j = l & 31;
+        for (int k = 0; k < 2; ++k) c[r] = fmaf(g_xch[w][i + 32 * k], g_xch2[w][j + 32 * k], c[r]);
+    }
+    g_wave[w].wait(); return c;
+}
+inline f32x4 __builtin_amdgcn_mfma_f32_16x16x4f32(float a, float b, f32x4 c, int, int, int) {
+    int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    g_xch[w][l] = a; g_xch2[w][l] = b; g_wave[w].wait();
+    for (int r = 0; r < 4; ++r) {
+        const int i = 4 * (l >> 4) + r, j = l & 15;
+        for (int k = 0; k < 4; ++k) c[r] = fmaf(g_xch[w][i + 16 * k], g_xch2[w][j + 16 * k], c[r]);
+    }
+    g_wave[w].wait(); return c;
+}
 template <class K, class... A> void emu_launch(K k, dim3 grid, dim3 block, A... a) {
-    for (unsigned by = 0; by < grid.y; ++by) for (unsigned bx = 0; bx < grid.x; ++bx) {
+    for (unsigned bz = 0; bz < grid.z; ++bz) for (unsigned by = 0; by < grid.y; ++by) for (unsigned bx = 0; bx < grid.x; ++bx) {
         g_block.live = block.x; g_block.waiting = 0;
         for (int w = 0; w < 16; ++w) { g_wave[w].live = 64; g_wave[w].waiting = 0; }
         std::vector<std::thread> ts;
         for (unsigned t = 0; t < block.x; ++t) ts.emplace_back([=] {
-            threadIdx = dim3(t); blockIdx = dim3(bx, by);
+            threadIdx = dim3(t); blockIdx = dim3(bx, by, bz);
             k(a...);
             g_block.drop(); g_wave[t >> 6].drop();
         });

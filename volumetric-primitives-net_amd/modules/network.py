@@ -1,7 +1,8 @@
 """modules/network of the reference: VPNetOneRes, VPNetTwoRes and SDNet (vpnet_one_resnet.py, vpnet_two_resnet.py,
 sdnet.py), with the same attribute and `state_dict` names, so that a reference checkpoint loads with strict=True
 (train_gcn.py:100-102, every test*.py).  The trunk is a ResNet-18: its convolutions are ATen's, and so is everything
-around them by default; with `fused_norm=True` each batch norm, with the residual add and the ReLU that follow it, is one
+around them by default; with `hip_conv` the 3x3 stride-1 convolutions of the chosen stages run on csrc/trunkconv.hip (the
+nn.Conv2d modules then only HOLD the weights); with `fused_norm=True` each batch norm, with the residual add and the ReLU that follow it, is one
 op on csrc/trunknorm.hip (the nn.BatchNorm2d modules then only HOLD parameters and buffers); the FC heads, the one part of the networks that is nothing but weight traffic, run on csrc/fcstack.hip: their
 nn.Linear modules only HOLD the parameters, the forward hands the tensors to FcStackFunction, which also applies what
 follows the last layer (restrict_range + split + restrict_volumes into packed rows, or SDNet's tanh).  GCNModel (gcn.py,
@@ -11,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from .. import config
-from ..ops import HeadPackFunction, FcStackFunction, BatchNormActFunction
+from ..ops import HeadPackFunction, FcStackFunction, BatchNormActFunction, Conv3x3Function
 from .gcn import GCNModel, GCNConv  # noqa: F401
 
 
@@ -41,10 +42,38 @@ def batch_norm_act(x, bn: nn.BatchNorm2d, residual=None, relu=True):
                                       residual, bn.training, bn.momentum, bn.eps, relu)
 
 
+def conv3x3(x, weight):
+    """conv2d(x, weight, stride 1, padding 1) for a (C_out, C_in, 3, 3) weight without bias, on csrc/trunkconv.hip: exact
+    fp32 products on the f32-input MFMA, one summation order, differentiable in x and weight."""
+    return Conv3x3Function.apply(x, weight)
+
+
+def _is_trunk_conv3x3(conv):
+    return (conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1) and
+            conv.groups == 1 and conv.bias is None and conv.padding_mode == 'zeros')
+
+
+TRUNK_STAGES = ('layer1', 'layer2', 'layer3', 'layer4')
+
+
+def _hip_conv_stages(hip_conv):
+    """hip_conv of ResNet18 -> the tuple of stage names whose 3x3 stride-1 convolutions leave ATen."""
+    if isinstance(hip_conv, bool) or hip_conv is None:
+        return TRUNK_STAGES if hip_conv else ()
+    if isinstance(hip_conv, str):
+        hip_conv = (hip_conv,)
+    stages = tuple(hip_conv)
+    for s in stages:
+        if s not in TRUNK_STAGES:
+            raise ValueError('hip_conv: %r is not one of %s' % (s, TRUNK_STAGES))
+    return tuple(s for s in TRUNK_STAGES if s in stages)
+
+
 class BasicBlock(nn.Module):
-    def __init__(self, inplanes, planes, stride=1, fused_norm=False):
+    def __init__(self, inplanes, planes, stride=1, fused_norm=False, hip_conv=False):
         super().__init__()
         self.fused_norm = bool(fused_norm)
+        self.hip_conv = bool(hip_conv)
         self.conv1 = nn.Conv2d(inplanes, planes, 3, stride, 1, bias=False)
         self.bn1 = nn.BatchNorm2d(planes)
         self.relu = nn.ReLU(inplace=True)
@@ -54,13 +83,18 @@ class BasicBlock(nn.Module):
         if stride != 1 or inplanes != planes:
             self.downsample = nn.Sequential(nn.Conv2d(inplanes, planes, 1, stride, bias=False), nn.BatchNorm2d(planes))
 
+    def _conv(self, conv, x):
+        """`conv` on csrc/trunkconv.hip when this block's stage was chosen and it is a 3x3 stride-1 one (the stride-2 conv1
+        of a stage's first block is not), else the module itself."""
+        return conv3x3(x, conv.weight) if self.hip_conv and _is_trunk_conv3x3(conv) else conv(x)
+
     def forward(self, x):
         if self.fused_norm:
-            out = batch_norm_act(self.conv1(x), self.bn1, relu=True)
+            out = batch_norm_act(self._conv(self.conv1, x), self.bn1, relu=True)
             identity = x if self.downsample is None else batch_norm_act(self.downsample[0](x), self.downsample[1], relu=False)
-            return batch_norm_act(self.conv2(out), self.bn2, residual=identity, relu=True)
-        out = self.relu(self.bn1(self.conv1(x)))
-        out = self.bn2(self.conv2(out))
+            return batch_norm_act(self._conv(self.conv2, out), self.bn2, residual=identity, relu=True)
+        out = self.relu(self.bn1(self._conv(self.conv1, x)))
+        out = self.bn2(self._conv(self.conv2, out))
         return self.relu(out + (x if self.downsample is None else self.downsample(x)))
 
 
@@ -68,19 +102,29 @@ class ResNet18(nn.Module):
     """ResNet-18 (He et al. 2016) laid out as torchvision.models.resnet18: 122 state_dict entries, 11 689 512
     parameters, the `fc` 512 -> 1000 that the reference's models never call included.  Weights come from
     load_state_dict alone: nothing is ever downloaded.  fused_norm=True: the same modules under the same names (the
-    same state_dict, loadable either way with strict=True), every norm / add / ReLU site on csrc/trunknorm.hip."""
+    same state_dict, loadable either way with strict=True), every norm / add / ReLU site on csrc/trunknorm.hip.
+    hip_conv: True, False or an iterable of stage names out of ('layer1', 'layer2', 'layer3', 'layer4'): the 13 convolutions
+    with kernel 3, stride 1, padding 1 of those stages run on csrc/trunkconv.hip, their nn.Conv2d modules only hold the
+    weights; conv1 (7x7), the three stride-2 convolutions and the three 1x1 downsamples stay ATen's.  Independent of
+    fused_norm; the state_dict is the same either way."""
 
-    def __init__(self, num_classes=1000, fused_norm=False):
+    def __init__(self, num_classes=1000, fused_norm=False, hip_conv=False):
         super().__init__()
         f = self.fused_norm = bool(fused_norm)
+        self.hip_conv = _hip_conv_stages(hip_conv)
+        h = {s: s in self.hip_conv for s in TRUNK_STAGES}
         self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         self.relu = nn.ReLU(inplace=True)
         self.maxpool = nn.MaxPool2d(3, 2, 1)
-        self.layer1 = nn.Sequential(BasicBlock(64, 64, fused_norm=f), BasicBlock(64, 64, fused_norm=f))
-        self.layer2 = nn.Sequential(BasicBlock(64, 128, 2, fused_norm=f), BasicBlock(128, 128, fused_norm=f))
-        self.layer3 = nn.Sequential(BasicBlock(128, 256, 2, fused_norm=f), BasicBlock(256, 256, fused_norm=f))
-        self.layer4 = nn.Sequential(BasicBlock(256, 512, 2, fused_norm=f), BasicBlock(512, 512, fused_norm=f))
+        k = dict(fused_norm=f, hip_conv=h['layer1'])
+        self.layer1 = nn.Sequential(BasicBlock(64, 64, **k), BasicBlock(64, 64, **k))
+        k = dict(fused_norm=f, hip_conv=h['layer2'])
+        self.layer2 = nn.Sequential(BasicBlock(64, 128, 2, **k), BasicBlock(128, 128, **k))
+        k = dict(fused_norm=f, hip_conv=h['layer3'])
+        self.layer3 = nn.Sequential(BasicBlock(128, 256, 2, **k), BasicBlock(256, 256, **k))
+        k = dict(fused_norm=f, hip_conv=h['layer4'])
+        self.layer4 = nn.Sequential(BasicBlock(256, 512, 2, **k), BasicBlock(512, 512, **k))
         self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
         self.fc = nn.Linear(512, num_classes)
         for m in self.modules():                       # torchvision's initialisation

@@ -2085,3 +2085,79 @@ class BatchNormActFunction(Function):
         if need_r and not relu:
             dres = dy
         return dx, dw, db, None, None, None, dres, None, None, None, None
+
+
+# ---- the trunk's 3x3 convolutions (csrc/trunkconv.hip): nn.Conv2d(kernel 3, stride 1, padding 1, no bias)
+# inside torchvision's BasicBlock (vpnet_one_resnet.py:45-57), forward and both gradients on the f32-input MFMA
+
+CONV_TILE, CONV_TILE_K = _H['VPN_CONV_TILE'], _H['VPN_CONV_TILE_K']                       # outputs / reduction elements of a workgroup's step
+CONV_SPLIT_TARGET, CONV_MAX_SPLIT = _H['VPN_CONV_SPLIT_TARGET'], _H['VPN_CONV_MAX_SPLIT']   # fewer tiles than the target: K is split
+CONV_FWD, CONV_DX, CONV_DW = _H['VPN_CONV_FWD'], _H['VPN_CONV_DX'], _H['VPN_CONV_DW']
+
+
+def conv3x3_splits(B, C_in, C_out, H, W, product):
+    """The host rule of include/vpn_hip.h restated: the slices S the reduction of `product` (CONV_FWD, CONV_DX, CONV_DW)
+    is split into; 1: one launch, no workspace.  tests hold it to the library's vpn_conv3x3_splits."""
+    M, N, K = {CONV_FWD: (C_out, B * H * W, 9 * C_in), CONV_DX: (C_in, B * H * W, 9 * C_out),
+               CONV_DW: (C_out, 9 * C_in, B * H * W)}[product]
+    tiles = -(-M // CONV_TILE) * -(-N // CONV_TILE)
+    if tiles >= CONV_SPLIT_TARGET:
+        return 1
+    return min(-(-CONV_SPLIT_TARGET // tiles), CONV_MAX_SPLIT, -(-K // CONV_TILE_K))
+
+
+def _conv3x3_check(x, weight):
+    """Everything Conv3x3Function refuses, before any launch (and before the library is loaded)."""
+    if x.dim() != 4:
+        raise ValueError('conv3x3: x must be (B, C_in, H, W), got %d dimensions' % x.dim())
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError('conv3x3: weight must be (C_out, C_in, 3, 3), got %s' % (tuple(weight.shape),))
+    if weight.shape[1] != x.shape[1]:
+        raise ValueError('conv3x3: weight has %d input channels, x has %d (groups = 1 only)' % (weight.shape[1], x.shape[1]))
+    for name, t in (('x', x), ('weight', weight)):
+        if t.dtype != torch.float32:
+            raise NotImplementedError('conv3x3: fp32 only (%s is %s)' % (name, t.dtype))
+    if x.numel() == 0 or weight.numel() == 0:
+        raise ValueError('conv3x3: empty input')
+    for name, t in (('x', x), ('weight', weight)):
+        if not t.is_cuda:
+            raise ValueError('conv3x3 runs on the GPU only (%s is a %s tensor); there is no CPU path' % (name, t.device.type))
+
+
+def _conv3x3_ws(dims, products, dev):
+    ws = _workspace('vpn_conv3x3_workspace', *dims, products, dev=dev)
+    return (ws, ws.numel() * 4) if ws.numel() else (None, 0)
+
+
+class Conv3x3Function(Function):
+    """y = conv2d(x, weight, stride 1, padding 1) for a 3x3 kernel without bias on csrc/trunkconv.hip.  apply(x, weight):
+    x (B, C_in, H, W), weight (C_out, C_in, 3, 3), fp32; strided and channels-last inputs are made NCHW-contiguous first.
+    Gradients for x and weight; each is skipped when not needed (a frozen trunk, an input that needs no gradient)."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        _conv3x3_check(x, weight)
+        x, weight = x.contiguous(), weight.contiguous()
+        B, Ci, H, W = x.shape
+        Co = weight.shape[0]
+        y = torch.empty((B, Co, H, W), dtype=torch.float32, device=x.device)
+        ws, nbytes = _conv3x3_ws((B, Ci, Co, H, W), CONV_FWD, x.device)
+        _lib.call('vpn_conv3x3_fwd', x, weight, y, B, Ci, Co, H, W, ws, nbytes, _lib.stream())
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, weight = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not need_x and not need_w:
+            return None, None
+        B, Ci, H, W = x.shape
+        Co = weight.shape[0]
+        dy = grad_y.contiguous()
+        dx = torch.empty_like(x) if need_x else None
+        dw = torch.empty_like(weight) if need_w else None
+        ws, nbytes = _conv3x3_ws((B, Ci, Co, H, W), (CONV_DX if need_x else 0) | (CONV_DW if need_w else 0), x.device)
+        _lib.call('vpn_conv3x3_bwd', dy, x, weight, dx, dw, B, Ci, Co, H, W, ws, nbytes, _lib.stream())
+        return dx, dw
