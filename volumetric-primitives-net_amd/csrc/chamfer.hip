@@ -665,6 +665,9 @@ constexpr float CM_DOMAIN16 = 64.0f;                         // |p|^2 bound of t
 // 26 covers both.  The pieces' absolute floor (fp16 subnormal spacing; the matrix pipe keeps subnormal inputs --
 // tools/ubench/mfma_f16_denorm.hip -- but the bound below also covers a flush) adds 2^-24 (|a|_1 + |b|_1).
 constexpr float CM_EPS_F16 = 26.0f * 5.9604644775390625e-08f;
+// candidate form of the fp16 scan: a target is kept unless |b - c|^2 > R^2 (1 + CCAND_EPS) + CCAND_FLOOR
+constexpr float CCAND_EPS = 3.0e-5f;
+constexpr float CCAND_FLOOR = 1.0e-30f;
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
 // feature planes / rows of a cloud and the kernel body that writes them: vpn_chamfer_feat.h (shared with sampler.hip,
@@ -1041,6 +1044,7 @@ struct ScanJob {          // one direction of a Chamfer call
     float* wgsum;                                 // [B][gx]: sum of the minima of each workgroup's queries (fixed order)
     const int32_t* qperm;                         // [B][pad32(Nq)]: the order the queries are visited in (null: natural)
     const float* tboxes;                          // fp16 filter: box per 256-target tile (vpn_chamfer_feat.h), null: no skipping
+    int cand;                                     // fp16 filter: each workgroup scans its candidate targets only
 };
 
 // Both directions of a Chamfer call in ONE launch: workgroups [0, j0.G) run job 0, the rest job 1.  Launched
@@ -1073,6 +1077,7 @@ __global__ __launch_bounds__(cm_block<PREC>(), PREC == 1 ? 5 : CM_WAVES_PER_EU) 
     const int wg = (int)blockIdx.x - (PREC == 2 ? oj.B : 0);
 #ifdef CM_EXP_TRACE
     const unsigned long long t_start = wall_clock64();
+    unsigned long long t_pro = t_start;                             // end of the candidate prologue
 #endif
     __shared__ int s_cnt;                                           // length of the workgroup's list of undecided queries (epilogue)
     if (threadIdx.x == 0) s_cnt = 0;
@@ -1088,6 +1093,17 @@ __global__ __launch_bounds__(cm_block<PREC>(), PREC == 1 ? 5 : CM_WAVES_PER_EU) 
     float* __restrict__ wgsum = other ? j1.wgsum : j0.wgsum;
     const int32_t* __restrict__ qperm = PREC == 2 ? (other ? j1.qperm : j0.qperm) : nullptr;   // the fp16 filter only
     const float* __restrict__ tboxes = PREC == 2 ? (other ? j1.tboxes : j0.tboxes) : nullptr;
+    const int cand = PREC == 2 ? (other ? j1.cand : j0.cand) : 0;
+    // The workgroup's list of undecided queries (epilogue): (query, sqrt(m2)) and (query number, index).  A candidate
+    // workgroup keeps the fp32 planes of its candidates in the same bytes until its exact finish has read them.
+    constexpr int QPW = cm_block<PREC>() / 2;                       // queries per workgroup = capacity of the list
+    constexpr int LISTB = QPW * 24 > (PREC == 2 ? 3 * CCAND_CAP * 4 : 0) ? QPW * 24 : 3 * CCAND_CAP * 4;
+    __shared__ __attribute__((aligned(16))) unsigned char s_list[LISTB];
+    float4* const s_qd = reinterpret_cast<float4*>(s_list);
+    int2* const s_qi = reinterpret_cast<int2*>(s_list + QPW * 16);
+    float* const s_cpl = reinterpret_cast<float*>(s_list);          // [3][CCAND_CAP]: x, y, z by compact position
+    __shared__ unsigned short s_cidx[PREC == 2 ? CCAND_CAP : 2];   // original index by compact position
+    int ccount = 0, cpad = 0;                                       // candidates and the same padded to 64; cpad != 0: candidate workgroup
     // Workgroups are dealt round-robin over the 8 XCDs (L2 is per XCD), so the id inside the job is remapped such
     // that all workgroups of a sample land on ONE XCD and stream its target rows out of that XCD's L2 (speed only:
     // any placement is correct; j0.G is a multiple of 8 whenever B is, so id & 7 is still the XCD).
@@ -1208,10 +1224,149 @@ __global__ __launch_bounds__(cm_block<PREC>(), PREC == 1 ? 5 : CM_WAVES_PER_EU) 
             const float E0 = CM_EPS_F16 * r2 * (1.0f + 1.0e-6f) + 5.9604644775390625e-08f * 1.7320509f * r;
             if (nb0 <= CM_DOMAIN16 && na0 <= CM_DOMAIN16) skipc = (na0 + E0) + (3.0e-5f * r2 + 1.0e-30f);
         }
+// one tile of up to 8 blocks at T (this lane's row and half): nblk = 2, 4, 6 or 8
+#define CM_SCAN_TILE(T, t0, nblk)                                                              \
+    {                                                                                          \
+        const float before = best;                                                             \
+        float4 a0 = rd(T, 0), a1 = rd(T, 1), b0 = rd(T, 2), b1 = rd(T, 3);                     \
+        CM_PAIR(a0, a1, 0)                                                                     \
+        if (nblk > 2) {                                                                        \
+            a0 = rd(T, 4); a1 = rd(T, 5);                                                      \
+            CM_PAIR(b0, b1, 1)                                                                 \
+            if (nblk > 4) {                                                                    \
+                b0 = rd(T, 6); b1 = rd(T, 7);                                                  \
+                CM_PAIR(a0, a1, 2)                                                             \
+                if (nblk > 6) CM_PAIR(b0, b1, 3)                                               \
+            }                                                                                  \
+        }                                                                                      \
+        blk = best < before ? (t0) + (blkc << 6) : blk;   /* the tile improved this lane's minimum */ \
+    }
+        int buf = 0, blkc = 0;
+        if (cand) {
+            // ---- Candidate prologue.  The workgroup's queries lie in a ball (c, rho); with d_c the distance
+            // from c to its nearest target every query has a neighbour within rho + d_c, so a target that can win or tie
+            // for any of them lies within R = 2 rho + d_c of c.  Those targets are compacted, in ascending index, into LDS:
+            // original index, fp32 planes and fp16 row by compact position.  More than CCAND_CAP of them, or a bound that
+            // is not finite: the workgroup scans the whole cloud as before.
+            __shared__ float s_cred[8][CM_WAVES16];                 // per wave: box lo xyz, hi xyz, max |a - c|^2, min |b - c|^2
+            __shared__ int s_cwn[2][CM_WAVES16];                    // candidates per wave of a pass (two passes in flight)
+            const float inf = __builtin_inff();
+            auto uni = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+            {
+                const float l0 = feat_wave_minmax<false>(ax), l1 = feat_wave_minmax<false>(ay), l2 = feat_wave_minmax<false>(az);
+                const float h0 = feat_wave_minmax<true>(ax), h1 = feat_wave_minmax<true>(ay), h2 = feat_wave_minmax<true>(az);
+                if (lane == 0) {
+                    s_cred[0][wave] = l0; s_cred[1][wave] = l1; s_cred[2][wave] = l2;
+                    s_cred[3][wave] = h0; s_cred[4][wave] = h1; s_cred[5][wave] = h2;
+                }
+            }
+            __syncthreads();
+            float cc[3];                                            // the centre: the same stored fp32 values in every lane
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                float l = s_cred[a][0], h = s_cred[3 + a][0];
+#pragma unroll
+                for (int w = 1; w < CM_WAVES16; ++w) { l = fminf(l, s_cred[a][w]); h = fmaxf(h, s_cred[3 + a][w]); }
+                cc[a] = uni((l + h) * 0.5f);
+            }
+            const int n4 = Ntp >> 2;
+            const float4* f4 = reinterpret_cast<const float4*>(Fb);  // planes x, y, z at f4 + {0, 1, 2} * n4
+            {
+                float r2 = dist2_exact(ax, ay, az, cc[0], cc[1], cc[2]);
+                r2 = r2 == r2 ? r2 : inf;                           // a NaN query: no bound
+                float dmin = inf;                                   // nearest real target to c (NaN targets are not near)
+                for (int g = threadIdx.x; g < n4; g += CM_BLOCK16) {
+                    const float4 X = f4[g], Y = f4[n4 + g], Z = f4[2 * n4 + g];
+                    const float xs[4] = {X.x, X.y, X.z, X.w}, ys[4] = {Y.x, Y.y, Y.z, Y.w}, zs[4] = {Z.x, Z.y, Z.z, Z.w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float d = dist2_exact(xs[e], ys[e], zs[e], cc[0], cc[1], cc[2]);
+                        dmin = 4 * g + e < Nt ? fminf(dmin, d) : dmin;          // rows past Nt are padding
+                    }
+                }
+                r2 = feat_wave_minmax<true>(r2); dmin = feat_wave_minmax<false>(dmin);
+                if (lane == 0) { s_cred[6][wave] = r2; s_cred[7][wave] = dmin; }
+            }
+            __syncthreads();
+            float thr;
+            {
+                float r2 = s_cred[6][0], dc2 = s_cred[7][0];
+#pragma unroll
+                for (int w = 1; w < CM_WAVES16; ++w) { r2 = fmaxf(r2, s_cred[6][w]); dc2 = fminf(dc2, s_cred[7][w]); }
+                const float R = (2.0f * sqrt_up(r2) + sqrt_up(dc2)) * (1.0f + 1.0e-6f);
+                thr = uni((R * R) * (1.0f + CCAND_EPS) + CCAND_FLOOR);
+            }
+            int total = CCAND_CAP + 1;                              // not finite (or NaN): fall back
+            if (thr < inf) {
+                total = 0;
+                int pass = 0;
+                for (int g0 = 0; g0 < n4; g0 += CM_BLOCK16, pass ^= 1) {
+                    // this lane's run of 4 consecutive targets; lanes, waves and passes follow each other in index order
+                    const int g = g0 + (int)threadIdx.x, gl = min(g, n4 - 1);
+                    const float4 X = f4[gl], Y = f4[n4 + gl], Z = f4[2 * n4 + gl];
+                    const float xs[4] = {X.x, X.y, X.z, X.w}, ys[4] = {Y.x, Y.y, Y.z, Y.w}, zs[4] = {Z.x, Z.y, Z.z, Z.w};
+                    bool keep[4];
+                    int before = 0, wtot = 0;                       // kept targets of lower lanes, of the wave
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float d = dist2_exact(xs[e], ys[e], zs[e], cc[0], cc[1], cc[2]);
+                        keep[e] = !(d > thr) && 4 * g + e < Nt;     // NaN compares false: kept
+                        const unsigned long long m = __ballot(keep[e]);
+                        before += __popcll(m & ((1ull << lane) - 1ull));
+                        wtot += __popcll(m);
+                    }
+                    if (lane == 0) s_cwn[pass][wave] = wtot;
+                    __syncthreads();
+                    int pos = total + before, all = 0;
+#pragma unroll
+                    for (int w = 0; w < CM_WAVES16; ++w) { const int c = s_cwn[pass][w]; pos += w < wave ? c : 0; all += c; }
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        if (keep[e]) {
+                            if (pos < CCAND_CAP) {
+                                const int j = 4 * g + e;
+                                s_cidx[pos] = (unsigned short)j;
+                                s_cpl[pos] = xs[e]; s_cpl[CCAND_CAP + pos] = ys[e]; s_cpl[2 * CCAND_CAP + pos] = zs[e];
+                                const uint4* hr = reinterpret_cast<const uint4*>(Hb + (size_t)j * CM_ROWB16);
+                                const uint4 r0 = hr[0], r1 = hr[1];
+                                *reinterpret_cast<uint4*>(&tileH16[pos * CM_ROWB]) = r0;
+                                *reinterpret_cast<uint4*>(&tileH16[pos * CM_ROWB + 16]) = r1;
+                            }
+                            ++pos;
+                        }
+                    }
+                    total = __builtin_amdgcn_readfirstlane(total + all);
+                    if (total > CCAND_CAP) break;                   // workgroup-uniform
+                }
+            }
+            if (total >= 1 && total <= CCAND_CAP) {
+                ccount = total; cpad = (total + 63) & ~63;
+                const int p = total + (int)threadIdx.x;             // pad to whole pairs of blocks with the sentinel row
+                if (p < cpad) {
+                    const Row16 pad = sentinel_row16();
+                    s_cidx[p] = 0;
+                    s_cpl[p] = 0.0f; s_cpl[CCAND_CAP + p] = 0.0f; s_cpl[2 * CCAND_CAP + p] = 0.0f;
+                    *reinterpret_cast<uint4*>(&tileH16[p * CM_ROWB]) = pad.lo;
+                    *reinterpret_cast<uint4*>(&tileH16[p * CM_ROWB + 16]) = pad.hi;
+                }
+            }
+            __syncthreads();                                        // the candidates are in LDS (or the tiles are free again)
+        }
+#ifdef CM_EXP_TRACE
+        t_pro = wall_clock64();
+#endif
+        if (cpad) {
+            // ---- candidate loop: the compact rows are all in LDS (no fetch, no stash, no barrier); blocks and cells are
+            // numbered by compact position, two "tiles" of 256 rows at the most
+            for (int t0 = 0; t0 < cpad; t0 += CM_TILE16) {
+                const int nblk = min(CM_TILE16, cpad - t0) >> 5;
+                const unsigned char* T = &tileH16[(t0 + jq) * CM_ROWB + half * 16];
+                CM_SCAN_TILE(T, t0, nblk)
+            }
+        } else {
         Pre pre = fetch(0);
         stash(0, pre);
         __syncthreads();
-        int buf = 0, blkc = 0;
         for (int t0 = 0; t0 < Ntp; t0 += CM_TILE16, buf ^= 1) {
             const bool more = t0 + CM_TILE16 < Ntp;
             if (more) pre = fetch(t0 + CM_TILE16);     // in flight during the MFMA loop, stored to LDS after it
@@ -1231,23 +1386,13 @@ __global__ __launch_bounds__(cm_block<PREC>(), PREC == 1 ? 5 : CM_WAVES_PER_EU) 
             if (scan) {
             const int nblk = min(CM_TILE16, Ntp - t0) >> 5;          // 2, 4, 6 or 8 (Ntp is a multiple of 64)
             const unsigned char* T = &tileH[buf][jq * CM_ROWB + half * 16];
-            const float before = best;
-            float4 a0 = rd(T, 0), a1 = rd(T, 1), b0 = rd(T, 2), b1 = rd(T, 3);
-            CM_PAIR(a0, a1, 0)
-            if (nblk > 2) {
-                a0 = rd(T, 4); a1 = rd(T, 5);
-                CM_PAIR(b0, b1, 1)
-                if (nblk > 4) {
-                    b0 = rd(T, 6); b1 = rd(T, 7);
-                    CM_PAIR(a0, a1, 2)
-                    if (nblk > 6) CM_PAIR(b0, b1, 3)
-                }
-            }
-            blk = best < before ? t0 + (blkc << 6) : blk;            // the tile improved this lane's minimum
+            CM_SCAN_TILE(T, t0, nblk)
             }
             if (more) stash(buf ^ 1, pre);
             __syncthreads();
         }
+        }
+#undef CM_SCAN_TILE
 #undef CM_PAIR
     } else     if constexpr (PREC == 1) {
         // ---- bf16 filter: v_mfma_f32_32x32x16_bf16 (K slots 0..15) + v_mfma_f32_32x32x8_bf16 (K slots 16..23) per 32x32
@@ -1424,16 +1569,25 @@ __global__ __launch_bounds__(cm_block<PREC>(), PREC == 1 ? 5 : CM_WAVES_PER_EU) 
     // K is a multiple of CM_CELL below Ntp by construction (tile base + unit number inside the tile; Ntp is a multiple
     // of 64); the clamp costs one instruction per query and keeps the gather inside the padded planes whatever
     // happened upstream
-    K = min(max(K, 0), Ntp - CM_CELL);
+    // (a candidate workgroup: K is a compact position below cpad, the cell's targets come from the compact planes in LDS
+    // and the padding starts at position ccount)
+    const int nreal = cpad ? ccount : Nt;
+    K = min(max(K, 0), (cpad ? cpad : Ntp) - CM_CELL);
     // this lane's targets: groups g = half * NT/4 + j (j < NT/4) of 4 consecutive targets at K + 8 g + 4 hw
     const int base = K + half * (2 * NT) + 4 * hw;
     {
         float4 X[NT / 4], Y[NT / 4], Z[NT / 4];
 #pragma unroll
         for (int v = 0; v < NT / 4; ++v) {
-            X[v] = *reinterpret_cast<const float4*>(Fb + base + 8 * v);
-            Y[v] = *reinterpret_cast<const float4*>(Fb + (size_t)Ntp + base + 8 * v);
-            Z[v] = *reinterpret_cast<const float4*>(Fb + 2 * (size_t)Ntp + base + 8 * v);
+            if (PREC == 2 && cpad) {                                // workgroup-uniform
+                X[v] = *reinterpret_cast<const float4*>(s_cpl + base + 8 * v);
+                Y[v] = *reinterpret_cast<const float4*>(s_cpl + CCAND_CAP + base + 8 * v);
+                Z[v] = *reinterpret_cast<const float4*>(s_cpl + 2 * CCAND_CAP + base + 8 * v);
+            } else {
+                X[v] = *reinterpret_cast<const float4*>(Fb + base + 8 * v);
+                Y[v] = *reinterpret_cast<const float4*>(Fb + (size_t)Ntp + base + 8 * v);
+                Z[v] = *reinterpret_cast<const float4*>(Fb + 2 * (size_t)Ntp + base + 8 * v);
+            }
         }
 #pragma unroll
         for (int v = 0; v < NT / 4; ++v) {
@@ -1444,9 +1598,9 @@ __global__ __launch_bounds__(cm_block<PREC>(), PREC == 1 ? 5 : CM_WAVES_PER_EU) 
         }
         // padding targets (coordinates 0) are masked only by the waves whose winner cell reaches into the padding:
         // three instructions per target that the other waves (all of them when Nt is a multiple of 64) skip
-        if (__ballot(K + CM_CELL > Nt)) {
+        if (__ballot(K + CM_CELL > nreal)) {
 #pragma unroll
-            for (int e = 0; e < NT; ++e) d2[e] += (base + 8 * (e >> 2) + (e & 3) < Nt) ? 0.0f : __builtin_inff();
+            for (int e = 0; e < NT; ++e) d2[e] += (base + 8 * (e >> 2) + (e & 3) < nreal) ? 0.0f : __builtin_inff();
         }
 #pragma unroll
         for (int e = 0; e < NT; ++e) m2 = fminf(m2, d2[e]);
@@ -1505,12 +1659,14 @@ __global__ __launch_bounds__(cm_block<PREC>(), PREC == 1 ? 5 : CM_WAVES_PER_EU) 
             if (d2[e] <= lim && sqrtf(d2[e]) == s) idx = min(idx, base + 8 * (e >> 2) + (e & 3));
     }
     idx = min(idx, __shfl_xor(idx, 32, 64));
+    if (PREC == 2 && cpad) {
+        // compaction is monotone: the lowest position among equals is the lowest original index among equals
+        idx = idx < cpad ? (int)s_cidx[idx] : idx;
+        __syncthreads();                                            // every wave has read the compact planes: the list may overwrite them
+    }
     // Decided queries store their result.  An undecided one goes on the WORKGROUP's list in LDS as (query, sqrt(m2),
     // index inside the best cell) and is resolved exactly by this workgroup before it exits (fixup_own): no list in
     // memory, no second launch, nothing shared between workgroups.
-    constexpr int QPW = cm_block<PREC>() / 2;                       // queries per workgroup = capacity of the list
-    __shared__ float4 s_qd[QPW];
-    __shared__ int2 s_qi[QPW];
     __shared__ float s_ws[cm_block<PREC>() / 64];
     int pos = -1;                                                   // (s_cnt was zeroed before the tile loop, whose barriers order it)
     if (half == 0 && qi < Nq) {
@@ -1558,6 +1714,7 @@ __global__ __launch_bounds__(cm_block<PREC>(), PREC == 1 ? 5 : CM_WAVES_PER_EU) 
 #ifdef CM_EXP_TRACE
         if (PREC == 2 && wg < 8192) {
             unsigned long long* g = g_ctrace + (size_t)wg * 8;
+            g[6] = t_pro; g[7] = (unsigned long long)cpad;
             g[0] = t_start; g[1] = t_loop; g[2] = t_epi; g[3] = wall_clock64(); g[4] = other ? 1ull : 0ull; g[5] = (unsigned long long)cnt;
         }
 #endif
@@ -1886,6 +2043,16 @@ __global__ __launch_bounds__(CM_BLOCK) void chamfer_nn_mfma_pruned_kernel(
     }
 }
 
+// VPN_CHAMFER_CAND=0 turns the candidate form of the fp16 scan off (A/B runs and tests of one build)
+static int chamfer_cand() {
+    static int on = -1;
+    if (on < 0) {
+        const char* e = getenv("VPN_CHAMFER_CAND");
+        on = !(e && e[0] == '0') ? 1 : 0;
+    }
+    return on;
+}
+
 static inline int pad32(int n) { return (n + 63) & ~63; }   // feature planes padded to 64 targets (blocks are processed in pairs)
 // one direction: fp32 planes + bf16 rows of the targets + one tile of slack (the row tiles are fetched without
 // bounds checks) + nmax[B][CFEAT_SLOTS] + the lists of undecided queries (count[pad4(B)], 16-byte entries[B][Nq])
@@ -1923,6 +2090,11 @@ static int mfma_both(const float* p1, const float* p2, int B, int N, int M, floa
     auto split = [](int Ntp) { return feat_split(Ntp); };
     // fp16 filter: direction 2 (queries p2) visits p2 in Morton-cell order and skips p1's tiles (vpn_chamfer_feat.h)
     const bool skip = prec == 2 && N >= CSKIP_MIN_TARGETS;
+    // ... and a direction without tile boxes scans each workgroup's candidate targets only (at C3: direction 1); from the
+    // sizes alone, so modes 6 and 7 decide alike
+    auto cand = [&](int Nq, int Nt, const float* boxes) {
+        return chamfer_cand() && prec == 2 && !boxes && Nq >= CSKIP_MIN_TARGETS && Nt <= CCAND_MAX_TARGETS ? 1 : 0;
+    };
     const FeatJob f2{p2, M, w2.Ntp, split(w2.Ntp), w2.F, w2.nmax, fp32_filter ? nullptr : w2.H, prec == 2, nullptr,
                      skip ? w2.perm : nullptr};
     const FeatJob f1{p1, N, w1.Ntp, split(w1.Ntp), w1.F, w1.nmax, fp32_filter ? nullptr : w1.H, prec == 2,
@@ -1937,9 +2109,10 @@ static int mfma_both(const float* p1, const float* p2, int B, int N, int M, floa
     {
         const int qpw = prec == 2 ? 32 * CM_WAVES16 : 128;          // queries per workgroup
         const int gx1 = (N + qpw - 1) / qpw, gx2 = (M + qpw - 1) / qpw;
-        const ScanJob s1{p1, w2.F, w2.H, w2.nmax, N, M, w2.Ntp, gx1, gx1 * B, d1, i1, w2.wgsum, nullptr, nullptr};  // p1 against p2
+        const ScanJob s1{p1, w2.F, w2.H, w2.nmax, N, M, w2.Ntp, gx1, gx1 * B, d1, i1, w2.wgsum, nullptr, nullptr,   // p1 against p2
+                         cand(N, M, nullptr)};
         const ScanJob s2{p2, w1.F, w1.H, w1.nmax, M, N, w1.Ntp, gx2, gx2 * B, d2, i2, w1.wgsum,                     // p2 against p1
-                         f2.perm, f1.tboxes};
+                         f2.perm, f1.tboxes, cand(M, N, f1.tboxes)};
         const bool long_first = (long long)N > (long long)M;       // direction 2 scans the N targets: more work per workgroup
         const ScanJob& ja = long_first ? s2 : s1;
         const ScanJob& jb = long_first ? s1 : s2;

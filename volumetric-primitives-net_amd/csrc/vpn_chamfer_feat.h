@@ -31,7 +31,8 @@ __device__ inline void split2_f16(float X, _Float16 h[2]) {
 }
 
 // one 32-byte row: K slots  x (b1 b1 b2), y (...), z (...), S^2 |p|^2 as p1 2^15 + p2 2^4 + p3, 4 zeros
-__device__ inline void write_row16(unsigned short* H, size_t row, float x, float y, float z, float n) {
+struct Row16 { uint4 lo, hi; };
+__device__ inline Row16 make_row16(float x, float y, float z, float n) {
 #pragma clang fp contract(off)
     _Float16 hx[2], hy[2], hz[2], pn[3];
     split2_f16(CM_S16 * x, hx); split2_f16(CM_S16 * y, hy); split2_f16(CM_S16 * z, hz);
@@ -47,9 +48,15 @@ __device__ inline void write_row16(unsigned short* H, size_t row, float x, float
     auto bits = [](_Float16 v) { return (unsigned)__builtin_bit_cast(unsigned short, v); };
     auto pk = [&](_Float16 lo, _Float16 hi) { return bits(lo) | (bits(hi) << 16); };
     const _Float16 zero = (_Float16)0.0f;
+    return Row16{make_uint4(pk(hx[0], hx[0]), pk(hx[1], hy[0]), pk(hy[0], hy[1]), pk(hz[0], hz[0])),
+                 make_uint4(pk(hz[1], pn[0]), pk(pn[1], pn[2]), pk(zero, zero), pk(zero, zero))};
+}
+// the row of a padding target (x = y = z = 0, the never-winning sentinel norm): what feat_point writes for rows j >= N
+__device__ inline Row16 sentinel_row16() { return make_row16(0.0f, 0.0f, 0.0f, 3.0e38f); }
+__device__ inline void write_row16(unsigned short* H, size_t row, float x, float y, float z, float n) {
+    const Row16 r = make_row16(x, y, z, n);
     uint4* dst = reinterpret_cast<uint4*>(reinterpret_cast<unsigned char*>(H) + row * CM_ROWB16);
-    dst[0] = make_uint4(pk(hx[0], hx[0]), pk(hx[1], hy[0]), pk(hy[0], hy[1]), pk(hz[0], hz[0]));
-    dst[1] = make_uint4(pk(hz[1], pn[0]), pk(pn[1], pn[2]), pk(zero, zero), pk(zero, zero));
+    dst[0] = r.lo; dst[1] = r.hi;
 }
 
 // feature planes F[b][4][Np] = (x, y, z, |p|^2) (padded with a never-winning sentinel) and
@@ -154,6 +161,10 @@ constexpr int CFEAT_BOXF = 8;            // floats per box: lo xyz, hi xyz, 2 un
 constexpr int CSKIP_MIN_TARGETS = 4096;
 constexpr int CORD_MAX = 2048;           // largest cloud one workgroup orders (8 cells per lane in registers); larger
                                          // clouds keep their natural order
+// Candidate form of the scan (chamfer.hip): a workgroup whose 256 queries lie close together scans only the
+// targets inside a ball around them.  Taken by a direction without tile boxes from CSKIP_MIN_TARGETS queries on.
+constexpr int CCAND_CAP = 512;           // candidates per workgroup at most (= the two 256-row LDS tiles as one buffer)
+constexpr int CCAND_MAX_TARGETS = 65535; // candidate indices are kept as 16-bit numbers
 
 // box entry of tile t of sample b of a cloud with Np padded rows (the workspace carves Np / 32 entries per sample)
 __device__ inline float* feat_tile_box(float* boxes, int Np, int b, int t) {
