@@ -948,6 +948,37 @@ int vpn_conv3x3_fwd(const float* x, const float* w, float* y, int B, int C_in, i
 int vpn_conv3x3_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, int B, int C_in, int C_out, int H, int W,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the trunk's strided convolutions (csrc/trunkstride.hip): square kernel R in {1, 3, 7}, stride >= 1,
+ * padding >= 0, dilation 1, groups 1, no bias, by the scheme and with the VPN_CONV_* constants of vpn_conv3x3_* above: exact
+ * fp32 products, one fixed summation order.  OH = (H + 2 pad - R) / stride + 1 (floor), OW likewise.  All tensors DEVICE fp32,
+ * contiguous, 4-byte aligned: x [B,C_in,H,W], w [C_out,C_in,R,R], y and dy [B,C_out,OH,OW], dx as x, dw as w.  Padding, stride
+ * gaps and the tails of every tile are masked loads.  No host synchronisation, nothing allocated, no atomics: bit-equal from
+ * run to run, capturable.  Added without a change of VPN_ABI_VERSION.
+ *   A product is a GEMM of M x N outputs over K: forward M = C_out, N = B OH OW, K = R R C_in; data gradient M = C_in,
+ *   N = B H W, K = R R C_out; weight gradient M = C_out, N = R R C_in, K = B OH OW.  Tiles, slices and the workspace follow the
+ *   rule stated at vpn_conv3x3_*: vpn_conv2d_splits returns S (1 when unsplit, or a negative VPN_E_* code),
+ *   vpn_conv2d_workspace the bytes for the products in `products` (the larger of a backward call's two; 0 when none is needed
+ *   or for arguments the entries reject).  With (R, stride, pad) = (3, 1, 1) both equal vpn_conv3x3_splits / _workspace and the
+ *   results equal vpn_conv3x3_fwd / _bwd bit for bit.
+ * vpn_conv2d_fwd replaces the forward of nn.Conv2d reached through the reference's vpnet_one_resnet.py:45-57 (the 7x7 stem,
+ *   the stride-2 3x3 and the 1x1 downsample convolutions of torchvision's resnet18):
+ *   y[b,co,oh,ow] = sum_{ci,r,s} x[b,ci,oh stride+r-pad,ow stride+s-pad] w[co,ci,r,s].
+ * vpn_conv2d_bwd replaces that module's backward (ATen's convolution_backward under the same lines):
+ *   dx[b,ci,ih,iw] = sum_{co,r,s} dy[b,co,(ih+pad-r)/stride,(iw+pad-s)/stride] w[co,ci,r,s] over the taps whose two quotients
+ *   are exact and in range (an input pixel that no output reads gets dx = 0, written by the call: dx need not be zeroed),
+ *   dw[co,ci,r,s] = sum_{b,oh,ow} dy[b,co,oh,ow] x[b,ci,oh stride+r-pad,ow stride+s-pad].  dx or dw may be NULL: that product is
+ *   neither computed nor stored; both NULL: nothing is launched.
+ * dy / x / w / y NULL, a non-positive size, R not 1, 3 or 7, stride < 1, pad < 0, H + 2 pad < R or W + 2 pad < R:
+ * VPN_E_BADARG; a workspace that is needed and missing, too small or not 16-byte aligned: VPN_E_BADARG; x, y or w of 2^31
+ * elements or more, H + 2 pad or W + 2 pad of 2^31 or more, or more than 65535 tiles along M: VPN_E_TOOBIG.  All before any HIP
+ * call. */
+size_t vpn_conv2d_workspace(int B, int C_in, int C_out, int H, int W, int R, int stride, int pad, int products);
+int vpn_conv2d_splits(int B, int C_in, int C_out, int H, int W, int R, int stride, int pad, int product);
+int vpn_conv2d_fwd(const float* x, const float* w, float* y, int B, int C_in, int C_out, int H, int W, int R, int stride, int pad,
+                   void* workspace, size_t workspace_bytes, void* stream);
+int vpn_conv2d_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, int B, int C_in, int C_out, int H, int W,
+                   int R, int stride, int pad, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

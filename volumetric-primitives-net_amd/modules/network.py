@@ -1,7 +1,8 @@
 """modules/network of the reference: VPNetOneRes, VPNetTwoRes and SDNet (vpnet_one_resnet.py, vpnet_two_resnet.py,
 sdnet.py), with the same attribute and `state_dict` names, so that a reference checkpoint loads with strict=True
 (train_gcn.py:100-102, every test*.py).  The trunk is a ResNet-18: its convolutions are ATen's, and so is everything
-around them by default; with `hip_conv` the 3x3 stride-1 convolutions of the chosen stages run on csrc/trunkconv.hip (the
+around them by default; with `hip_conv` the 3x3 stride-1 convolutions of the chosen stages run on csrc/trunkconv.hip, with
+`hip_conv_strided` the seven stride-2 ones (the stem, layerN.0.conv1, layerN.0.downsample.0) on csrc/trunkstride.hip (the
 nn.Conv2d modules then only HOLD the weights); with `fused_norm=True` each batch norm, with the residual add and the ReLU that follow it, is one
 op on csrc/trunknorm.hip (the nn.BatchNorm2d modules then only HOLD parameters and buffers); the FC heads, the one part of the networks that is nothing but weight traffic, run on csrc/fcstack.hip: their
 nn.Linear modules only HOLD the parameters, the forward hands the tensors to FcStackFunction, which also applies what
@@ -12,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from .. import config
-from ..ops import HeadPackFunction, FcStackFunction, BatchNormActFunction, Conv3x3Function
+from ..ops import HeadPackFunction, FcStackFunction, BatchNormActFunction, Conv3x3Function, Conv2dFunction
 from .gcn import GCNModel, GCNConv  # noqa: F401
 
 
@@ -48,6 +49,27 @@ def conv3x3(x, weight):
     return Conv3x3Function.apply(x, weight)
 
 
+def conv2d(x, weight, stride=1, padding=0):
+    """conv2d(x, weight, stride, padding) for a (C_out, C_in, R, R) weight with R of 1, 3 or 7, without bias, on
+    csrc/trunkstride.hip: exact fp32 products on the f32-input MFMA, one summation order, differentiable in x and weight.
+    stride and padding are ints (both directions alike).  With a 3x3 weight, stride 1 and padding 1 it equals conv3x3 bit
+    for bit."""
+    return Conv2dFunction.apply(x, weight, stride, padding)
+
+
+def _is_trunk_conv_strided(conv):
+    """The trunk's convolutions with a stride: the 7x7 stem, the 3x3 layerN.0.conv1 and the 1x1 layerN.0.downsample.0."""
+    k, p = conv.kernel_size, conv.padding
+    return (k[0] == k[1] and k[0] in (1, 3, 7) and conv.stride[0] == conv.stride[1] and conv.stride[0] > 1 and
+            not isinstance(p, str) and p[0] == p[1] and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None and
+            conv.padding_mode == 'zeros')
+
+
+def _conv_strided(conv, x):
+    """`conv` (a module _is_trunk_conv_strided accepts) on csrc/trunkstride.hip: the module only holds the weight."""
+    return Conv2dFunction.apply(x, conv.weight, conv.stride[0], conv.padding[0])
+
+
 def _is_trunk_conv3x3(conv):
     return (conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1) and
             conv.groups == 1 and conv.bias is None and conv.padding_mode == 'zeros')
@@ -70,10 +92,11 @@ def _hip_conv_stages(hip_conv):
 
 
 class BasicBlock(nn.Module):
-    def __init__(self, inplanes, planes, stride=1, fused_norm=False, hip_conv=False):
+    def __init__(self, inplanes, planes, stride=1, fused_norm=False, hip_conv=False, hip_conv_strided=False):
         super().__init__()
         self.fused_norm = bool(fused_norm)
         self.hip_conv = bool(hip_conv)
+        self.hip_conv_strided = bool(hip_conv_strided)
         self.conv1 = nn.Conv2d(inplanes, planes, 3, stride, 1, bias=False)
         self.bn1 = nn.BatchNorm2d(planes)
         self.relu = nn.ReLU(inplace=True)
@@ -84,18 +107,27 @@ class BasicBlock(nn.Module):
             self.downsample = nn.Sequential(nn.Conv2d(inplanes, planes, 1, stride, bias=False), nn.BatchNorm2d(planes))
 
     def _conv(self, conv, x):
-        """`conv` on csrc/trunkconv.hip when this block's stage was chosen and it is a 3x3 stride-1 one (the stride-2 conv1
-        of a stage's first block is not), else the module itself."""
-        return conv3x3(x, conv.weight) if self.hip_conv and _is_trunk_conv3x3(conv) else conv(x)
+        """`conv` on csrc/trunkconv.hip when this block's stage was chosen and it is a 3x3 stride-1 one, on
+        csrc/trunkstride.hip when hip_conv_strided and it has a stride (the conv1 and the downsample of a stage's first
+        block), else the module itself."""
+        if self.hip_conv and _is_trunk_conv3x3(conv):
+            return conv3x3(x, conv.weight)
+        if self.hip_conv_strided and _is_trunk_conv_strided(conv):
+            return _conv_strided(conv, x)
+        return conv(x)
 
     def forward(self, x):
         if self.fused_norm:
             out = batch_norm_act(self._conv(self.conv1, x), self.bn1, relu=True)
-            identity = x if self.downsample is None else batch_norm_act(self.downsample[0](x), self.downsample[1], relu=False)
+            identity = x if self.downsample is None else batch_norm_act(self._conv(self.downsample[0], x), self.downsample[1], relu=False)
             return batch_norm_act(self._conv(self.conv2, out), self.bn2, residual=identity, relu=True)
         out = self.relu(self.bn1(self._conv(self.conv1, x)))
         out = self.bn2(self._conv(self.conv2, out))
-        return self.relu(out + (x if self.downsample is None else self.downsample(x)))
+        if self.downsample is None:
+            return self.relu(out + x)
+        if self.hip_conv_strided and _is_trunk_conv_strided(self.downsample[0]):
+            return self.relu(out + self.downsample[1](_conv_strided(self.downsample[0], x)))
+        return self.relu(out + self.downsample(x))
 
 
 class ResNet18(nn.Module):
@@ -105,25 +137,28 @@ class ResNet18(nn.Module):
     same state_dict, loadable either way with strict=True), every norm / add / ReLU site on csrc/trunknorm.hip.
     hip_conv: True, False or an iterable of stage names out of ('layer1', 'layer2', 'layer3', 'layer4'): the 13 convolutions
     with kernel 3, stride 1, padding 1 of those stages run on csrc/trunkconv.hip, their nn.Conv2d modules only hold the
-    weights; conv1 (7x7), the three stride-2 convolutions and the three 1x1 downsamples stay ATen's.  Independent of
-    fused_norm; the state_dict is the same either way."""
+    weights; conv1 (7x7), the three stride-2 convolutions and the three 1x1 downsamples are not among them.
+    hip_conv_strided=True: those seven (conv1, every layerN.0.conv1 and layerN.0.downsample[0] with stride 2) run on
+    csrc/trunkstride.hip; with hip_conv=True as well no library convolution is left in the trunk, forward or backward.  The
+    three keywords are independent; the state_dict is the same either way."""
 
-    def __init__(self, num_classes=1000, fused_norm=False, hip_conv=False):
+    def __init__(self, num_classes=1000, fused_norm=False, hip_conv=False, hip_conv_strided=False):
         super().__init__()
         f = self.fused_norm = bool(fused_norm)
+        g = self.hip_conv_strided = bool(hip_conv_strided)
         self.hip_conv = _hip_conv_stages(hip_conv)
         h = {s: s in self.hip_conv for s in TRUNK_STAGES}
         self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         self.relu = nn.ReLU(inplace=True)
         self.maxpool = nn.MaxPool2d(3, 2, 1)
-        k = dict(fused_norm=f, hip_conv=h['layer1'])
+        k = dict(fused_norm=f, hip_conv=h['layer1'], hip_conv_strided=g)
         self.layer1 = nn.Sequential(BasicBlock(64, 64, **k), BasicBlock(64, 64, **k))
-        k = dict(fused_norm=f, hip_conv=h['layer2'])
+        k = dict(fused_norm=f, hip_conv=h['layer2'], hip_conv_strided=g)
         self.layer2 = nn.Sequential(BasicBlock(64, 128, 2, **k), BasicBlock(128, 128, **k))
-        k = dict(fused_norm=f, hip_conv=h['layer3'])
+        k = dict(fused_norm=f, hip_conv=h['layer3'], hip_conv_strided=g)
         self.layer3 = nn.Sequential(BasicBlock(128, 256, 2, **k), BasicBlock(256, 256, **k))
-        k = dict(fused_norm=f, hip_conv=h['layer4'])
+        k = dict(fused_norm=f, hip_conv=h['layer4'], hip_conv_strided=g)
         self.layer4 = nn.Sequential(BasicBlock(256, 512, 2, **k), BasicBlock(512, 512, **k))
         self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
         self.fc = nn.Linear(512, num_classes)
@@ -131,10 +166,14 @@ class ResNet18(nn.Module):
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
 
+    def _conv1(self, x):
+        """The 7x7 stem convolution: on csrc/trunkstride.hip with hip_conv_strided, else the module itself."""
+        return _conv_strided(self.conv1, x) if self.hip_conv_strided and _is_trunk_conv_strided(self.conv1) else self.conv1(x)
+
     def _stem(self, x):
         if self.fused_norm:
-            return self.maxpool(batch_norm_act(self.conv1(x), self.bn1, relu=True))
-        return self.maxpool(self.relu(self.bn1(self.conv1(x))))
+            return self.maxpool(batch_norm_act(self._conv1(x), self.bn1, relu=True))
+        return self.maxpool(self.relu(self.bn1(self._conv1(x))))
 
     def forward(self, x):
         x = self._stem(x)
@@ -144,10 +183,11 @@ class ResNet18(nn.Module):
 
 def _trunk_maps(model, imgs):
     """conv1 .. layer4 of a trunk (extract_feature of the three models): the four residual stages' outputs."""
+    stem = model._conv1(imgs) if getattr(model, 'hip_conv_strided', False) else model.conv1(imgs)
     if getattr(model, 'fused_norm', False):
-        out = model.maxpool(batch_norm_act(model.conv1(imgs), model.bn1, relu=True))
+        out = model.maxpool(batch_norm_act(stem, model.bn1, relu=True))
     else:
-        out = model.maxpool(model.relu(model.bn1(model.conv1(imgs))))
+        out = model.maxpool(model.relu(model.bn1(stem)))
     l1 = model.layer1(out)
     l2 = model.layer2(l1)
     l3 = model.layer3(l2)

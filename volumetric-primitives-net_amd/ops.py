@@ -2161,3 +2161,100 @@ class Conv3x3Function(Function):
         ws, nbytes = _conv3x3_ws((B, Ci, Co, H, W), (CONV_DX if need_x else 0) | (CONV_DW if need_w else 0), x.device)
         _lib.call('vpn_conv3x3_bwd', dy, x, weight, dx, dw, B, Ci, Co, H, W, ws, nbytes, _lib.stream())
         return dx, dw
+
+
+# ---- the trunk's strided convolutions (csrc/trunkstride.hip): nn.Conv2d(kernel 1, 3 or 7, any stride and
+# padding, no bias) reached through vpnet_one_resnet.py:45-57 (the stem, the stride-2 3x3 and the 1x1 downsamples), forward
+# and both gradients by the scheme of the 3x3 convolutions above
+
+CONV2D_KERNELS = (1, 3, 7)                # the kernel sizes csrc/trunkstride.hip instantiates
+
+
+def conv2d_out_size(H, W, R, stride, padding):
+    """(OH, OW) = ((H + 2 p - R) // stride + 1, likewise for W)."""
+    return (H + 2 * padding - R) // stride + 1, (W + 2 * padding - R) // stride + 1
+
+
+def conv2d_splits(B, C_in, C_out, H, W, R, stride, padding, product):
+    """The host rule of include/vpn_hip.h restated over the generalised M, N, K: the slices S the reduction of `product`
+    (CONV_FWD, CONV_DX, CONV_DW) is split into; 1: one launch, no workspace.  tests hold it to the library's
+    vpn_conv2d_splits."""
+    OH, OW = conv2d_out_size(H, W, R, stride, padding)
+    M, N, K = {CONV_FWD: (C_out, B * OH * OW, R * R * C_in), CONV_DX: (C_in, B * H * W, R * R * C_out),
+               CONV_DW: (C_out, R * R * C_in, B * OH * OW)}[product]
+    tiles = -(-M // CONV_TILE) * -(-N // CONV_TILE)
+    if tiles >= CONV_SPLIT_TARGET:
+        return 1
+    return min(-(-CONV_SPLIT_TARGET // tiles), CONV_MAX_SPLIT, -(-K // CONV_TILE_K))
+
+
+def _conv2d_check(x, weight, stride, padding):
+    """Everything Conv2dFunction refuses, before any launch (and before the library is loaded)."""
+    if x.dim() != 4:
+        raise ValueError('conv2d: x must be (B, C_in, H, W), got %d dimensions' % x.dim())
+    if weight.dim() != 4 or weight.shape[2] != weight.shape[3]:
+        raise ValueError('conv2d: weight must be (C_out, C_in, R, R), got %s' % (tuple(weight.shape),))
+    if weight.shape[2] not in CONV2D_KERNELS:
+        raise NotImplementedError('conv2d: kernel size %d is not one of %s' % (weight.shape[2], CONV2D_KERNELS))
+    if weight.shape[1] != x.shape[1]:
+        raise ValueError('conv2d: weight has %d input channels, x has %d (groups = 1 only)' % (weight.shape[1], x.shape[1]))
+    if not isinstance(stride, int) or isinstance(stride, bool) or stride < 1:
+        raise ValueError('conv2d: stride must be an int >= 1, got %r' % (stride,))
+    if not isinstance(padding, int) or isinstance(padding, bool) or padding < 0:
+        raise ValueError('conv2d: padding must be an int >= 0, got %r' % (padding,))
+    for name, t in (('x', x), ('weight', weight)):
+        if t.dtype != torch.float32:
+            raise NotImplementedError('conv2d: fp32 only (%s is %s)' % (name, t.dtype))
+    if x.numel() == 0 or weight.numel() == 0:
+        raise ValueError('conv2d: empty input')
+    R = weight.shape[2]
+    if x.shape[2] + 2 * padding < R or x.shape[3] + 2 * padding < R:
+        raise ValueError('conv2d: the padded image (%d + 2 x %d) x (%d + 2 x %d) is smaller than the %d x %d kernel' %
+                         (x.shape[2], padding, x.shape[3], padding, R, R))
+    for name, t in (('x', x), ('weight', weight)):
+        if not t.is_cuda:
+            raise ValueError('conv2d runs on the GPU only (%s is a %s tensor); there is no CPU path' % (name, t.device.type))
+
+
+def _conv2d_ws(dims, products, dev):
+    ws = _workspace('vpn_conv2d_workspace', *dims, products, dev=dev)
+    return (ws, ws.numel() * 4) if ws.numel() else (None, 0)
+
+
+class Conv2dFunction(Function):
+    """y = conv2d(x, weight, stride, padding) for a square kernel of 1, 3 or 7 without bias on csrc/trunkstride.hip.
+    apply(x, weight, stride, padding): x (B, C_in, H, W), weight (C_out, C_in, R, R), fp32, stride >= 1 and padding >= 0
+    ints; strided and channels-last inputs are made NCHW-contiguous first.  Gradients for x and weight; each is skipped
+    when not needed (the stem's input, a frozen trunk)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride, padding):
+        _conv2d_check(x, weight, stride, padding)
+        x, weight = x.contiguous(), weight.contiguous()
+        B, Ci, H, W = x.shape
+        Co, R = weight.shape[0], weight.shape[2]
+        OH, OW = conv2d_out_size(H, W, R, stride, padding)
+        y = torch.empty((B, Co, OH, OW), dtype=torch.float32, device=x.device)
+        ws, nbytes = _conv2d_ws((B, Ci, Co, H, W, R, stride, padding), CONV_FWD, x.device)
+        _lib.call('vpn_conv2d_fwd', x, weight, y, B, Ci, Co, H, W, R, stride, padding, ws, nbytes, _lib.stream())
+        ctx.save_for_backward(x, weight)
+        ctx.cfg = (stride, padding)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, weight = ctx.saved_tensors
+        stride, padding = ctx.cfg
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not need_x and not need_w:
+            return None, None, None, None
+        B, Ci, H, W = x.shape
+        Co, R = weight.shape[0], weight.shape[2]
+        dy = grad_y.contiguous()
+        dx = torch.empty_like(x) if need_x else None
+        dw = torch.empty_like(weight) if need_w else None
+        ws, nbytes = _conv2d_ws((B, Ci, Co, H, W, R, stride, padding), (CONV_DX if need_x else 0) | (CONV_DW if need_w else 0),
+                                x.device)
+        _lib.call('vpn_conv2d_bwd', dy, x, weight, dx, dw, B, Ci, Co, H, W, R, stride, padding, ws, nbytes, _lib.stream())
+        return dx, dw, None, None
