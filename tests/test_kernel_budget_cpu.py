@@ -3,35 +3,11 @@ registers and LDS.  Measured in round 4: with the auction at 94-96 VGPRs (a buil
 instead of 86 the co-running raster and the second Chamfer scan stretched to 480 / 256 us, the main branch became as long
 as the auction and the C5 step went from 0.90 to 1.02 ms.  This test compiles emd.hip the way build.py does and holds the
 kernel to the budget the overlap was measured with."""
-import os
-import re
-import subprocess
-import sys
-
-import pytest
-
-from conftest import ROOT
+from kernel_resources import kernel_resources
 
 
 def _resources(src, kernel):
-    sys.path.insert(0, os.path.join(ROOT, 'volumetric-primitives-net_amd'))
-    import importlib.util
-    spec = importlib.util.spec_from_file_location('vpn_build', os.path.join(ROOT, 'volumetric-primitives-net_amd', 'build.py'))
-    b = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(b)
-    cmd = [b.hipcc()] + b.COMMON + b.PER_FILE.get(src, []) + ['-c', os.path.join(b.CSRC, src), '-o', os.devnull,
-                                                               '-Rpass-analysis=kernel-resource-usage']
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600).stderr
-    cur, rows = None, {}
-    for line in out.splitlines():
-        m = re.search(r'remark:\s+(Function Name|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\S+)', line)
-        if not m:
-            continue
-        if m.group(1) == 'Function Name':
-            cur = m.group(2)
-            rows[cur] = {}
-        elif cur:
-            rows[cur][m.group(1).split(' ')[0]] = int(m.group(2))
+    rows = kernel_resources(src)
     hits = [v for k, v in rows.items() if kernel in k]
     assert len(hits) == 1, (kernel, list(rows))
     return hits[0]

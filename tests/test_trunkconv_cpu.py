@@ -3,30 +3,19 @@
 restatement tests/trunkconv_ref.py against torch's own convolution and autograd in float64, the state_dict of the trunk, and
 the kernels' scratch."""
 import ctypes
-import os
-import re
-import subprocess
 
 import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import ROOT
+from kernel_resources import kernel_resources, load_build
 import trunkconv_ref as R
 
 TILE_CONSTANTS = ('VPN_CONV_TILE', 'VPN_CONV_TILE_K', 'VPN_CONV_SPLIT_TARGET', 'VPN_CONV_MAX_SPLIT')
 
 
-def _build():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location('vpn_build', os.path.join(ROOT, 'volumetric-primitives-net_amd', 'build.py'))
-    b = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(b)
-    return b
-
-
 def test_header_declares_the_entry_points_and_the_library_exports_them():
-    b = _build()
+    b = load_build()
     assert 'trunkconv.hip' in b.SOURCES
     import vpn_amd
     import vpn_amd._lib as lib
@@ -186,25 +175,10 @@ def test_every_refusal_of_the_function_is_raised_before_any_launch(monkeypatch):
 
 
 def test_trunkconv_compiles_as_build_py_compiles_it_without_scratch():
-    b = _build()
-    src = 'trunkconv.hip'
-    cmd = [b.hipcc()] + b.COMMON + b.PER_FILE.get(src, []) + ['-c', os.path.join(b.CSRC, src), '-o', os.devnull,
-                                                               '-Rpass-analysis=kernel-resource-usage']
-    run = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert run.returncode == 0, run.stderr[-2000:]
-    cur, rows = None, {}
-    for line in run.stderr.splitlines():
-        m = re.search(r'remark:\s+(Function Name|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\S+)', line)
-        if not m:
-            continue
-        if m.group(1) == 'Function Name':
-            cur = m.group(2)
-            rows[cur] = {}
-        elif cur:
-            rows[cur][m.group(1).split(' ')[0]] = int(m.group(2))
-    kernels = {k: v for k, v in rows.items() if 'cv_' in k}
+    rows = kernel_resources('trunkconv.hip')
+    kernels = {k: v for k, v in rows.items() if 'cv_gemm_kernel' in k or 'cg_merge_kernel' in k}
     assert len(kernels) == len(rows) == 4, list(rows)          # the GEMM kernel for data and weights, the merge by 4 and by 1
-    assert sum('cv_gemm_kernel' in k for k in kernels) == 2 and sum('cv_merge_kernel' in k for k in kernels) == 2
+    assert sum('cv_gemm_kernel' in k for k in kernels) == 2 and sum('cg_merge_kernel' in k for k in kernels) == 2
     for k, v in kernels.items():
         assert v['ScratchSize'] == 0, (k, v)
         assert v['LDS'] <= 64 * 1024, (k, v)

@@ -3,15 +3,12 @@ ResNet18(hip_conv_strided)): the C ABI, every rejection before a
 (held to the 3x3 rule where the two overlap), the restatement tests/trunkstride_ref.py against torch's own convolution and
 autograd in float64, the state_dict and the routing of the trunk, and the kernels' resources."""
 import ctypes
-import os
-import re
-import subprocess
 
 import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import ROOT
+from kernel_resources import kernel_resources, load_build
 import trunkstride_ref as R
 
 ENTRIES = ('vpn_conv2d_workspace', 'vpn_conv2d_splits', 'vpn_conv2d_fwd', 'vpn_conv2d_bwd')
@@ -32,16 +29,8 @@ ODD = [(1, 1, 1, 1, 1, 1, 2, 0), (1, 1, 1, 1, 1, 3, 2, 1), (1, 2, 3, 2, 2, 7, 2,
        (1, 3, 130, 2, 67, 7, 1, 5), (4, 3, 64, 128, 128, 7, 2, 3)]
 
 
-def _build():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location('vpn_build', os.path.join(ROOT, 'volumetric-primitives-net_amd', 'build.py'))
-    b = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(b)
-    return b
-
-
 def test_header_declares_the_entry_points_and_the_library_exports_them():
-    b = _build()
+    b = load_build()
     assert 'trunkstride.hip' in b.SOURCES
     import vpn_amd
     import vpn_amd._lib as lib
@@ -305,26 +294,11 @@ def test_every_refusal_of_the_function_is_raised_before_any_launch(monkeypatch):
 
 
 def test_trunkstride_compiles_as_build_py_compiles_it_within_the_resource_limits():
-    b = _build()
-    src = 'trunkstride.hip'
-    cmd = [b.hipcc()] + b.COMMON + b.PER_FILE.get(src, []) + ['-c', os.path.join(b.CSRC, src), '-o', os.devnull,
-                                                               '-Rpass-analysis=kernel-resource-usage']
-    run = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert run.returncode == 0, run.stderr[-2000:]
-    cur, rows = None, {}
-    for line in run.stderr.splitlines():
-        m = re.search(r'remark:\s+(Function Name|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\S+)', line)
-        if not m:
-            continue
-        if m.group(1) == 'Function Name':
-            cur = m.group(2)
-            rows[cur] = {}
-        elif cur:
-            rows[cur][m.group(1).split(' ')[0]] = int(m.group(2))
-    kernels = {k: v for k, v in rows.items() if 'cs_' in k}
+    rows = kernel_resources('trunkstride.hip')
+    kernels = {k: v for k, v in rows.items() if 'cs_gemm_kernel' in k or 'cg_merge_kernel' in k}
     # the GEMM kernel for three kernel sizes x three products, the merge by 4 and by 1
     assert len(kernels) == len(rows) == 11, list(rows)
-    assert sum('cs_gemm_kernel' in k for k in kernels) == 9 and sum('cs_merge_kernel' in k for k in kernels) == 2
+    assert sum('cs_gemm_kernel' in k for k in kernels) == 9 and sum('cg_merge_kernel' in k for k in kernels) == 2
     for k, v in kernels.items():
         assert v['ScratchSize'] == 0, (k, v)
         assert v['LDS'] <= 64 * 1024, (k, v)

@@ -15,6 +15,7 @@
 #define __host__
 #define __restrict__
 #define __launch_bounds__(...)
+#define __forceinline__ inline
 #define __shared__ static
 typedef int hipError_t; const int hipSuccess = 0; typedef void* hipStream_t;
 inline hipError_t hipGetLastError() { return 0; }

@@ -2087,86 +2087,14 @@ class BatchNormActFunction(Function):
         return dx, dw, db, None, None, None, dres, None, None, None, None
 
 
-# ---- the trunk's 3x3 convolutions (csrc/trunkconv.hip): nn.Conv2d(kernel 3, stride 1, padding 1, no bias)
-# inside torchvision's BasicBlock (vpnet_one_resnet.py:45-57), forward and both gradients on the f32-input MFMA
+# ---- the trunk's convolutions (csrc/trunkconv.hip, csrc/trunkstride.hip on the tile loop of csrc/vpn_conv_gemm.h; DESIGN.md
+# 4.19, 4.20): nn.Conv2d(square kernel, no bias) reached through vpnet_one_resnet.py:45-57, forward and both gradients on the
+# f32-input MFMA.  Conv3x3Function: kernel 3, stride 1, padding 1 inside torchvision's BasicBlock; Conv2dFunction: kernel 1, 3
+# or 7, any stride and padding (the stem, the stride-2 3x3 and the 1x1 downsamples)
 
 CONV_TILE, CONV_TILE_K = _H['VPN_CONV_TILE'], _H['VPN_CONV_TILE_K']                       # outputs / reduction elements of a workgroup's step
 CONV_SPLIT_TARGET, CONV_MAX_SPLIT = _H['VPN_CONV_SPLIT_TARGET'], _H['VPN_CONV_MAX_SPLIT']   # fewer tiles than the target: K is split
 CONV_FWD, CONV_DX, CONV_DW = _H['VPN_CONV_FWD'], _H['VPN_CONV_DX'], _H['VPN_CONV_DW']
-
-
-def conv3x3_splits(B, C_in, C_out, H, W, product):
-    """The host rule of include/vpn_hip.h restated: the slices S the reduction of `product` (CONV_FWD, CONV_DX, CONV_DW)
-    is split into; 1: one launch, no workspace.  tests hold it to the library's vpn_conv3x3_splits."""
-    M, N, K = {CONV_FWD: (C_out, B * H * W, 9 * C_in), CONV_DX: (C_in, B * H * W, 9 * C_out),
-               CONV_DW: (C_out, 9 * C_in, B * H * W)}[product]
-    tiles = -(-M // CONV_TILE) * -(-N // CONV_TILE)
-    if tiles >= CONV_SPLIT_TARGET:
-        return 1
-    return min(-(-CONV_SPLIT_TARGET // tiles), CONV_MAX_SPLIT, -(-K // CONV_TILE_K))
-
-
-def _conv3x3_check(x, weight):
-    """Everything Conv3x3Function refuses, before any launch (and before the library is loaded)."""
-    if x.dim() != 4:
-        raise ValueError('conv3x3: x must be (B, C_in, H, W), got %d dimensions' % x.dim())
-    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
-        raise ValueError('conv3x3: weight must be (C_out, C_in, 3, 3), got %s' % (tuple(weight.shape),))
-    if weight.shape[1] != x.shape[1]:
-        raise ValueError('conv3x3: weight has %d input channels, x has %d (groups = 1 only)' % (weight.shape[1], x.shape[1]))
-    for name, t in (('x', x), ('weight', weight)):
-        if t.dtype != torch.float32:
-            raise NotImplementedError('conv3x3: fp32 only (%s is %s)' % (name, t.dtype))
-    if x.numel() == 0 or weight.numel() == 0:
-        raise ValueError('conv3x3: empty input')
-    for name, t in (('x', x), ('weight', weight)):
-        if not t.is_cuda:
-            raise ValueError('conv3x3 runs on the GPU only (%s is a %s tensor); there is no CPU path' % (name, t.device.type))
-
-
-def _conv3x3_ws(dims, products, dev):
-    ws = _workspace('vpn_conv3x3_workspace', *dims, products, dev=dev)
-    return (ws, ws.numel() * 4) if ws.numel() else (None, 0)
-
-
-class Conv3x3Function(Function):
-    """y = conv2d(x, weight, stride 1, padding 1) for a 3x3 kernel without bias on csrc/trunkconv.hip.  apply(x, weight):
-    x (B, C_in, H, W), weight (C_out, C_in, 3, 3), fp32; strided and channels-last inputs are made NCHW-contiguous first.
-    Gradients for x and weight; each is skipped when not needed (a frozen trunk, an input that needs no gradient)."""
-
-    @staticmethod
-    def forward(ctx, x, weight):
-        _conv3x3_check(x, weight)
-        x, weight = x.contiguous(), weight.contiguous()
-        B, Ci, H, W = x.shape
-        Co = weight.shape[0]
-        y = torch.empty((B, Co, H, W), dtype=torch.float32, device=x.device)
-        ws, nbytes = _conv3x3_ws((B, Ci, Co, H, W), CONV_FWD, x.device)
-        _lib.call('vpn_conv3x3_fwd', x, weight, y, B, Ci, Co, H, W, ws, nbytes, _lib.stream())
-        ctx.save_for_backward(x, weight)
-        return y
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_y):
-        x, weight = ctx.saved_tensors
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not need_x and not need_w:
-            return None, None
-        B, Ci, H, W = x.shape
-        Co = weight.shape[0]
-        dy = grad_y.contiguous()
-        dx = torch.empty_like(x) if need_x else None
-        dw = torch.empty_like(weight) if need_w else None
-        ws, nbytes = _conv3x3_ws((B, Ci, Co, H, W), (CONV_DX if need_x else 0) | (CONV_DW if need_w else 0), x.device)
-        _lib.call('vpn_conv3x3_bwd', dy, x, weight, dx, dw, B, Ci, Co, H, W, ws, nbytes, _lib.stream())
-        return dx, dw
-
-
-# ---- the trunk's strided convolutions (csrc/trunkstride.hip; DESIGN.md 4.20): nn.Conv2d(kernel 1, 3 or 7, any stride and
-# padding, no bias) reached through vpnet_one_resnet.py:45-57 (the stem, the stride-2 3x3 and the 1x1 downsamples), forward
-# and both gradients by the scheme of the 3x3 convolutions above
-
 CONV2D_KERNELS = (1, 3, 7)                # the kernel sizes csrc/trunkstride.hip instantiates
 
 
@@ -2176,9 +2104,8 @@ def conv2d_out_size(H, W, R, stride, padding):
 
 
 def conv2d_splits(B, C_in, C_out, H, W, R, stride, padding, product):
-    """The host rule of include/vpn_hip.h restated over the generalised M, N, K: the slices S the reduction of `product`
-    (CONV_FWD, CONV_DX, CONV_DW) is split into; 1: one launch, no workspace.  tests hold it to the library's
-    vpn_conv2d_splits."""
+    """The host rule of include/vpn_hip.h restated: the slices S the reduction of `product` (CONV_FWD, CONV_DX, CONV_DW) is
+    split into; 1: one launch, no workspace.  tests hold it to the library's vpn_conv2d_splits and vpn_conv3x3_splits."""
     OH, OW = conv2d_out_size(H, W, R, stride, padding)
     M, N, K = {CONV_FWD: (C_out, B * OH * OW, R * R * C_in), CONV_DX: (C_in, B * H * W, R * R * C_out),
                CONV_DW: (C_out, R * R * C_in, B * OH * OW)}[product]
@@ -2188,37 +2115,100 @@ def conv2d_splits(B, C_in, C_out, H, W, R, stride, padding, product):
     return min(-(-CONV_SPLIT_TARGET // tiles), CONV_MAX_SPLIT, -(-K // CONV_TILE_K))
 
 
-def _conv2d_check(x, weight, stride, padding):
-    """Everything Conv2dFunction refuses, before any launch (and before the library is loaded)."""
+def conv3x3_splits(B, C_in, C_out, H, W, product):
+    """conv2d_splits for kernel 3, stride 1, padding 1."""
+    return conv2d_splits(B, C_in, C_out, H, W, 3, 1, 1, product)
+
+
+def _conv_check(name, x, weight, kernel, kernel_ok):
+    """What Conv3x3Function and Conv2dFunction both refuse about their tensors, before any launch (and before the library is
+    loaded); `kernel`: the last two weight dimensions as the message names them, `kernel_ok`: the test they must pass."""
     if x.dim() != 4:
-        raise ValueError('conv2d: x must be (B, C_in, H, W), got %d dimensions' % x.dim())
-    if weight.dim() != 4 or weight.shape[2] != weight.shape[3]:
-        raise ValueError('conv2d: weight must be (C_out, C_in, R, R), got %s' % (tuple(weight.shape),))
-    if weight.shape[2] not in CONV2D_KERNELS:
-        raise NotImplementedError('conv2d: kernel size %d is not one of %s' % (weight.shape[2], CONV2D_KERNELS))
+        raise ValueError('%s: x must be (B, C_in, H, W), got %d dimensions' % (name, x.dim()))
+    if weight.dim() != 4 or not kernel_ok(tuple(weight.shape[2:])):
+        raise ValueError('%s: weight must be (C_out, C_in, %s), got %s' % (name, kernel, tuple(weight.shape)))
     if weight.shape[1] != x.shape[1]:
-        raise ValueError('conv2d: weight has %d input channels, x has %d (groups = 1 only)' % (weight.shape[1], x.shape[1]))
+        raise ValueError('%s: weight has %d input channels, x has %d (groups = 1 only)' % (name, weight.shape[1], x.shape[1]))
+    for which, t in (('x', x), ('weight', weight)):
+        if t.dtype != torch.float32:
+            raise NotImplementedError('%s: fp32 only (%s is %s)' % (name, which, t.dtype))
+    if x.numel() == 0 or weight.numel() == 0:
+        raise ValueError('%s: empty input' % name)
+
+
+def _conv_check_gpu(name, x, weight):
+    """The last refusal of both functions: there is no CPU path."""
+    for which, t in (('x', x), ('weight', weight)):
+        if not t.is_cuda:
+            raise ValueError('%s runs on the GPU only (%s is a %s tensor); there is no CPU path' % (name, which, t.device.type))
+
+
+def _conv2d_check(x, weight, stride, padding):
+    """Everything Conv2dFunction refuses: the shared checks, then what only a general convolution can get wrong."""
+    _conv_check('conv2d', x, weight, 'R, R', lambda k: k[0] == k[1])
+    R = weight.shape[2]
+    if R not in CONV2D_KERNELS:
+        raise NotImplementedError('conv2d: kernel size %d is not one of %s' % (R, CONV2D_KERNELS))
     if not isinstance(stride, int) or isinstance(stride, bool) or stride < 1:
         raise ValueError('conv2d: stride must be an int >= 1, got %r' % (stride,))
     if not isinstance(padding, int) or isinstance(padding, bool) or padding < 0:
         raise ValueError('conv2d: padding must be an int >= 0, got %r' % (padding,))
-    for name, t in (('x', x), ('weight', weight)):
-        if t.dtype != torch.float32:
-            raise NotImplementedError('conv2d: fp32 only (%s is %s)' % (name, t.dtype))
-    if x.numel() == 0 or weight.numel() == 0:
-        raise ValueError('conv2d: empty input')
-    R = weight.shape[2]
     if x.shape[2] + 2 * padding < R or x.shape[3] + 2 * padding < R:
         raise ValueError('conv2d: the padded image (%d + 2 x %d) x (%d + 2 x %d) is smaller than the %d x %d kernel' %
                          (x.shape[2], padding, x.shape[3], padding, R, R))
-    for name, t in (('x', x), ('weight', weight)):
-        if not t.is_cuda:
-            raise ValueError('conv2d runs on the GPU only (%s is a %s tensor); there is no CPU path' % (name, t.device.type))
+    _conv_check_gpu('conv2d', x, weight)
 
 
-def _conv2d_ws(dims, products, dev):
-    ws = _workspace('vpn_conv2d_workspace', *dims, products, dev=dev)
+# serves both entry families; it keeps the conv2d name and default because tests/test_trunkstride.py calls it that way
+def _conv2d_ws(dims, products, dev, entry='conv2d'):
+    """(workspace, bytes) of the mask `products` for the entry family `entry`, (None, 0) when no product is split."""
+    ws = _workspace('vpn_%s_workspace' % entry, *dims, products, dev=dev)
     return (ws, ws.numel() * 4) if ws.numel() else (None, 0)
+
+
+def _conv_forward(ctx, entry, x, weight, tail, out_hw):
+    """y of entry family `entry` ('conv3x3', 'conv2d'); `tail`: the dimensions its entries take after (B, C_in, C_out, H, W)."""
+    x, weight = x.contiguous(), weight.contiguous()
+    B, Ci, H, W = x.shape
+    Co = weight.shape[0]
+    dims = (B, Ci, Co, H, W) + tail
+    y = torch.empty((B, Co) + out_hw, dtype=torch.float32, device=x.device)
+    ws, nbytes = _conv2d_ws(dims, CONV_FWD, x.device, entry)
+    _lib.call('vpn_%s_fwd' % entry, x, weight, y, *dims, ws, nbytes, _lib.stream())
+    ctx.save_for_backward(x, weight)
+    ctx.dims = dims
+    return y
+
+
+def _conv_backward(ctx, entry, grad_y):
+    """(dx, dw); each is None when not needed (a frozen trunk, an input that needs no gradient)."""
+    x, weight = ctx.saved_tensors
+    need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    if not need_x and not need_w:
+        return None, None
+    dy = grad_y.contiguous()
+    dx = torch.empty_like(x) if need_x else None
+    dw = torch.empty_like(weight) if need_w else None
+    ws, nbytes = _conv2d_ws(ctx.dims, (CONV_DX if need_x else 0) | (CONV_DW if need_w else 0), x.device, entry)
+    _lib.call('vpn_%s_bwd' % entry, dy, x, weight, dx, dw, *ctx.dims, ws, nbytes, _lib.stream())
+    return dx, dw
+
+
+class Conv3x3Function(Function):
+    """y = conv2d(x, weight, stride 1, padding 1) for a 3x3 kernel without bias on csrc/trunkconv.hip.  apply(x, weight):
+    x (B, C_in, H, W), weight (C_out, C_in, 3, 3), fp32; strided and channels-last inputs are made NCHW-contiguous first.
+    Gradients for x and weight; each is skipped when not needed (a frozen trunk, an input that needs no gradient)."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        _conv_check('conv3x3', x, weight, '3, 3', lambda k: k == (3, 3))
+        _conv_check_gpu('conv3x3', x, weight)
+        return _conv_forward(ctx, 'conv3x3', x, weight, (), tuple(x.shape[2:]))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        return _conv_backward(ctx, 'conv3x3', grad_y)
 
 
 class Conv2dFunction(Function):
@@ -2230,31 +2220,10 @@ class Conv2dFunction(Function):
     @staticmethod
     def forward(ctx, x, weight, stride, padding):
         _conv2d_check(x, weight, stride, padding)
-        x, weight = x.contiguous(), weight.contiguous()
-        B, Ci, H, W = x.shape
-        Co, R = weight.shape[0], weight.shape[2]
-        OH, OW = conv2d_out_size(H, W, R, stride, padding)
-        y = torch.empty((B, Co, OH, OW), dtype=torch.float32, device=x.device)
-        ws, nbytes = _conv2d_ws((B, Ci, Co, H, W, R, stride, padding), CONV_FWD, x.device)
-        _lib.call('vpn_conv2d_fwd', x, weight, y, B, Ci, Co, H, W, R, stride, padding, ws, nbytes, _lib.stream())
-        ctx.save_for_backward(x, weight)
-        ctx.cfg = (stride, padding)
-        return y
+        R = weight.shape[2]
+        return _conv_forward(ctx, 'conv2d', x, weight, (R, stride, padding), conv2d_out_size(x.shape[2], x.shape[3], R, stride, padding))
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_y):
-        x, weight = ctx.saved_tensors
-        stride, padding = ctx.cfg
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not need_x and not need_w:
-            return None, None, None, None
-        B, Ci, H, W = x.shape
-        Co, R = weight.shape[0], weight.shape[2]
-        dy = grad_y.contiguous()
-        dx = torch.empty_like(x) if need_x else None
-        dw = torch.empty_like(weight) if need_w else None
-        ws, nbytes = _conv2d_ws((B, Ci, Co, H, W, R, stride, padding), (CONV_DX if need_x else 0) | (CONV_DW if need_w else 0),
-                                x.device)
-        _lib.call('vpn_conv2d_bwd', dy, x, weight, dx, dw, B, Ci, Co, H, W, R, stride, padding, ws, nbytes, _lib.stream())
-        return dx, dw, None, None
+        return _conv_backward(ctx, 'conv2d', grad_y) + (None, None)
