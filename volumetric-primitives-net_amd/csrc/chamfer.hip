@@ -22,6 +22,7 @@
 #include "vpn_raster_common.h"      // the tile-order rider of the training step (raster_order_wg)
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -901,6 +902,14 @@ __device__ inline float min16(const f16v& v) {
     return vmin3(vmin3(a, b, c), g, g);
 }
 
+// over 8 consecutive accumulators of a block (two adjacent row groups): 4 instructions
+template <int O>
+__device__ inline float min8(const f16v& v) {
+    const float a = __builtin_fminf(__builtin_fminf(v[O], v[O + 1]), v[O + 2]);
+    const float b = __builtin_fminf(__builtin_fminf(v[O + 3], v[O + 4]), v[O + 5]);
+    return vmin3(a, b, __builtin_fminf(v[O + 6], v[O + 7]));
+}
+
 // the same over the 32 accumulators of two blocks: 16 instructions (10 compiler-visible first-level v_min3, then 6)
 __device__ inline float min32(const f16v& u, const f16v& v) {
     const float a = __builtin_fminf(__builtin_fminf(u[0], u[1]), u[2]);
@@ -1045,6 +1054,8 @@ struct ScanJob {          // one direction of a Chamfer call
     const int32_t* qperm;                         // [B][pad32(Nq)]: the order the queries are visited in (null: natural)
     const float* tboxes;                          // fp16 filter: box per 256-target tile (vpn_chamfer_feat.h), null: no skipping
     int cand;                                     // fp16 filter: each workgroup scans its candidate targets only
+    const float* qboxes;                          // candidate form: box per 256-row tile of the QUERY cloud in its natural order
+                                                  // (= per workgroup; the centre of the ball comes from it), null: computed
 };
 
 // Both directions of a Chamfer call in ONE launch: workgroups [0, j0.G) run job 0, the rest job 1.  Launched
@@ -1094,6 +1105,7 @@ __global__ __launch_bounds__(cm_block<PREC>(), PREC == 1 ? 5 : CM_WAVES_PER_EU) 
     const int32_t* __restrict__ qperm = PREC == 2 ? (other ? j1.qperm : j0.qperm) : nullptr;   // the fp16 filter only
     const float* __restrict__ tboxes = PREC == 2 ? (other ? j1.tboxes : j0.tboxes) : nullptr;
     const int cand = PREC == 2 ? (other ? j1.cand : j0.cand) : 0;
+    const float* __restrict__ qboxes = PREC == 2 ? (other ? j1.qboxes : j0.qboxes) : nullptr;
     // The workgroup's list of undecided queries (epilogue): (query, sqrt(m2)) and (query number, index).  A candidate
     // workgroup keeps the fp32 planes of its candidates in the same bytes until its exact finish has read them.
     constexpr int QPW = cm_block<PREC>() / 2;                       // queries per workgroup = capacity of the list
@@ -1241,6 +1253,35 @@ __global__ __launch_bounds__(cm_block<PREC>(), PREC == 1 ? 5 : CM_WAVES_PER_EU) 
         }                                                                                      \
         blk = best < before ? (t0) + (blkc << 6) : blk;   /* the tile improved this lane's minimum */ \
     }
+// The candidate loop tracks QUARTERS of a pair: unit q of a pair is the 8 accumulators of one block that a lane holds
+// for two adjacent row groups, i.e. what one half-wave saw of 16 consecutive compact positions.  Four 4-instruction
+// trees and four updates per pair instead of one tree of 16 and one update (32 VALU against 20, over the 2-5 pairs a
+// candidate workgroup scans), for an exact finish of 4 targets per lane instead of 16.
+#define CM_QUADS(oa, ob, J0, J1, J2, J3)                                                       \
+    {                                                                                          \
+        const f16v accA = block(oa), accB = block(ob);                                         \
+        const float q0 = min8<0>(accA), q1 = min8<8>(accA), q2 = min8<0>(accB), q3 = min8<8>(accB); \
+        CM_UPDATE_C(q0, J0)                                                                    \
+        CM_UPDATE_C(q1, J1)                                                                    \
+        CM_UPDATE_C(q2, J2)                                                                    \
+        CM_UPDATE_C(q3, J3)                                                                    \
+    }
+#define CM_SCAN_TILE_Q(T, t0, nblk)                                                            \
+    {                                                                                          \
+        const float before = best;                                                             \
+        float4 a0 = rd(T, 0), a1 = rd(T, 1), b0 = rd(T, 2), b1 = rd(T, 3);                     \
+        CM_QUADS(a0, a1, 0, 1, 2, 3)                                                           \
+        if (nblk > 2) {                                                                        \
+            a0 = rd(T, 4); a1 = rd(T, 5);                                                      \
+            CM_QUADS(b0, b1, 4, 5, 6, 7)                                                       \
+            if (nblk > 4) {                                                                    \
+                b0 = rd(T, 6); b1 = rd(T, 7);                                                  \
+                CM_QUADS(a0, a1, 8, 9, 10, 11)                                                 \
+                if (nblk > 6) CM_QUADS(b0, b1, 12, 13, 14, 15)                                 \
+            }                                                                                  \
+        }                                                                                      \
+        blk = best < before ? (t0) + (blkc << 4) : blk;   /* the tile improved this lane's minimum */ \
+    }
         int buf = 0, blkc = 0;
         if (cand) {
             // ---- Candidate prologue.  The workgroup's queries lie in a ball (c, rho); with d_c the distance
@@ -1252,22 +1293,40 @@ __global__ __launch_bounds__(cm_block<PREC>(), PREC == 1 ? 5 : CM_WAVES_PER_EU) 
             __shared__ int s_cwn[2][CM_WAVES16];                    // candidates per wave of a pass (two passes in flight)
             const float inf = __builtin_inff();
             auto uni = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
-            {
-                const float l0 = feat_wave_minmax<false>(ax), l1 = feat_wave_minmax<false>(ay), l2 = feat_wave_minmax<false>(az);
-                const float h0 = feat_wave_minmax<true>(ax), h1 = feat_wave_minmax<true>(ay), h2 = feat_wave_minmax<true>(az);
-                if (lane == 0) {
-                    s_cred[0][wave] = l0; s_cred[1][wave] = l1; s_cred[2][wave] = l2;
-                    s_cred[3][wave] = h0; s_cred[4][wave] = h1; s_cred[5][wave] = h2;
+            float cc[3];                                            // the centre: the same stored fp32 values in every lane
+            // The workgroup's queries are tile bx of their cloud, whose box the feature launch has stored (natural order
+            // only).  Only the centre is taken from it, and only if all six values are finite (a tile shared by two writers
+            // has the box of all space); rho and d_c below come from the points themselves, so any centre is valid.
+            bool boxed = false;                                     // workgroup-uniform
+            if (qboxes && !qperm) {
+                const float* qbox = qboxes + ((size_t)b * (((Nq + 63) & ~63) >> 5) + bx) * CFEAT_BOXF;   // feat_tile_box
+                const float4 bl = *reinterpret_cast<const float4*>(qbox);
+                const float2 bh = *reinterpret_cast<const float2*>(qbox + 4);
+                const float lo[3] = {bl.x, bl.y, bl.z}, hi[3] = {bl.w, bh.x, bh.y};
+                boxed = true;
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    boxed = boxed && fabsf(lo[a]) < inf && fabsf(hi[a]) < inf;
+                    cc[a] = uni((lo[a] + hi[a]) * 0.5f);
                 }
             }
-            __syncthreads();
-            float cc[3];                                            // the centre: the same stored fp32 values in every lane
+            if (!boxed) {
+                {
+                    const float l0 = feat_wave_minmax<false>(ax), l1 = feat_wave_minmax<false>(ay), l2 = feat_wave_minmax<false>(az);
+                    const float h0 = feat_wave_minmax<true>(ax), h1 = feat_wave_minmax<true>(ay), h2 = feat_wave_minmax<true>(az);
+                    if (lane == 0) {
+                        s_cred[0][wave] = l0; s_cred[1][wave] = l1; s_cred[2][wave] = l2;
+                        s_cred[3][wave] = h0; s_cred[4][wave] = h1; s_cred[5][wave] = h2;
+                    }
+                }
+                __syncthreads();
 #pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                float l = s_cred[a][0], h = s_cred[3 + a][0];
+                for (int a = 0; a < 3; ++a) {
+                    float l = s_cred[a][0], h = s_cred[3 + a][0];
 #pragma unroll
-                for (int w = 1; w < CM_WAVES16; ++w) { l = fminf(l, s_cred[a][w]); h = fmaxf(h, s_cred[3 + a][w]); }
-                cc[a] = uni((l + h) * 0.5f);
+                    for (int w = 1; w < CM_WAVES16; ++w) { l = fminf(l, s_cred[a][w]); h = fmaxf(h, s_cred[3 + a][w]); }
+                    cc[a] = uni((l + h) * 0.5f);
+                }
             }
             const int n4 = Ntp >> 2;
             const float4* f4 = reinterpret_cast<const float4*>(Fb);  // planes x, y, z at f4 + {0, 1, 2} * n4
@@ -1357,11 +1416,11 @@ __global__ __launch_bounds__(cm_block<PREC>(), PREC == 1 ? 5 : CM_WAVES_PER_EU) 
 #endif
         if (cpad) {
             // ---- candidate loop: the compact rows are all in LDS (no fetch, no stash, no barrier); blocks and cells are
-            // numbered by compact position, two "tiles" of 256 rows at the most
+            // numbered by compact position, two "tiles" of 256 rows at the most; cells of CCAND_CELL positions
             for (int t0 = 0; t0 < cpad; t0 += CM_TILE16) {
                 const int nblk = min(CM_TILE16, cpad - t0) >> 5;
                 const unsigned char* T = &tileH16[(t0 + jq) * CM_ROWB + half * 16];
-                CM_SCAN_TILE(T, t0, nblk)
+                CM_SCAN_TILE_Q(T, t0, nblk)
             }
         } else {
         Pre pre = fetch(0);
@@ -1392,6 +1451,8 @@ __global__ __launch_bounds__(cm_block<PREC>(), PREC == 1 ? 5 : CM_WAVES_PER_EU) 
             __syncthreads();
         }
         }
+#undef CM_SCAN_TILE_Q
+#undef CM_QUADS
 #undef CM_SCAN_TILE
 #undef CM_PAIR
     } else     if constexpr (PREC == 1) {
@@ -1547,122 +1608,135 @@ __global__ __launch_bounds__(cm_block<PREC>(), PREC == 1 ? 5 : CM_WAVES_PER_EU) 
     // the smallest filtered minimum over both half-waves of the query; V2 = the smallest filtered minimum over ALL other
     // cells (the loser's best, the winner's second).  Only the winner cell is evaluated exactly, its CM_CELL/2 targets
     // split over the two lanes of the query: half of the exact work of evaluating the whole block (or pair of blocks).
-    constexpr int CM_CELL = PREC == 2 ? 64 : 32;       // targets per tracked unit: the fp16 loop tracks pairs of blocks
-    constexpr int NT = CM_CELL / 4;                    // exact evaluations per lane
-    int K, hw;
-    float Bv, V2;
-    {
-        const float ob = __shfl_xor(best, 32, 64), os = __shfl_xor(second, 32, 64);
-        const int ok = __shfl_xor(blk, 32, 64);
-        // lexicographic (value, block, half): both lanes of the query reach the same verdict
-        const bool mine = best < ob || (best == ob && (blk < ok || (blk == ok && half == 0)));
-        Bv = mine ? best : ob;
-        K = mine ? blk : ok;
-        hw = mine ? half : half ^ 1;
-        V2 = mine ? fminf(second, ob) : fminf(os, best);
-    }
-    float d2[NT];
-    float m2 = __builtin_inff();
-#ifdef VPN_CHAMFER_DEBUG
-    if (K < 0 || K + CM_CELL > Ntp || (K & (CM_CELL - 1))) atomicAdd(&g_dbg[7], 1ull);    // the cell index the gather below trusts
-#endif
-    // K is a multiple of CM_CELL below Ntp by construction (tile base + unit number inside the tile; Ntp is a multiple
-    // of 64); the clamp costs one instruction per query and keeps the gather inside the padded planes whatever
-    // happened upstream
-    // (a candidate workgroup: K is a compact position below cpad, the cell's targets come from the compact planes in LDS
-    // and the padding starts at position ccount)
-    const int nreal = cpad ? ccount : Nt;
-    K = min(max(K, 0), (cpad ? cpad : Ntp) - CM_CELL);
-    // this lane's targets: groups g = half * NT/4 + j (j < NT/4) of 4 consecutive targets at K + 8 g + 4 hw
-    const int base = K + half * (2 * NT) + 4 * hw;
-    {
-        float4 X[NT / 4], Y[NT / 4], Z[NT / 4];
-#pragma unroll
-        for (int v = 0; v < NT / 4; ++v) {
-            if (PREC == 2 && cpad) {                                // workgroup-uniform
-                X[v] = *reinterpret_cast<const float4*>(s_cpl + base + 8 * v);
-                Y[v] = *reinterpret_cast<const float4*>(s_cpl + CCAND_CAP + base + 8 * v);
-                Z[v] = *reinterpret_cast<const float4*>(s_cpl + 2 * CCAND_CAP + base + 8 * v);
-            } else {
-                X[v] = *reinterpret_cast<const float4*>(Fb + base + 8 * v);
-                Y[v] = *reinterpret_cast<const float4*>(Fb + (size_t)Ntp + base + 8 * v);
-                Z[v] = *reinterpret_cast<const float4*>(Fb + 2 * (size_t)Ntp + base + 8 * v);
-            }
-        }
-#pragma unroll
-        for (int v = 0; v < NT / 4; ++v) {
-            const float xs[4] = {X[v].x, X[v].y, X[v].z, X[v].w}, ys[4] = {Y[v].x, Y[v].y, Y[v].z, Y[v].w};
-            const float zs[4] = {Z[v].x, Z[v].y, Z[v].z, Z[v].w};
-#pragma unroll
-            for (int w = 0; w < 4; ++w) d2[v * 4 + w] = dist2_exact(ax, ay, az, xs[w], ys[w], zs[w]);
-        }
-        // padding targets (coordinates 0) are masked only by the waves whose winner cell reaches into the padding:
-        // three instructions per target that the other waves (all of them when Nt is a multiple of 64) skip
-        if (__ballot(K + CM_CELL > nreal)) {
-#pragma unroll
-            for (int e = 0; e < NT; ++e) d2[e] += (base + 8 * (e >> 2) + (e & 3) < nreal) ? 0.0f : __builtin_inff();
-        }
-#pragma unroll
-        for (int e = 0; e < NT; ++e) m2 = fminf(m2, d2[e]);
-    }
-    m2 = fminf(m2, __shfl_xor(m2, 32, 64));
-    // t = d2 - |a|^2 within E; exact d2 within 4e-7 relative: a block whose filtered minimum lies outside `band`
-    // can neither win nor tie.  Otherwise the query is undecided here and goes to the fix-up list.
+    // (the fp16 tile loop tracks pairs of blocks, CM_CELL = 64; its candidate loop quarters of a pair, CM_CELL = CCAND_CELL.
+    // The finish is exact for any partition of the scanned targets into cells: DESIGN 4.1.)
     static_assert(CFEAT_SLOTS <= 64, "one slot per lane");
     // norms are >= 0: their bit patterns order like unsigned integers (v_max_u32 takes the DPP operand directly and
     // needs no NaN quieting; a NaN norm has the largest pattern and so survives, as it must)
     const float nb = __uint_as_float(wave_max_bits(lane < CFEAT_SLOTS ? nmax[b * CFEAT_SLOTS + lane] : 0u));
     const float na = ax * ax + ay * ay + az * az;
     const float sna = sqrt_up(na), snb = sqrt_up(nb);                           // bounds only: no IEEE sqrt sequences
-    float E = (PREC == 2 ? CM_EPS_F16 : (PREC == 1 ? CM_EPS_BF16 : CM_EPS)) * (2.0f * sna * snb + nb + na) * (1.0f + 1.0e-6f);
-    if (PREC == 2) {
-        E += 5.9604644775390625e-08f * 1.7320509f * (sna + snb);               // absolute floor of the fp16 pieces
-        Bv *= CM_INV_S16SQ; V2 *= CM_INV_S16SQ;                                 // the fp16 filter works on S x: values scaled by S^2
-    }
-    // m2 is exact, so the runner-up is compared with it rather than with the filtered value of the best block:
-    // only the runner-up's own filter error E remains (the band was 2E before; this halves the undecided queries).
-    // 4e-6 m2 covers the rounding of m2 and of |a|^2 and the width of a sqrt bucket.
-    const float s = sqrtf(m2);                                      // IEEE: this one is the result
-    const float band = E + 4.0e-6f * (m2 + na);                     // any target of the cloud (consistency of the best block)
-    // possible winners: a runner-up that can win or tie has exact d2 <= m2 (1 + 1e-6), i.e. a real d2 <= m2 (1 + 1.4e-6),
-    // and filters to at most that - |a|^2 + E_near; against the computed m2 - na (|a|^2 good to 3 ulp, the difference to
-    // 1): 4e-6 m2 + 4e-7 na covers it (|a|^2 used to be charged 4e-6 too: 2e-6 of a 4e-6 band for a query half a unit from
-    // the origin -- and 40 % of the undecided queries of direction 2)
-    const float band_near = near_error(PREC == 2 ? CM_EPS_F16 : (PREC == 1 ? CM_EPS_BF16 : CM_EPS), PREC == 2 ? 5.9604644775390625e-08f : 0.0f,
-                                       na, sna, s * (1.0f + 1.0e-7f), E) + (4.0e-6f * m2 + 4.0e-7f * na);
-    bool ambiguous = !(V2 > (m2 - na) + band_near) || !(m2 - na <= Bv + band);
-    if (PREC == 2) ambiguous |= !(nb <= CM_DOMAIN16 && na <= CM_DOMAIN16);     // outside the fp16 filter's range: exact fix-up
-    // lowest index attaining the minimum; a different d2 can only share the sqrt if it lies within a few ulp
-    // of it, which is rare: only then are the sqrt values compared
-    const float lim = m2 * (1.0f + 1.0e-6f);
-    int li = NT;                                                    // position inside this lane's targets (inline constants)
+    float s;                                                        // the query's distance, its index and whether the fix-up decides
+    int idx;
+    bool ambiguous;
+    auto finish = [&](auto cell) {
+        constexpr int CM_CELL = decltype(cell)::value; // targets per tracked unit
+        constexpr int NT = CM_CELL / 4;                // exact evaluations per lane
+        int K, hw;
+        float Bv, V2;
+        {
+            const float ob = __shfl_xor(best, 32, 64), os = __shfl_xor(second, 32, 64);
+            const int ok = __shfl_xor(blk, 32, 64);
+            // lexicographic (value, block, half): both lanes of the query reach the same verdict
+            const bool mine = best < ob || (best == ob && (blk < ok || (blk == ok && half == 0)));
+            Bv = mine ? best : ob;
+            K = mine ? blk : ok;
+            hw = mine ? half : half ^ 1;
+            V2 = mine ? fminf(second, ob) : fminf(os, best);
+        }
+        float d2[NT];
+        float m2 = __builtin_inff();
+#ifdef VPN_CHAMFER_DEBUG
+        if (K < 0 || K + CM_CELL > Ntp || (K & (CM_CELL - 1))) atomicAdd(&g_dbg[7], 1ull);    // the cell index the gather below trusts
+#endif
+        // K is a multiple of CM_CELL below Ntp by construction (tile base + unit number inside the tile; Ntp is a multiple
+        // of 64); the clamp costs one instruction per query and keeps the gather inside the padded planes whatever
+        // happened upstream
+        // (a candidate workgroup: K is a compact position below cpad, the cell's targets come from the compact planes in LDS
+        // and the padding starts at position ccount)
+        const int nreal = cpad ? ccount : Nt;
+        K = min(max(K, 0), (cpad ? cpad : Ntp) - CM_CELL);
+        // this lane's targets: groups g = half * NT/4 + j (j < NT/4) of 4 consecutive targets at K + 8 g + 4 hw
+        const int base = K + half * (2 * NT) + 4 * hw;
+        {
+            float4 X[NT / 4], Y[NT / 4], Z[NT / 4];
 #pragma unroll
-    for (int e = NT - 1; e >= 0; --e)
-        if (d2[e] == m2) li = e;                                    // target index grows with e: the lowest wins
-    int idx = li < NT ? base + 8 * (li >> 2) + (li & 3) : 0x7fffffff;
-    // near tie: some d2 with m2 < d2 <= lim.  d2 >= 0, so the bit patterns order like the values: the smallest
-    // (bits(d2) - bits(m2) - 1) as an unsigned number is below bits(lim) - bits(m2) exactly then (equal values wrap
-    // to 0xffffffff; a NaN d2 has a larger pattern than any finite lim).  One subtraction per target and a min3 tree
-    // instead of three compares and two mask operations per target.
-    bool near_tie;
-    {
-        const unsigned mb1 = __float_as_uint(m2) + 1u;
-        unsigned gm = 0xffffffffu;
+            for (int v = 0; v < NT / 4; ++v) {
+                if (PREC == 2 && cpad) {                                // workgroup-uniform
+                    X[v] = *reinterpret_cast<const float4*>(s_cpl + base + 8 * v);
+                    Y[v] = *reinterpret_cast<const float4*>(s_cpl + CCAND_CAP + base + 8 * v);
+                    Z[v] = *reinterpret_cast<const float4*>(s_cpl + 2 * CCAND_CAP + base + 8 * v);
+                } else {
+                    X[v] = *reinterpret_cast<const float4*>(Fb + base + 8 * v);
+                    Y[v] = *reinterpret_cast<const float4*>(Fb + (size_t)Ntp + base + 8 * v);
+                    Z[v] = *reinterpret_cast<const float4*>(Fb + 2 * (size_t)Ntp + base + 8 * v);
+                }
+            }
 #pragma unroll
-        for (int e = 0; e < NT; e += 2)                              // the compiler forms v_min3_u32
-            gm = min(gm, min(__float_as_uint(d2[e]) - mb1, __float_as_uint(d2[e + 1]) - mb1));
-        near_tie = m2 < __builtin_inff() && gm < __float_as_uint(lim) - __float_as_uint(m2);
-    }
-    if (__ballot(near_tie)) {
+            for (int v = 0; v < NT / 4; ++v) {
+                const float xs[4] = {X[v].x, X[v].y, X[v].z, X[v].w}, ys[4] = {Y[v].x, Y[v].y, Y[v].z, Y[v].w};
+                const float zs[4] = {Z[v].x, Z[v].y, Z[v].z, Z[v].w};
+#pragma unroll
+                for (int w = 0; w < 4; ++w) d2[v * 4 + w] = dist2_exact(ax, ay, az, xs[w], ys[w], zs[w]);
+            }
+            // padding targets (coordinates 0) are masked only by the waves whose winner cell reaches into the padding:
+            // three instructions per target that the other waves (all of them when Nt is a multiple of 64) skip
+            if (__ballot(K + CM_CELL > nreal)) {
+#pragma unroll
+                for (int e = 0; e < NT; ++e) d2[e] += (base + 8 * (e >> 2) + (e & 3) < nreal) ? 0.0f : __builtin_inff();
+            }
+#pragma unroll
+            for (int e = 0; e < NT; ++e) m2 = fminf(m2, d2[e]);
+        }
+        m2 = fminf(m2, __shfl_xor(m2, 32, 64));
+        // t = d2 - |a|^2 within E; exact d2 within 4e-7 relative: a block whose filtered minimum lies outside `band`
+        // can neither win nor tie.  Otherwise the query is undecided here and goes to the fix-up list.
+        float E = (PREC == 2 ? CM_EPS_F16 : (PREC == 1 ? CM_EPS_BF16 : CM_EPS)) * (2.0f * sna * snb + nb + na) * (1.0f + 1.0e-6f);
+        if (PREC == 2) {
+            E += 5.9604644775390625e-08f * 1.7320509f * (sna + snb);               // absolute floor of the fp16 pieces
+            Bv *= CM_INV_S16SQ; V2 *= CM_INV_S16SQ;                                 // the fp16 filter works on S x: values scaled by S^2
+        }
+        // m2 is exact, so the runner-up is compared with it rather than with the filtered value of the best block:
+        // only the runner-up's own filter error E remains (the band was 2E before; this halves the undecided queries).
+        // 4e-6 m2 covers the rounding of m2 and of |a|^2 and the width of a sqrt bucket.
+        s = sqrtf(m2);                                                  // IEEE: this one is the result
+        const float band = E + 4.0e-6f * (m2 + na);                     // any target of the cloud (consistency of the best block)
+        // possible winners: a runner-up that can win or tie has exact d2 <= m2 (1 + 1e-6), i.e. a real d2 <= m2 (1 + 1.4e-6),
+        // and filters to at most that - |a|^2 + E_near; against the computed m2 - na (|a|^2 good to 3 ulp, the difference to
+        // 1): 4e-6 m2 + 4e-7 na covers it (|a|^2 used to be charged 4e-6 too: 2e-6 of a 4e-6 band for a query half a unit from
+        // the origin -- and 40 % of the undecided queries of direction 2)
+        const float band_near = near_error(PREC == 2 ? CM_EPS_F16 : (PREC == 1 ? CM_EPS_BF16 : CM_EPS), PREC == 2 ? 5.9604644775390625e-08f : 0.0f,
+                                           na, sna, s * (1.0f + 1.0e-7f), E) + (4.0e-6f * m2 + 4.0e-7f * na);
+        ambiguous = !(V2 > (m2 - na) + band_near) || !(m2 - na <= Bv + band);
+        if (PREC == 2) ambiguous |= !(nb <= CM_DOMAIN16 && na <= CM_DOMAIN16);     // outside the fp16 filter's range: exact fix-up
+        // lowest index attaining the minimum; a different d2 can only share the sqrt if it lies within a few ulp
+        // of it, which is rare: only then are the sqrt values compared
+        const float lim = m2 * (1.0f + 1.0e-6f);
+        int li = NT;                                                    // position inside this lane's targets (inline constants)
 #pragma unroll
         for (int e = NT - 1; e >= 0; --e)
-            if (d2[e] <= lim && sqrtf(d2[e]) == s) idx = min(idx, base + 8 * (e >> 2) + (e & 3));
-    }
-    idx = min(idx, __shfl_xor(idx, 32, 64));
-    if (PREC == 2 && cpad) {
-        // compaction is monotone: the lowest position among equals is the lowest original index among equals
-        idx = idx < cpad ? (int)s_cidx[idx] : idx;
-        __syncthreads();                                            // every wave has read the compact planes: the list may overwrite them
+            if (d2[e] == m2) li = e;                                    // target index grows with e: the lowest wins
+        idx = li < NT ? base + 8 * (li >> 2) + (li & 3) : 0x7fffffff;
+        // near tie: some d2 with m2 < d2 <= lim.  d2 >= 0, so the bit patterns order like the values: the smallest
+        // (bits(d2) - bits(m2) - 1) as an unsigned number is below bits(lim) - bits(m2) exactly then (equal values wrap
+        // to 0xffffffff; a NaN d2 has a larger pattern than any finite lim).  One subtraction per target and a min3 tree
+        // instead of three compares and two mask operations per target.
+        bool near_tie;
+        {
+            const unsigned mb1 = __float_as_uint(m2) + 1u;
+            unsigned gm = 0xffffffffu;
+#pragma unroll
+            for (int e = 0; e < NT; e += 2)                              // the compiler forms v_min3_u32
+                gm = min(gm, min(__float_as_uint(d2[e]) - mb1, __float_as_uint(d2[e + 1]) - mb1));
+            near_tie = m2 < __builtin_inff() && gm < __float_as_uint(lim) - __float_as_uint(m2);
+        }
+        if (__ballot(near_tie)) {
+#pragma unroll
+            for (int e = NT - 1; e >= 0; --e)
+                if (d2[e] <= lim && sqrtf(d2[e]) == s) idx = min(idx, base + 8 * (e >> 2) + (e & 3));
+        }
+        idx = min(idx, __shfl_xor(idx, 32, 64));
+        if (PREC == 2 && cpad) {
+            // compaction is monotone: the lowest position among equals is the lowest original index among equals
+            idx = idx < cpad ? (int)s_cidx[idx] : idx;
+            __syncthreads();                                            // every wave has read the compact planes: the list may overwrite them
+        }
+    };
+    if constexpr (PREC == 2) {
+        if (cpad) finish(std::integral_constant<int, CCAND_CELL>{});             // workgroup-uniform
+        else finish(std::integral_constant<int, 64>{});
+    } else {
+        finish(std::integral_constant<int, 32>{});
     }
     // Decided queries store their result.  An undecided one goes on the WORKGROUP's list in LDS as (query, sqrt(m2),
     // index inside the best cell) and is resolved exactly by this workgroup before it exits (fixup_own): no list in
@@ -2109,10 +2183,11 @@ static int mfma_both(const float* p1, const float* p2, int B, int N, int M, floa
     {
         const int qpw = prec == 2 ? 32 * CM_WAVES16 : 128;          // queries per workgroup
         const int gx1 = (N + qpw - 1) / qpw, gx2 = (M + qpw - 1) / qpw;
+        // (its queries are p1 in natural order: the tile boxes of p1, written for direction 2's skipping, are its workgroups')
         const ScanJob s1{p1, w2.F, w2.H, w2.nmax, N, M, w2.Ntp, gx1, gx1 * B, d1, i1, w2.wgsum, nullptr, nullptr,   // p1 against p2
-                         cand(N, M, nullptr)};
+                         cand(N, M, nullptr), f1.tboxes};
         const ScanJob s2{p2, w1.F, w1.H, w1.nmax, M, N, w1.Ntp, gx2, gx2 * B, d2, i2, w1.wgsum,                     // p2 against p1
-                         f2.perm, f1.tboxes, cand(M, N, f1.tboxes)};
+                         f2.perm, f1.tboxes, cand(M, N, f1.tboxes), nullptr};
         const bool long_first = (long long)N > (long long)M;       // direction 2 scans the N targets: more work per workgroup
         const ScanJob& ja = long_first ? s2 : s1;
         const ScanJob& jb = long_first ? s1 : s2;

@@ -165,6 +165,7 @@ constexpr int CORD_MAX = 2048;           // largest cloud one workgroup orders (
 // targets inside a ball around them.  Taken by a direction without tile boxes from CSKIP_MIN_TARGETS queries on.
 constexpr int CCAND_CAP = 512;           // candidates per workgroup at most (= the two 256-row LDS tiles as one buffer)
 constexpr int CCAND_MAX_TARGETS = 65535; // candidate indices are kept as 16-bit numbers
+constexpr int CCAND_CELL = 16;           // compact positions per tracked cell of the candidate loop (a quarter of a pair of blocks)
 
 // box entry of tile t of sample b of a cloud with Np padded rows (the workspace carves Np / 32 entries per sample)
 __device__ inline float* feat_tile_box(float* boxes, int Np, int b, int t) {
