@@ -911,6 +911,48 @@ int vpn_bn_act_bwd(const float* dy, const float* x, const float* y, const float*
                    const float* stat_var, int B, int C, int H, int W, int training, float eps, int relu, float* dx,
                    float* d_residual, float* d_weight, float* d_bias, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the trunk's stem: batch norm, ReLU and MaxPool2d(3, 2, 1) as ONE op, forward and backward (the tp_ kernels of
+ * csrc/trunknorm.hip; `maxpool(relu(bn1(conv1(x))))` of the torchvision ResNet-18).  The pool is fixed:
+ * kernel 3, stride 2, padding 1, dilation 1, the only pool of the reference's networks.  x, dx: [B,C,H,W]; p, dp: [B,C,PH,PW]
+ * with PH = (H - 1) / 2 + 1, PW = (W - 1) / 2 + 1; idx: [B,C,PH,PW] uint8.  All DEVICE, fp32 but idx, contiguous, 4-byte
+ * aligned (idx: any).  Window (ph, pw) covers rows 2 ph - 1 .. 2 ph + 1 and columns 2 pw - 1 .. 2 pw + 1; taps outside the map
+ * take no part.  y = max((x - mean) * invstd * weight + bias, 0) per tap with the roundings of vpn_bn_act_fwd, p = the
+ * maximum of the window's taps, idx = the tap number r * 3 + s (0 .. 8) of the winner: taps are scanned r then s ascending
+ * and a tap replaces the best so far only if it is greater or is NaN (ATen's rule: the first maximum wins).  The full-size
+ * y is never written.  The windows and the backward access x and dx 16 bytes at a time when W is a multiple of 4 and x (and
+ * dx) is 16-byte aligned, the statistics when H * W is and x is aligned; element accesses otherwise (decided per call, no
+ * error).  No host synchronisation, nothing allocated, no atomics: bit-equal from run to run, capturable.  Added without a
+ * change of VPN_ABI_VERSION.
+ * vpn_bn_pool_workspace: C * ceil(N / VPN_BN_SLICE) * 2 floats in bytes, N = B * H * W; 0 for sizes the entries refuse.
+ * vpn_bn_pool_fwd, training != 0: the statistics of vpn_bn_act_fwd by the same code: save_mean, save_invstd [C] written,
+ *   running_mean / running_var (each may be NULL) and num_batches_tracked (int64, may be NULL) updated, all bit-equal to
+ *   what vpn_bn_act_fwd writes for the same x.  N <= VPN_BN_ONE_PASS_MAX: ONE launch (the channel's slab stays in LDS between
+ *   the statistics and the windows), no workspace (may be NULL).  Larger N: TWO launches, the statistics launch of
+ *   vpn_bn_act_fwd over slices of VPN_BN_SLICE elements into the workspace (4-byte aligned, uninitialised), then one over
+ *   slices of VPN_BN_POOL_SLICE pooled outputs that merges them and writes p and idx.  training == 0: ONE launch on the
+ *   running statistics; save_mean / save_invstd / num_batches_tracked / workspace are not touched (may be NULL).
+ *   weight, bias: [C] or NULL (1 and 0).  Written: p, idx and the statistics named above, nothing else.
+ * vpn_bn_pool_bwd: the upstream gradient of pixel (h, w) is g = sum dp[ph,pw] * [p[ph,pw] > 0] over the at most four windows
+ *   that contain the pixel and whose idx names it, ph then pw ascending; then the arithmetic of vpn_bn_act_bwd: d_bias =
+ *   sum g, d_weight = sum g * xhat, dx = weight * invstd * (g - d_bias / N - xhat * d_weight / N); training == 0: stat_mean /
+ *   stat_var = running_mean / running_var and dx = g * weight / sqrt(running_var + eps).  Reads dp, p, idx, x and the two
+ *   statistics.  At most TWO launches for every N: the two sums per slice of VPN_BN_SLICE elements into the workspace, then
+ *   their merge (the order of vpn_bn_act_bwd) and dx; ONE when training == 0 and d_weight and d_bias are NULL (no workspace
+ *   needed then).  dx, d_weight, d_bias: each may be NULL and is then neither computed nor written; all NULL: nothing is
+ *   launched.
+ * Non-positive sizes, a required pointer that is NULL, N == 1 in training, eps < 0, momentum outside [0, 1], a needed
+ * workspace that is missing, too small or misaligned: VPN_E_BADARG.  N >= 2^31, more than 65535 slices of either kind:
+ * VPN_E_TOOBIG.  Both before any HIP call. */
+#define VPN_BN_POOL_SLICE 512          /* pooled outputs per workgroup of the pooling launch: 256 lanes x 2 */
+size_t vpn_bn_pool_workspace(int B, int C, int H, int W);
+int vpn_bn_pool_fwd(const float* x, const float* weight, const float* bias, float* running_mean, float* running_var,
+                    long long* num_batches_tracked, int B, int C, int H, int W, int training, float momentum, float eps,
+                    float* p, unsigned char* idx, float* save_mean, float* save_invstd, void* workspace, size_t workspace_bytes,
+                    void* stream);
+int vpn_bn_pool_bwd(const float* dp, const float* x, const float* p, const unsigned char* idx, const float* weight,
+                    const float* stat_mean, const float* stat_var, int B, int C, int H, int W, int training, float eps,
+                    float* dx, float* d_weight, float* d_bias, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the trunk's 3x3 convolutions (csrc/trunkconv.hip): kernel 3x3, stride 1, padding 1, dilation 1,
  * groups 1, no bias, as an implicit GEMM on the f32-input MFMA: exact fp32 products, one fixed summation order.  All tensors
  * DEVICE fp32, contiguous, 4-byte aligned: x [B,C_in,H,W], w [C_out,C_in,3,3], y and dy [B,C_out,H,W], dx as x, dw as w.  Any

@@ -1,5 +1,6 @@
 // trunknorm.hip — the trunk's norm / add / ReLU ring (gfx950): batch norm, the residual add and the ReLU of a ResNet-18
-// site as ONE op, forward and backward.
+// site as ONE op, forward and backward, and the stem's form of it that also holds the 3x3 stride-2 max
+// pool (the tp_ kernels below).
 //
 // Replaces, around the convolutions of the reference's torchvision trunk (vpnet_one_resnet.py:21, vpnet_two_resnet.py:21-22,
 // sdnet.py:13), `relu(bn1(.))`, `bn2(.)`, `out += identity; relu(out)` and the downsample branch's norm: 20 training-mode
@@ -103,21 +104,17 @@ __device__ inline float tn_act(float x, float mean, float invstd, float gamma, f
     return (x - mean) * invstd * gamma + beta;
 }
 
-// ---- forward, one-pass regime: grid C, one workgroup (BLOCK = 64: one wave) per channel.  A work-item reads back from
-// LDS only what it wrote itself, so the slab needs no barrier.
+// the statistics of a channel whose slab fits LDS (xc: the channel's first element): the slab filled in unit order, then
+// the mean, the biased variance and invstd, the same in every work-item
 template <int BLOCK, int V>
-__global__ __launch_bounds__(BLOCK) void tn_fwd_onepass_kernel(TnShape s, TnFwd a) {
-    constexpr int SLAB = BLOCK == 64 ? TN_SMALL : TN_MAX;      // the one-wave form leaves the CU's LDS to other workgroups
-    __shared__ __attribute__((aligned(16))) float slab[SLAB];
-    __shared__ float red[2 * (TN_BLOCK / 64)];
-    const int c = blockIdx.x, tid = threadIdx.x;
-    if (s.N > SLAB) return;                         // the host never asks: nothing outside the slab either way
-    const size_t chan = (size_t)c * s.HW;
+__device__ inline void tn_slab_stats(const TnShape& s, const float* xc, float eps, float* slab, float* red, float& mean, float& var,
+                                     float& invstd) {
+    const int tid = threadIdx.x;
     float sum = 0.0f, m2 = 0.0f;
     {
         TnWalk k(tid, s.RU);
         for (int u = tid; u < s.NU; u += BLOCK, k.step(s)) {
-            const Vec<V> r = ldv<V>(a.x + chan + k.at<V>(s));
+            const Vec<V> r = ldv<V>(xc + k.at<V>(s));
             stv<V>(slab + (size_t)u * V, r);
 #pragma unroll
             for (int j = 0; j < V; ++j) sum += r.v[j];
@@ -135,9 +132,23 @@ __global__ __launch_bounds__(BLOCK) void tn_fwd_onepass_kernel(TnShape s, TnFwd 
     }
     block_sum2<BLOCK>(rs, m2, red);
     const float dm = rs / (float)s.N;
-    const float mean = mean0 + dm;
-    const float var = fmaxf(m2 - rs * dm, 0.0f) / (float)s.N;
-    const float invstd = 1.0f / sqrtf(var + a.eps);
+    mean = mean0 + dm;
+    var = fmaxf(m2 - rs * dm, 0.0f) / (float)s.N;
+    invstd = 1.0f / sqrtf(var + eps);
+}
+
+// ---- forward, one-pass regime: grid C, one workgroup (BLOCK = 64: one wave) per channel.  A work-item reads back from
+// LDS only what it wrote itself, so the slab needs no barrier.
+template <int BLOCK, int V>
+__global__ __launch_bounds__(BLOCK) void tn_fwd_onepass_kernel(TnShape s, TnFwd a) {
+    constexpr int SLAB = BLOCK == 64 ? TN_SMALL : TN_MAX;      // the one-wave form leaves the CU's LDS to other workgroups
+    __shared__ __attribute__((aligned(16))) float slab[SLAB];
+    __shared__ float red[2 * (TN_BLOCK / 64)];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    if (s.N > SLAB) return;                         // the host never asks: nothing outside the slab either way
+    const size_t chan = (size_t)c * s.HW;
+    float mean, var, invstd;
+    tn_slab_stats<BLOCK, V>(s, a.x + chan, a.eps, slab, red, mean, var, invstd);
     if (tid == 0) tn_publish(a, c, s.N, mean, var, invstd);
     const float gamma = a.w ? a.w[c] : 1.0f, beta = a.b ? a.b[c] : 0.0f;
     TnWalk k(tid, s.RU);
@@ -195,6 +206,32 @@ __global__ __launch_bounds__(TN_BLOCK) void tn_stats_kernel(TnShape s, TnFwd a) 
     }
 }
 
+// the S partials (mean, M2) of a channel merged by the first wave, in double: lane l takes the slices l, l + 64, ... in
+// order, then the wave's butterfly; first the mean, then M2 around it (Chan's rule with the exact mean: M2 =
+// sum M2_i + n_i (mean_i - mean)^2).  The same order, so the same value, in every workgroup of the channel.
+__device__ inline void tn_merge_stats(const TnShape& s, const float* part, float eps, float& mean, float& var, float& invstd) {
+    __shared__ double mrg[2];
+    const int tid = threadIdx.x;
+    if (tid < 64) {
+        const double last = (double)(s.N - (s.S - 1) * TN_SLICE);
+        double A = 0.0;
+        for (int i = tid; i < s.S; i += 64) A += (i + 1 < s.S ? (double)TN_SLICE : last) * (double)part[2 * i];
+        const double m = wave_sum_d(A) / (double)s.N;
+        double Q = 0.0;
+        for (int i = tid; i < s.S; i += 64) {
+            const double d = (double)part[2 * i] - m;
+            Q += (double)part[2 * i + 1] + (i + 1 < s.S ? (double)TN_SLICE : last) * d * d;
+        }
+        Q = wave_sum_d(Q);
+        if (tid == 0) { mrg[0] = m; mrg[1] = Q; }
+    }
+    __syncthreads();
+    const double mu = mrg[0], M2 = mrg[1];
+    mean = (float)mu;
+    var = (float)(M2 / (double)s.N);
+    invstd = 1.0f / sqrtf(var + eps);
+}
+
 // ---- forward, split regime launch 2 (a.ws: merge the partials) and the eval forward (a.ws == NULL: running statistics):
 // grid (C, S), every workgroup normalises its slice
 template <int V>
@@ -205,29 +242,8 @@ __global__ __launch_bounds__(TN_BLOCK) void tn_fwd_apply_kernel(TnShape s, TnFwd
     if (sl >= s.S || u0 >= s.NU) return;
     float mean, invstd;
     if (a.ws) {
-        // the S partials (count, mean, M2) merged by the first wave, in double: lane l takes the slices l, l + 64, ... in
-        // order, then the wave's butterfly; first the mean, then M2 around it (Chan's rule with the exact mean: M2 =
-        // sum M2_i + n_i (mean_i - mean)^2).  The same order, so the same value, in every workgroup of the channel.
-        __shared__ double mrg[2];
-        if (tid < 64) {
-            const float* part = a.ws + (size_t)c * s.S * 2;
-            const double last = (double)(s.N - (s.S - 1) * TN_SLICE);
-            double A = 0.0;
-            for (int i = tid; i < s.S; i += 64) A += (i + 1 < s.S ? (double)TN_SLICE : last) * (double)part[2 * i];
-            const double m = wave_sum_d(A) / (double)s.N;
-            double Q = 0.0;
-            for (int i = tid; i < s.S; i += 64) {
-                const double d = (double)part[2 * i] - m;
-                Q += (double)part[2 * i + 1] + (i + 1 < s.S ? (double)TN_SLICE : last) * d * d;
-            }
-            Q = wave_sum_d(Q);
-            if (tid == 0) { mrg[0] = m; mrg[1] = Q; }
-        }
-        __syncthreads();
-        const double mu = mrg[0], M2 = mrg[1];
-        mean = (float)mu;
-        const float var = (float)(M2 / (double)s.N);
-        invstd = 1.0f / sqrtf(var + a.eps);
+        float var;
+        tn_merge_stats(s, a.ws + (size_t)c * s.S * 2, a.eps, mean, var, invstd);
         if (sl == 0 && tid == 0) tn_publish(a, c, s.N, mean, var, invstd);
     } else {
         mean = a.rm[c];
@@ -344,6 +360,22 @@ __global__ __launch_bounds__(TN_BLOCK) void tn_bwd_partial_kernel(TnShape s, TnB
     }
 }
 
+// the S partials (sum g, sum g xhat) of a channel added by the first wave, in double: lane l takes the slices l, l + 64,
+// ... in order, then the wave's butterfly: the same order, so the same value, in every workgroup of the channel
+__device__ inline void tn_merge_sums(const TnShape& s, const float* part, float& sg, float& sgx) {
+    __shared__ double mrg[2];
+    const int tid = threadIdx.x;
+    if (tid < 64) {
+        double P = 0.0, Q = 0.0;
+        for (int i = tid; i < s.S; i += 64) { P += (double)part[2 * i]; Q += (double)part[2 * i + 1]; }
+        P = wave_sum_d(P); Q = wave_sum_d(Q);
+        if (tid == 0) { mrg[0] = P; mrg[1] = Q; }
+    }
+    __syncthreads();
+    const double A = mrg[0], Bx = mrg[1];
+    sg = (float)A; sgx = (float)Bx;
+}
+
 // ---- backward, split regime launch 2, and the eval backward without affine gradients (a.sums == 0): grid (C, S), or
 // (C, 1) when only the affine gradients are wanted (a.dx == NULL)
 template <int V>
@@ -354,19 +386,7 @@ __global__ __launch_bounds__(TN_BLOCK) void tn_bwd_apply_kernel(TnShape s, TnBwd
     if (sl >= s.S || u0 >= s.NU) return;
     float sg = 0.0f, sgx = 0.0f;
     if (a.sums) {
-        // the S partials added by the first wave, in double: lane l takes the slices l, l + 64, ... in order, then the
-        // wave's butterfly: the same order, so the same value, in every workgroup of the channel
-        __shared__ double mrg[2];
-        if (tid < 64) {
-            const float* part = a.ws + (size_t)c * s.S * 2;
-            double P = 0.0, Q = 0.0;
-            for (int i = tid; i < s.S; i += 64) { P += (double)part[2 * i]; Q += (double)part[2 * i + 1]; }
-            P = wave_sum_d(P); Q = wave_sum_d(Q);
-            if (tid == 0) { mrg[0] = P; mrg[1] = Q; }
-        }
-        __syncthreads();
-        const double A = mrg[0], Bx = mrg[1];
-        sg = (float)A; sgx = (float)Bx;
+        tn_merge_sums(s, a.ws + (size_t)c * s.S * 2, sg, sgx);
         if (sl == 0 && tid == 0) {
             if (a.db) a.db[c] = sg;
             if (a.dw) a.dw[c] = sgx;
@@ -387,6 +407,204 @@ __global__ __launch_bounds__(TN_BLOCK) void tn_bwd_apply_kernel(TnShape s, TnBwd
 #pragma unroll
         for (int j = 0; j < V; ++j) g.v[j] = kk * (g.v[j] - mg - xh.v[j] * mgx);
         stv<V>(a.dx + e, g);
+    }
+}
+
+// ---- the stem's pool: max(tn_act(x), 0) and MaxPool2d(3, 2, 1) as one op.  Window (ph, pw) covers rows
+// 2 ph - 1 .. 2 ph + 1 and columns 2 pw - 1 .. 2 pw + 1, taps outside the map take no part; p is the window's maximum and
+// idx the tap number r * 3 + s of the first one.  Halo: none is staged; a work-item reads its window's taps from global
+// memory and the overlap of neighbouring windows comes out of the cache (the windows of a workgroup are neighbours).
+constexpr int TP_SLICE = VPN_BN_POOL_SLICE;     // pooled outputs of a channel a workgroup of tp_fwd_kernel owns
+static_assert(TP_SLICE % (2 * TN_BLOCK) == 0, "a workgroup takes whole pairs of outputs per work-item");
+
+// NP = B PH PW pooled outputs per channel, in SP slices of TP_SLICE
+struct TpShape { int H, W, PH, PW, NP, SP; };
+
+// y of tn_fwd_apply_kernel with its roundings pinned: the product with gamma and the sum with beta contracted
+__device__ inline float tp_act(float x, float mean, float invstd, float gamma, float beta) {
+    return fmaxf(__builtin_fmaf((x - mean) * invstd, gamma, beta), 0.0f);
+}
+
+// ATen's rule: a tap replaces the best so far only if it is greater or is NaN, so the first maximum wins
+__device__ inline void tp_tap(float& best, int& k, float y, int tap) {
+    if (y > best || y != y) { best = y; k = tap; }
+}
+
+// window (ph, pw) of one map `m` (rows of W floats), taps scanned r then s ascending
+__device__ inline void tp_window(const float* m, const TpShape& g, int ph, int pw, float mean, float invstd, float gamma,
+                                 float beta, float& best, int& k) {
+    best = -INFINITY; k = 0;
+    for (int r = 0; r < 3; ++r) {
+        const int h = 2 * ph - 1 + r;
+        if (h < 0 || h >= g.H) continue;
+        for (int t = 0; t < 3; ++t) {
+            const int w = 2 * pw - 1 + t;
+            if (w < 0 || w >= g.W) continue;
+            tp_tap(best, k, tp_act(m[(size_t)h * g.W + w], mean, invstd, gamma, beta), r * 3 + t);
+        }
+    }
+}
+
+// ---- forward, one-pass regime: grid C; the statistics of tn_fwd_onepass_kernel, then the windows are read from the slab
+// (element n of the channel = batch row n / HW, pixel n % HW)
+template <int BLOCK, int V>
+__global__ __launch_bounds__(BLOCK) void tp_fwd_onepass_kernel(TnShape s, TpShape g, TnFwd a, unsigned char* idx) {
+    constexpr int SLAB = BLOCK == 64 ? TN_SMALL : TN_MAX;
+    __shared__ __attribute__((aligned(16))) float slab[SLAB];
+    __shared__ float red[2 * (TN_BLOCK / 64)];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    if (s.N > SLAB) return;
+    float mean, var, invstd;
+    tn_slab_stats<BLOCK, V>(s, a.x + (size_t)c * s.HW, a.eps, slab, red, mean, var, invstd);
+    if (tid == 0) tn_publish(a, c, s.N, mean, var, invstd);
+    __syncthreads();                                  // from here a work-item reads what others wrote to the slab
+    const float gamma = a.w ? a.w[c] : 1.0f, beta = a.b ? a.b[c] : 0.0f;
+    const int PHW = g.PH * g.PW;
+    for (int o = tid; o < g.NP; o += BLOCK) {
+        const int b = o / PHW, r = o - b * PHW, ph = r / g.PW, pw = r - ph * g.PW;
+        float best; int k;
+        tp_window(slab + (size_t)b * s.HW, g, ph, pw, mean, invstd, gamma, beta, best, k);
+        const size_t e = ((size_t)b * s.C + c) * PHW + r;
+        a.y[e] = best;
+        idx[e] = (unsigned char)k;
+    }
+}
+
+// ---- forward, split regime launch 2 (a.ws: merge the partials of tn_stats_kernel) and the eval forward (a.ws == NULL):
+// grid (C, SP).  V = 4 (W a multiple of 4, x 16-byte aligned): a work-item takes the outputs (ph, pw), (ph, pw + 1) with pw
+// even: of each row the four columns 2 pw .. 2 pw + 3 in one 16-byte access and column 2 pw - 1 by itself.
+template <int V>
+__global__ __launch_bounds__(TN_BLOCK) void tp_fwd_kernel(TnShape s, TpShape g, TnFwd a, unsigned char* idx) {
+    const int c = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
+    constexpr int OUT = V == 4 ? 2 : 1;
+    const int o0 = sl * TP_SLICE, o1 = o0 + TP_SLICE < g.NP ? o0 + TP_SLICE : g.NP;
+    if (sl >= g.SP || o0 >= g.NP) return;
+    float mean, invstd;
+    if (a.ws) {
+        float var;
+        tn_merge_stats(s, a.ws + (size_t)c * s.S * 2, a.eps, mean, var, invstd);
+        if (sl == 0 && tid == 0) tn_publish(a, c, s.N, mean, var, invstd);
+    } else {
+        mean = a.rm[c];
+        invstd = 1.0f / sqrtf(a.rv[c] + a.eps);
+    }
+    const float gamma = a.w ? a.w[c] : 1.0f, beta = a.b ? a.b[c] : 0.0f;
+    const int PHW = g.PH * g.PW;
+    for (int o = o0 + tid * OUT; o < o1; o += TN_BLOCK * OUT) {
+        const int b = o / PHW, r = o - b * PHW, ph = r / g.PW, pw = r - ph * g.PW;
+        const float* m = a.x + ((size_t)b * s.C + c) * s.HW;
+        const size_t e = ((size_t)b * s.C + c) * PHW + r;
+        if (V == 4) {
+            float b0 = -INFINITY, b1 = -INFINITY; int k0 = 0, k1 = 0;
+#pragma unroll
+            for (int rr = 0; rr < 3; ++rr) {
+                const int h = 2 * ph - 1 + rr;
+                if (h < 0 || h >= g.H) continue;
+                const float* row = m + (size_t)h * g.W + 2 * pw;
+                const Vec<4> q = ldv<4>(row);
+                float y[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) y[j] = tp_act(q.v[j], mean, invstd, gamma, beta);
+                if (pw > 0) tp_tap(b0, k0, tp_act(row[-1], mean, invstd, gamma, beta), rr * 3);
+                tp_tap(b0, k0, y[0], rr * 3 + 1); tp_tap(b0, k0, y[1], rr * 3 + 2);
+                tp_tap(b1, k1, y[1], rr * 3); tp_tap(b1, k1, y[2], rr * 3 + 1); tp_tap(b1, k1, y[3], rr * 3 + 2);
+            }
+            a.y[e] = b0; a.y[e + 1] = b1;
+            idx[e] = (unsigned char)k0; idx[e + 1] = (unsigned char)k1;
+        } else {
+            float best; int k;
+            tp_window(m, g, ph, pw, mean, invstd, gamma, beta, best, k);
+            a.y[e] = best;
+            idx[e] = (unsigned char)k;
+        }
+    }
+}
+
+// upstream gradient of pixel (h, w) of the map whose pooled maps begin at element pc: dp [p > 0] of the at most four
+// windows that hold the pixel and whose idx names it, ph then pw ascending.  a.dy: dp, a.y: p.
+__device__ inline float tp_g(const TnBwd& a, const unsigned char* idx, const TpShape& g, size_t pc, int h, int w) {
+    float sum = 0.0f;
+    for (int ph = h >> 1; ph <= ((h + 1) >> 1) && ph < g.PH; ++ph) {
+        const int r = h - 2 * ph + 1;
+        for (int pw = w >> 1; pw <= ((w + 1) >> 1) && pw < g.PW; ++pw) {
+            const size_t o = pc + (size_t)ph * g.PW + pw;
+            const int k = idx[o];                         // the three loads do not wait for one another
+            const float pv = a.y[o], dv = a.dy[o];
+            sum += k == r * 3 + (w - 2 * pw + 1) && pv > 0.0f ? dv : 0.0f;
+        }
+    }
+    return sum;
+}
+
+// g and xhat of the V elements of unit k of channel c (V = 4: W is a multiple of 4, the four share a row)
+template <int V>
+__device__ inline void tp_bwd_load(const TnShape& s, const TpShape& g, const TnBwd& a, const unsigned char* idx, int c,
+                                   const TnWalk& k, float mean, float invstd, Vec<V>& gr, Vec<V>& xh) {
+    const int i = k.i * V, h = i / g.W, w = i - h * g.W;
+    const size_t pc = ((size_t)k.b * s.C + c) * g.PH * g.PW;
+    xh = ldv<V>(a.x + (size_t)c * s.HW + k.at<V>(s));
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        gr.v[j] = tp_g(a, idx, g, pc, h, w + j);
+        xh.v[j] = (xh.v[j] - mean) * invstd;
+    }
+}
+
+// ---- backward launch 1: grid (C, S); the two sums of a slice of the input map
+template <int V>
+__global__ __launch_bounds__(TN_BLOCK) void tp_bwd_partial_kernel(TnShape s, TpShape g, TnBwd a, const unsigned char* idx) {
+    __shared__ float red[2 * (TN_BLOCK / 64)];
+    const int c = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
+    constexpr int SU = TN_SLICE / V, PER = TN_PER / V;
+    const int u0 = sl * SU, u1 = u0 + SU < s.NU ? u0 + SU : s.NU;
+    if (sl >= s.S || u0 >= s.NU) return;
+    float mean, invstd;
+    tn_bwd_stats(a, c, mean, invstd);
+    float sg = 0.0f, sgx = 0.0f;
+    TnWalk k(u0 + tid, s.RU);
+    for (int p = 0; p < PER; ++p, k.step(s)) {
+        if (u0 + tid + p * TN_BLOCK >= u1) break;
+        Vec<V> gr, xh;
+        tp_bwd_load<V>(s, g, a, idx, c, k, mean, invstd, gr, xh);
+#pragma unroll
+        for (int j = 0; j < V; ++j) { sg += gr.v[j]; sgx += gr.v[j] * xh.v[j]; }
+    }
+    block_sum2<TN_BLOCK>(sg, sgx, red);
+    if (tid == 0) {
+        a.ws[((size_t)c * s.S + sl) * 2] = sg;
+        a.ws[((size_t)c * s.S + sl) * 2 + 1] = sgx;
+    }
+}
+
+// ---- backward launch 2, and the eval backward without affine gradients (a.sums == 0): grid (C, S), or (C, 1) when only
+// the affine gradients are wanted (a.dx == NULL); the merge of tn_bwd_apply_kernel
+template <int V>
+__global__ __launch_bounds__(TN_BLOCK) void tp_bwd_apply_kernel(TnShape s, TpShape g, TnBwd a, const unsigned char* idx) {
+    const int c = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
+    constexpr int SU = TN_SLICE / V, PER = TN_PER / V;
+    const int u0 = sl * SU, u1 = u0 + SU < s.NU ? u0 + SU : s.NU;
+    if (sl >= s.S || u0 >= s.NU) return;
+    float sg = 0.0f, sgx = 0.0f;
+    if (a.sums) {
+        tn_merge_sums(s, a.ws + (size_t)c * s.S * 2, sg, sgx);
+        if (sl == 0 && tid == 0) {
+            if (a.db) a.db[c] = sg;
+            if (a.dw) a.dw[c] = sgx;
+        }
+    }
+    if (!a.dx) return;
+    float mean, invstd;
+    tn_bwd_stats(a, c, mean, invstd);
+    const float kk = (a.w ? a.w[c] : 1.0f) * invstd;
+    const float mg = a.eval ? 0.0f : sg / (float)s.N, mgx = a.eval ? 0.0f : sgx / (float)s.N;
+    TnWalk k(u0 + tid, s.RU);
+    for (int p = 0; p < PER; ++p, k.step(s)) {
+        if (u0 + tid + p * TN_BLOCK >= u1) break;
+        Vec<V> gr, xh;
+        tp_bwd_load<V>(s, g, a, idx, c, k, mean, invstd, gr, xh);
+#pragma unroll
+        for (int j = 0; j < V; ++j) gr.v[j] = kk * (gr.v[j] - mg - xh.v[j] * mgx);
+        stv<V>(a.dx + (size_t)c * s.HW + k.at<V>(s), gr);
     }
 }
 
@@ -506,5 +724,101 @@ extern "C" int vpn_bn_act_bwd(const float* dy, const float* x, const float* y, c
         else VPN_LAUNCH_AS("tn_bwd_apply_kernel", (tn_bwd_apply_kernel<1>), g2, dim3(TN_BLOCK), 0, st, s, a);
         VPN_LAUNCH_CHECK();
     }
+    return 0;
+}
+
+// shape checks of the pool's entry points on top of tn_shape
+static int tp_shape(int B, int C, int H, int W, TnShape* s, TpShape* g) {
+    const int rc = tn_shape(B, C, H, W, s);
+    if (rc) return rc;
+    g->H = H; g->W = W; g->PH = (H - 1) / 2 + 1; g->PW = (W - 1) / 2 + 1;
+    const long long NP = (long long)B * g->PH * g->PW, SP = (NP + TP_SLICE - 1) / TP_SLICE;
+    if (SP > 65535) return VPN_E_TOOBIG;
+    g->NP = (int)NP; g->SP = (int)SP;
+    return 0;
+}
+
+extern "C" size_t vpn_bn_pool_workspace(int B, int C, int H, int W) {
+    TnShape s;
+    TpShape g;
+    if (tp_shape(B, C, H, W, &s, &g) != 0) return 0;
+    return (size_t)C * s.S * 2 * sizeof(float);
+}
+
+static bool tp_workspace_ok(const void* workspace, size_t bytes, int B, int C, int H, int W) {
+    return workspace && bytes >= vpn_bn_pool_workspace(B, C, H, W) && !((uintptr_t)workspace & 3);
+}
+
+extern "C" int vpn_bn_pool_fwd(const float* x, const float* weight, const float* bias, float* running_mean, float* running_var,
+                               long long* num_batches_tracked, int B, int C, int H, int W, int training, float momentum, float eps,
+                               float* p, unsigned char* idx, float* save_mean, float* save_invstd, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    TnShape s;
+    TpShape g;
+    const int rc = tp_shape(B, C, H, W, &s, &g);
+    if (rc) return rc;
+    if (!x || !p || !idx || !(eps >= 0.0f)) return VPN_E_BADARG;
+    if (training ? (!save_mean || !save_invstd || s.N < 2 || !(momentum >= 0.0f && momentum <= 1.0f)) : (!running_mean || !running_var))
+        return VPN_E_BADARG;
+    const bool split = training && s.N > TN_MAX;
+    if (split && !tp_workspace_ok(workspace, workspace_bytes, B, C, H, W)) return VPN_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    TnFwd a{x, nullptr, weight, bias, running_mean, running_var, training ? num_batches_tracked : nullptr, p, save_mean,
+            save_invstd, split ? (float*)workspace : nullptr, momentum, eps, 1};
+    const bool vec = s.HW % 4 == 0 && tn_aligned16(x);              // how the statistics read x; the pool asks for W % 4 == 0
+    const int block = training && s.N <= TN_SMALL ? 64 : TN_BLOCK;
+    tn_units(&s, vec ? 4 : 1, block);
+    if (training && !split) {
+        const dim3 grid((unsigned)C);
+        if (block == 64) {
+            if (vec) VPN_LAUNCH_AS("tp_fwd_onepass_kernel", (tp_fwd_onepass_kernel<64, 4>), grid, dim3(64), 0, st, s, g, a, idx);
+            else VPN_LAUNCH_AS("tp_fwd_onepass_kernel", (tp_fwd_onepass_kernel<64, 1>), grid, dim3(64), 0, st, s, g, a, idx);
+        } else {
+            if (vec) VPN_LAUNCH_AS("tp_fwd_onepass_kernel", (tp_fwd_onepass_kernel<TN_BLOCK, 4>), grid, dim3(TN_BLOCK), 0, st, s, g, a, idx);
+            else VPN_LAUNCH_AS("tp_fwd_onepass_kernel", (tp_fwd_onepass_kernel<TN_BLOCK, 1>), grid, dim3(TN_BLOCK), 0, st, s, g, a, idx);
+        }
+        VPN_LAUNCH_CHECK();
+        return 0;
+    }
+    if (split) {                                   // the statistics launch of vpn_bn_act_fwd
+        const dim3 grid((unsigned)C, (unsigned)s.S);
+        if (vec) VPN_LAUNCH_AS("tn_stats_kernel", (tn_stats_kernel<4>), grid, dim3(TN_BLOCK), 0, st, s, a);
+        else VPN_LAUNCH_AS("tn_stats_kernel", (tn_stats_kernel<1>), grid, dim3(TN_BLOCK), 0, st, s, a);
+        VPN_LAUNCH_CHECK();
+    }
+    const dim3 grid((unsigned)C, (unsigned)g.SP);
+    if (vec && W % 4 == 0) VPN_LAUNCH_AS("tp_fwd_kernel", (tp_fwd_kernel<4>), grid, dim3(TN_BLOCK), 0, st, s, g, a, idx);
+    else VPN_LAUNCH_AS("tp_fwd_kernel", (tp_fwd_kernel<1>), grid, dim3(TN_BLOCK), 0, st, s, g, a, idx);
+    VPN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vpn_bn_pool_bwd(const float* dp, const float* x, const float* p, const unsigned char* idx, const float* weight,
+                               const float* stat_mean, const float* stat_var, int B, int C, int H, int W, int training, float eps,
+                               float* dx, float* d_weight, float* d_bias, void* workspace, size_t workspace_bytes, void* stream) {
+    TnShape s;
+    TpShape g;
+    const int rc = tp_shape(B, C, H, W, &s, &g);
+    if (rc) return rc;
+    if (!dp || !x || !p || !idx || !stat_mean || !stat_var || !(eps >= 0.0f) || (training && s.N < 2)) return VPN_E_BADARG;
+    const bool affine = d_weight || d_bias;
+    if (!dx && !affine) return 0;                                    // nothing is wanted
+    const bool sums = training || affine;                            // eval: dx needs no sum
+    if (sums && !tp_workspace_ok(workspace, workspace_bytes, B, C, H, W)) return VPN_E_BADARG;
+    const bool vec = W % 4 == 0 && tn_aligned16(x) && tn_aligned16(dx);
+    hipStream_t st = (hipStream_t)stream;
+    TnBwd a{dp, x, p, weight, stat_mean, stat_var, dx, nullptr, d_weight, d_bias, sums ? (float*)workspace : nullptr, eps,
+            training ? 0 : 1, sums ? 1 : 0};
+    tn_units(&s, vec ? 4 : 1, TN_BLOCK);
+    const dim3 grid((unsigned)C, (unsigned)s.S);
+    if (sums) {
+        if (vec) VPN_LAUNCH_AS("tp_bwd_partial_kernel", (tp_bwd_partial_kernel<4>), grid, dim3(TN_BLOCK), 0, st, s, g, a, idx);
+        else VPN_LAUNCH_AS("tp_bwd_partial_kernel", (tp_bwd_partial_kernel<1>), grid, dim3(TN_BLOCK), 0, st, s, g, a, idx);
+        VPN_LAUNCH_CHECK();
+    }
+    const dim3 g2 = dx ? grid : dim3((unsigned)C, 1u);
+    if (vec) VPN_LAUNCH_AS("tp_bwd_apply_kernel", (tp_bwd_apply_kernel<4>), g2, dim3(TN_BLOCK), 0, st, s, g, a, idx);
+    else VPN_LAUNCH_AS("tp_bwd_apply_kernel", (tp_bwd_apply_kernel<1>), g2, dim3(TN_BLOCK), 0, st, s, g, a, idx);
+    VPN_LAUNCH_CHECK();
     return 0;
 }

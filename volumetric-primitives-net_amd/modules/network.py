@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from .. import config
-from ..ops import HeadPackFunction, FcStackFunction, BatchNormActFunction, Conv3x3Function, Conv2dFunction
+from ..ops import HeadPackFunction, FcStackFunction, BatchNormActFunction, BatchNormPoolFunction, Conv3x3Function, Conv2dFunction
 from .gcn import GCNModel, GCNConv  # noqa: F401
 
 
@@ -41,6 +41,22 @@ def batch_norm_act(x, bn: nn.BatchNorm2d, residual=None, relu=True):
     device, as nn.BatchNorm2d does."""
     return BatchNormActFunction.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
                                       residual, bn.training, bn.momentum, bn.eps, relu)
+
+
+def batch_norm_relu_pool(x, bn: nn.BatchNorm2d):
+    """max_pool2d(relu(bn(x)), 3, 2, 1) in one op on csrc/trunknorm.hip, with the parameters, buffers,
+    momentum, eps and mode of `bn`, which is not called; the full-size activation is never written.  Training mode updates
+    the running statistics and num_batches_tracked in place on the device, as nn.BatchNorm2d does."""
+    return BatchNormPoolFunction.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
+                                       bn.training, bn.momentum, bn.eps)
+
+
+def _is_stem_pool(pool):
+    """MaxPool2d(3, 2, 1): the one pool csrc/trunknorm.hip holds."""
+    def both(v):
+        return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+    return (both(pool.kernel_size) == (3, 3) and both(pool.stride) == (2, 2) and both(pool.padding) == (1, 1) and
+            both(pool.dilation) == (1, 1) and not pool.ceil_mode and not pool.return_indices)
 
 
 def conv3x3(x, weight):
@@ -139,12 +155,15 @@ class ResNet18(nn.Module):
     with kernel 3, stride 1, padding 1 of those stages run on csrc/trunkconv.hip, their nn.Conv2d modules only hold the
     weights; conv1 (7x7), the three stride-2 convolutions and the three 1x1 downsamples are not among them.
     hip_conv_strided=True: those seven (conv1, every layerN.0.conv1 and layerN.0.downsample[0] with stride 2) run on
-    csrc/trunkstride.hip; with hip_conv=True as well no library convolution is left in the trunk, forward or backward.  The
-    three keywords are independent; the state_dict is the same either way."""
+    csrc/trunkstride.hip; with hip_conv=True as well no library convolution is left in the trunk, forward or backward.
+    fused_pool=True: the stem's maxpool(relu(bn1(.))) is one op on csrc/trunknorm.hip (batch_norm_relu_pool) whatever
+    fused_norm says; self.maxpool stays registered and is not called.  The four keywords are independent; the state_dict is
+    the same either way."""
 
-    def __init__(self, num_classes=1000, fused_norm=False, hip_conv=False, hip_conv_strided=False):
+    def __init__(self, num_classes=1000, fused_norm=False, hip_conv=False, hip_conv_strided=False, fused_pool=False):
         super().__init__()
         f = self.fused_norm = bool(fused_norm)
+        self.fused_pool = bool(fused_pool)
         g = self.hip_conv_strided = bool(hip_conv_strided)
         self.hip_conv = _hip_conv_stages(hip_conv)
         h = {s: s in self.hip_conv for s in TRUNK_STAGES}
@@ -170,10 +189,18 @@ class ResNet18(nn.Module):
         """The 7x7 stem convolution: on csrc/trunkstride.hip with hip_conv_strided, else the module itself."""
         return _conv_strided(self.conv1, x) if self.hip_conv_strided and _is_trunk_conv_strided(self.conv1) else self.conv1(x)
 
-    def _stem(self, x):
+    def _stem_tail(self, x):
+        """maxpool(relu(bn1(x))) of the stem convolution's output, by the form the keywords chose."""
+        if self.fused_pool:
+            if not _is_stem_pool(self.maxpool):
+                raise ValueError('fused_pool: csrc/trunknorm.hip holds MaxPool2d(3, 2, 1) only, self.maxpool is %r' % (self.maxpool,))
+            return batch_norm_relu_pool(x, self.bn1)
         if self.fused_norm:
-            return self.maxpool(batch_norm_act(self._conv1(x), self.bn1, relu=True))
-        return self.maxpool(self.relu(self.bn1(self._conv1(x))))
+            return self.maxpool(batch_norm_act(x, self.bn1, relu=True))
+        return self.maxpool(self.relu(self.bn1(x)))
+
+    def _stem(self, x):
+        return self._stem_tail(self._conv1(x))
 
     def forward(self, x):
         x = self._stem(x)
@@ -184,8 +211,8 @@ class ResNet18(nn.Module):
 def _trunk_maps(model, imgs):
     """conv1 .. layer4 of a trunk (extract_feature of the three models): the four residual stages' outputs."""
     stem = model._conv1(imgs) if getattr(model, 'hip_conv_strided', False) else model.conv1(imgs)
-    if getattr(model, 'fused_norm', False):
-        out = model.maxpool(batch_norm_act(stem, model.bn1, relu=True))
+    if hasattr(model, '_stem_tail'):                      # ResNet18: by the form its keywords chose
+        out = model._stem_tail(stem)
     else:
         out = model.maxpool(model.relu(model.bn1(stem)))
     l1 = model.layer1(out)

@@ -2087,6 +2087,63 @@ class BatchNormActFunction(Function):
         return dx, dw, db, None, None, None, dres, None, None, None, None
 
 
+def pool_out_size(H, W):
+    """(PH, PW) of MaxPool2d(3, 2, 1): ((H - 1) // 2 + 1, (W - 1) // 2 + 1)."""
+    return (H - 1) // 2 + 1, (W - 1) // 2 + 1
+
+
+class BatchNormPoolFunction(Function):
+    """p = max_pool2d(relu(batch_norm(x)), 3, 2, 1) on the tp_ kernels of csrc/trunknorm.hip: the stem of the
+    ResNet-18 trunk.  apply(x, weight, bias, running_mean, running_var, num_batches_tracked, training, momentum, eps).
+    Training: batch statistics, the running statistics and the counter are updated in place on the device, bit-equal to
+    BatchNormActFunction's.  The full-size activation is never written: x, p, the uint8 tap index of every window, weight and
+    the two statistics are saved (in this order).  Gradients for x, weight and bias; each is skipped when not needed."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, num_batches_tracked, training, momentum, eps):
+        training = bool(training)
+        _bn_act_check(x, weight, bias, running_mean, running_var, num_batches_tracked, None, training, momentum)
+        x = x.contiguous()
+        weight = None if weight is None else weight.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        B, C, H, W = x.shape
+        PH, PW = pool_out_size(H, W)
+        dev = x.device
+        p = torch.empty((B, C, PH, PW), dtype=torch.float32, device=dev)
+        idx = torch.empty((B, C, PH, PW), dtype=torch.uint8, device=dev)
+        save_mean = save_invstd = ws = None
+        if training:
+            save_mean = torch.empty((C,), dtype=torch.float32, device=dev)
+            save_invstd = torch.empty((C,), dtype=torch.float32, device=dev)
+            if B * H * W > TRUNKNORM_ONE_PASS_MAX:
+                ws = _workspace('vpn_bn_pool_workspace', B, C, H, W, dev=dev)
+        _lib.call('vpn_bn_pool_fwd', x, weight, bias, running_mean, running_var, num_batches_tracked, B, C, H, W, int(training),
+                  float(momentum), float(eps), p, idx, save_mean, save_invstd, ws, 0 if ws is None else ws.numel() * 4,
+                  _lib.stream())
+        stats = (save_mean, save_invstd) if training else (running_mean, running_var)
+        ctx.save_for_backward(x, p, idx, weight, *stats)
+        ctx.cfg = (training, float(eps))
+        return p
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_p):
+        x, p, idx, weight, stat_a, stat_b = ctx.saved_tensors
+        training, eps = ctx.cfg
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        B, C, H, W = x.shape
+        dev = x.device
+        dp = grad_p.contiguous()
+        dx = torch.empty_like(x) if need_x else None
+        dw = torch.empty((C,), dtype=torch.float32, device=dev) if need_w else None
+        db = torch.empty((C,), dtype=torch.float32, device=dev) if need_b else None
+        if dx is not None or dw is not None or db is not None:
+            ws = _workspace('vpn_bn_pool_workspace', B, C, H, W, dev=dev)
+            _lib.call('vpn_bn_pool_bwd', dp, x, p, idx, weight, stat_a, stat_b, B, C, H, W, int(training), eps, dx, dw, db, ws,
+                      ws.numel() * 4, _lib.stream())
+        return dx, dw, db, None, None, None, None, None, None
+
+
 # ---- the trunk's convolutions (csrc/trunkconv.hip, csrc/trunkstride.hip on the tile loop of csrc/vpn_conv_gemm.h; DESIGN.md
 # 4.19, 4.20): nn.Conv2d(square kernel, no bias) reached through vpnet_one_resnet.py:45-57, forward and both gradients on the
 # f32-input MFMA.  Conv3x3Function: kernel 3, stride 1, padding 1 inside torchvision's BasicBlock; Conv2dFunction: kernel 1, 3
