@@ -75,6 +75,8 @@ def main(argv=None):
     ap.add_argument('--trunk-norm', default='torch', choices=('torch', 'hip', 'hip+pool'),
                     help='hip: the ResNet-18 trunk runs each batch norm with its residual add and ReLU as one op (csrc/trunknorm.hip); '
                          'hip+pool: the stem\'s norm, ReLU and max pool as one op as well')
+    ap.add_argument('--trunk-tail', default='torch', choices=('torch', 'hip'),
+                    help='hip: the last norm site of the ResNet-18 trunk and the global average pool run as one op (csrc/trunknorm.hip)')
     ap.add_argument('--trunk-conv', default='torch', choices=('torch', 'hip', 'all'),
                     help='hip: the 13 stride-1 3x3 convolutions of the ResNet-18 trunk run on the f32-input MFMA (csrc/trunkconv.hip); '
                          'all: the seven stride-2 ones as well (csrc/trunkstride.hip): no library convolution is left in the trunk')
@@ -82,7 +84,7 @@ def main(argv=None):
     dev = torch.device('cuda')
     torch.manual_seed(1234)
     if args.vpn or args.net == 'vpnet_oneres':
-        vpn = vpn_amd.VPNetOneRes(vp_num=VP_NUM, trunk=vpn_amd.ResNet18(fused_norm=args.trunk_norm != 'torch', fused_pool=args.trunk_norm == 'hip+pool', hip_conv=args.trunk_conv in ('hip', 'all'), hip_conv_strided=args.trunk_conv == 'all') if (args.trunk_norm, args.trunk_conv) != ('torch', 'torch') else None)
+        vpn = vpn_amd.VPNetOneRes(vp_num=VP_NUM, trunk=vpn_amd.ResNet18(fused_norm=args.trunk_norm != 'torch', fused_pool=args.trunk_norm == 'hip+pool', hip_conv=args.trunk_conv in ('hip', 'all'), hip_conv_strided=args.trunk_conv == 'all', fused_tail=args.trunk_tail == 'hip') if (args.trunk_norm, args.trunk_conv, args.trunk_tail) != ('torch', 'torch', 'torch') else None)
         if args.vpn:
             vpn.load_state_dict(torch.load(args.vpn, map_location='cpu'))
         vpn = vpn.to(dev).eval()

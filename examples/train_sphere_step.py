@@ -93,6 +93,8 @@ if __name__ == '__main__':
     ap.add_argument('--trunk-norm', default='torch', choices=('torch', 'hip', 'hip+pool'),
                     help='hip: the ResNet-18 trunk runs each batch norm with its residual add and ReLU as one op (csrc/trunknorm.hip); '
                          'hip+pool: the stem\'s norm, ReLU and max pool as one op as well')
+    ap.add_argument('--trunk-tail', default='torch', choices=('torch', 'hip'),
+                    help='hip: the last norm site of the ResNet-18 trunk and the global average pool run as one op (csrc/trunknorm.hip)')
     ap.add_argument('--trunk-conv', default='torch', choices=('torch', 'hip', 'all'),
                     help='hip: the 13 stride-1 3x3 convolutions of the ResNet-18 trunk run on the f32-input MFMA (csrc/trunkconv.hip); '
                          'all: the seven stride-2 ones as well (csrc/trunkstride.hip): no library convolution is left in the trunk')
@@ -101,7 +103,7 @@ if __name__ == '__main__':
     torch.manual_seed(0)
     batch = make_batch(4, 2048, 64, dev)                              # BASELINE config C1: batch 4, 64 x 64
     P = vpn_amd.load_obj(args.obj)[0].shape[0] if args.obj else 288
-    net = (vpn_amd.SDNet(vertex_num=P, trunk=vpn_amd.ResNet18(fused_norm=args.trunk_norm != 'torch', fused_pool=args.trunk_norm == 'hip+pool', hip_conv=args.trunk_conv in ('hip', 'all'), hip_conv_strided=args.trunk_conv == 'all') if (args.trunk_norm, args.trunk_conv) != ('torch', 'torch') else None) if args.net == 'sdnet' else Offsets(64, P)).to(dev)
+    net = (vpn_amd.SDNet(vertex_num=P, trunk=vpn_amd.ResNet18(fused_norm=args.trunk_norm != 'torch', fused_pool=args.trunk_norm == 'hip+pool', hip_conv=args.trunk_conv in ('hip', 'all'), hip_conv_strided=args.trunk_conv == 'all', fused_tail=args.trunk_tail == 'hip') if (args.trunk_norm, args.trunk_conv, args.trunk_tail) != ('torch', 'torch', 'torch') else None) if args.net == 'sdnet' else Offsets(64, P)).to(dev)
     if args.optimizer == 'hip':
         opt = vpn_amd.Adam(net.parameters(), lr=2e-3, betas=(0.9, 0.99))            # train_sphere.py:92
     else:

@@ -1,6 +1,6 @@
 """A training step of the reference (train.py:221-268) on the drop-in surface, with a stand-in network.
 
-    python examples/train_step.py [--steps 20] [--net standin|vpnet_oneres|vpnet_twores] [--optimizer torch|hip] [--trunk-norm torch|hip|hip+pool] [--trunk-conv torch|hip|all]
+    python examples/train_step.py [--steps 20] [--net standin|vpnet_oneres|vpnet_twores] [--optimizer torch|hip] [--trunk-norm torch|hip|hip+pool] [--trunk-conv torch|hip|all] [--trunk-tail torch|hip]
 
 By default a two-layer MLP on a random feature vector produces the three head outputs (volumes [B,3K], rotates [B,4K],
 translates [B,3K]); --net vpnet_oneres / vpnet_twores trains the reference's network instead (modules/network.py: a
@@ -146,6 +146,8 @@ def main():
     ap.add_argument('--trunk-norm', default='torch', choices=('torch', 'hip', 'hip+pool'),
                     help='hip: the ResNet-18 trunk runs each batch norm with its residual add and ReLU as one op (csrc/trunknorm.hip); '
                          'hip+pool: the stem\'s norm, ReLU and max pool as one op as well')
+    ap.add_argument('--trunk-tail', default='torch', choices=('torch', 'hip'),
+                    help='hip: the last norm site of the ResNet-18 trunk and the global average pool run as one op (csrc/trunknorm.hip)')
     ap.add_argument('--trunk-conv', default='torch', choices=('torch', 'hip', 'all'),
                     help='hip: the 13 stride-1 3x3 convolutions of the ResNet-18 trunk run on the f32-input MFMA (csrc/trunkconv.hip); '
                          'all: the seven stride-2 ones as well (csrc/trunkstride.hip): no library convolution is left in the trunk')
@@ -157,10 +159,10 @@ def main():
     torch.manual_seed(1234)
     batch = make_batch(args.batch, args.prims, args.sample_num, args.size, dev)
 
-    own_trunk = (args.trunk_norm, args.trunk_conv) != ('torch', 'torch')
+    own_trunk = (args.trunk_norm, args.trunk_conv, args.trunk_tail) != ('torch', 'torch', 'torch')
 
     def trunk():           # None: the model builds its own plain trunk, as it always did
-        return vpn_amd.ResNet18(fused_norm=args.trunk_norm != 'torch', fused_pool=args.trunk_norm == 'hip+pool', hip_conv=args.trunk_conv in ('hip', 'all'), hip_conv_strided=args.trunk_conv == 'all') if own_trunk else None
+        return vpn_amd.ResNet18(fused_norm=args.trunk_norm != 'torch', fused_pool=args.trunk_norm == 'hip+pool', hip_conv=args.trunk_conv in ('hip', 'all'), hip_conv_strided=args.trunk_conv == 'all', fused_tail=args.trunk_tail == 'hip') if own_trunk else None
     net = {'standin': lambda: Heads(64, args.prims), 'vpnet_oneres': lambda: vpn_amd.VPNetOneRes(vp_num=args.prims, trunk=trunk()),
            'vpnet_twores': lambda: vpn_amd.VPNetTwoRes(vp_num=args.prims, trunk=(trunk(), trunk()) if own_trunk else None)}[args.net]().to(dev)
     if args.optimizer == 'hip':

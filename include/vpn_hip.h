@@ -953,6 +953,43 @@ int vpn_bn_pool_bwd(const float* dp, const float* x, const float* p, const unsig
                     const float* stat_mean, const float* stat_var, int B, int C, int H, int W, int training, float eps,
                     float* dx, float* d_weight, float* d_bias, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the trunk's tail: the last norm / add / ReLU site and the global average pool as ONE op, forward and backward (the
+ * tt_ kernels of csrc/trunknorm.hip; `avgpool(layer4(.))` of the torchvision ResNet-18).  x, residual, y, dy,
+ * dx, d_residual: [B,C,H,W]; m, dm: [B,C].  All DEVICE fp32, contiguous, 4-byte aligned; 16-byte accesses under the rule of
+ * vpn_bn_act_* (m and dm are always accessed by element).  A row is the H * W elements of one (b, c).
+ *   m[b,c] = (sum over hw of y[b,c,hw]) / (float)(H * W): an fp32 sum in one fixed order, then ONE fp32 division.  The order:
+ *   where the rows a workgroup owns fit LDS (every case but rows longer than VPN_BN_SLICE outside the one-launch regime), a
+ *   group of G lanes, G the smallest power of two >= min(H * W, 64), owns a row, lane j adds the elements j, j + G, ... in
+ *   order, then the group's butterfly; a longer row is owned by one workgroup, a work-item adds its elements in order, then
+ *   the wave's butterfly, then the waves in order.
+ *   The upstream gradient of an element is dy[b,c,hw] + dm[b,c] / (float)(H * W): one IEEE fp32 division per row, then one
+ *   fp32 addition.
+ * No host synchronisation, nothing allocated, no atomics: bit-equal from run to run, capturable.  Added without a change of
+ * VPN_ABI_VERSION.
+ * vpn_bn_tail_workspace: the rule of vpn_bn_act_workspace: C * ceil(N / VPN_BN_SLICE) * 2 floats in bytes when N = B * H * W >
+ *   VPN_BN_ONE_PASS_MAX, else 0; 0 for sizes the entries refuse.
+ * vpn_bn_tail_fwd: y, save_mean, save_invstd, the running statistics and num_batches_tracked are what vpn_bn_act_fwd writes
+ *   for the same arguments, bit for bit; m is written in addition.  residual and relu are optional as there.  training != 0
+ *   and N <= VPN_BN_ONE_PASS_MAX: ONE launch (the rows are summed from the channel's slab in LDS), no workspace.  Larger N:
+ *   TWO launches, the statistics launch of vpn_bn_act_fwd, then an apply launch on a grid (C, ceil(B / R)) whose workgroups
+ *   own R = max(VPN_BN_SLICE / (H * W), 1) whole batch rows of a channel.  training == 0: ONE launch, the apply launch on the
+ *   running statistics.
+ * vpn_bn_tail_bwd: vpn_bn_act_bwd on the upstream gradient above: g, the two sums, dx, d_residual, d_weight and d_bias
+ *   follow it exactly, with its launch counts and its workspace rule.  dy NULL: no gradient reaches the map, the upstream
+ *   gradient is dm[b,c] / (H * W) and dy is not read.  dm NULL: the call equals vpn_bn_act_bwd bit for bit.  Both NULL:
+ *   VPN_E_BADARG.  dx, d_residual, d_weight, d_bias all NULL: nothing is launched.
+ * The rules of vpn_bn_act_fwd / _bwd, and m == NULL: VPN_E_BADARG.  N >= 2^31, more than 65535 slices, or an apply grid with
+ * ceil(B / R) > 65535: VPN_E_TOOBIG.  Both before any HIP call. */
+size_t vpn_bn_tail_workspace(int B, int C, int H, int W);
+int vpn_bn_tail_fwd(const float* x, const float* residual, const float* weight, const float* bias, float* running_mean,
+                    float* running_var, long long* num_batches_tracked, int B, int C, int H, int W, int training, float momentum,
+                    float eps, int relu, float* y, float* m, float* save_mean, float* save_invstd, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int vpn_bn_tail_bwd(const float* dy, const float* dm, const float* x, const float* y, const float* weight,
+                    const float* stat_mean, const float* stat_var, int B, int C, int H, int W, int training, float eps, int relu,
+                    float* dx, float* d_residual, float* d_weight, float* d_bias, void* workspace, size_t workspace_bytes,
+                    void* stream);
+
 /* ---- the trunk's 3x3 convolutions (csrc/trunkconv.hip): kernel 3x3, stride 1, padding 1, dilation 1,
  * groups 1, no bias, as an implicit GEMM on the f32-input MFMA: exact fp32 products, one fixed summation order.  All tensors
  * DEVICE fp32, contiguous, 4-byte aligned: x [B,C_in,H,W], w [C_out,C_in,3,3], y and dy [B,C_out,H,W], dx as x, dw as w.  Any

@@ -4,7 +4,7 @@ Import as `vpn_amd` (repo-root alias module); the directory name is fixed by the
 layout.  Everything here runs on hand-written HIP kernels in libvpn_hip.so through the C
 ABI of include/vpn_hip.h; there is no CPU fallback."""
 from . import config
-from .ops import (SPHERE, CUBOID, SampleFunction, TransformFunction, ChamferFunction, EmdFunction, HeadPackFunction, FcStackFunction, BatchNormActFunction, BatchNormPoolFunction, MeshFunction,
+from .ops import (SPHERE, CUBOID, SampleFunction, TransformFunction, ChamferFunction, EmdFunction, HeadPackFunction, FcStackFunction, BatchNormActFunction, BatchNormPoolFunction, BatchNormMeanFunction, MeshFunction,
                   CameraTransformFunction, RasterFunction,
                   RasterLossFunction, RasterTotalFunction, HotPathLossFunction, TrainStepLossFunction, chamfer_nn, kinds_tensor,
                   emd_recovered_samples, emd_last_group, eval_step, vis_primitives, vis_mesh, phong_mesh,
@@ -17,5 +17,5 @@ from .modules import (Sampling, ChamferDistanceLoss, EarthMoverDistanceLoss, Sil
                       points_to_meshes_and_colors, points_to_mesh_batch, meshes_to_imgs, generate_point_mixup_data, acd, augment,
                       acd_mix_meshes, acd_mix_data, EvaluationMeter, prepare_images,
                       MeshBatch, sample_gt_points, gt_points, view_center_xforms, genre_xforms,
-                      Visualizer, FcHeads, batch_norm_act, batch_norm_relu_pool, conv3x3, conv2d, ResNet18, VPNetOneRes, VPNetTwoRes, SDNet, Adam)
+                      Visualizer, FcHeads, batch_norm_act, batch_norm_relu_pool, batch_norm_act_mean, conv3x3, conv2d, ResNet18, VPNetOneRes, VPNetTwoRes, SDNet, Adam)
 from . import modules

@@ -1,6 +1,7 @@
 // trunknorm.hip — the trunk's norm / add / ReLU ring (gfx950): batch norm, the residual add and the ReLU of a ResNet-18
-// site as ONE op, forward and backward, and the stem's form of it that also holds the 3x3 stride-2 max
-// pool (the tp_ kernels below).
+// site as ONE op, forward and backward, the stem's form of it that also holds the 3x3 stride-2 max
+// pool (the tp_ kernels below) and the tail's form that also holds the global average pool (DESIGN.md
+// 4.22; the tt_ kernels below).
 //
 // Replaces, around the convolutions of the reference's torchvision trunk (vpnet_one_resnet.py:21, vpnet_two_resnet.py:21-22,
 // sdnet.py:13), `relu(bn1(.))`, `bn2(.)`, `out += identity; relu(out)` and the downsample branch's norm: 20 training-mode
@@ -608,6 +609,252 @@ __global__ __launch_bounds__(TN_BLOCK) void tp_bwd_apply_kernel(TnShape s, TpSha
     }
 }
 
+// ---- the trunk's tail: the last norm site also writes m[b,c] = (sum_hw y[b,c,hw]) / HW, the global
+// average pool the heads read, and its backward takes m's gradient: upstream = dy + dm[b,c] / HW.  A row is the HW elements
+// of one (batch row, channel).  Rows are summed from LDS where they fit: a group of G = 2^LG lanes (the smallest power of
+// two >= min(HW, 64)) owns a row, lane j of the group adds the elements j, j + G, ... in order, then the group's butterfly.
+// B: batch rows; RPB: rows a workgroup of tt_fwd_apply_kernel owns.
+struct TtRows { int B, RPB, LG; };
+
+// y with the roundings of tn_fwd_onepass_kernel / tn_fwd_apply_kernel pinned (tp_act says which), before the ReLU
+__device__ inline float tt_act(float x, float mean, float invstd, float gamma, float beta) {
+    return __builtin_fmaf((x - mean) * invstd, gamma, beta);
+}
+
+// the means of `rows` rows of HW floats that lie one after another in LDS; row r goes to m[r * stride]
+template <int BLOCK>
+__device__ inline void tt_row_means(const float* slab, int rows, int HW, int LG, float* m, size_t stride) {
+    const int lane = threadIdx.x & 63, G = 1 << LG, per = 64 >> LG, j = lane & (G - 1);
+    for (int r0 = (threadIdx.x >> 6) * per; r0 < rows; r0 += (BLOCK / 64) * per) {      // the same trip count in a wave
+        const int r = r0 + (lane >> LG);
+        float v = 0.0f;
+        if (r < rows) {
+            const float* p = slab + (size_t)r * HW;
+            for (int i = j; i < HW; i += G) v += p[i];
+        }
+        for (int o = G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (r < rows && j == 0) m[(size_t)r * stride] = v / (float)HW;
+    }
+}
+
+// ---- forward, one-pass regime: tn_fwd_onepass_kernel, with y written back to the slab and its rows summed from there
+template <int BLOCK, int V>
+__global__ __launch_bounds__(BLOCK) void tt_fwd_onepass_kernel(TnShape s, TtRows t, TnFwd a, float* m) {
+    constexpr int SLAB = BLOCK == 64 ? TN_SMALL : TN_MAX;
+    __shared__ __attribute__((aligned(16))) float slab[SLAB];
+    __shared__ float red[2 * (TN_BLOCK / 64)];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    if (s.N > SLAB) return;
+    const size_t chan = (size_t)c * s.HW;
+    float mean, var, invstd;
+    tn_slab_stats<BLOCK, V>(s, a.x + chan, a.eps, slab, red, mean, var, invstd);
+    if (tid == 0) tn_publish(a, c, s.N, mean, var, invstd);
+    const float gamma = a.w ? a.w[c] : 1.0f, beta = a.b ? a.b[c] : 0.0f;
+    TnWalk k(tid, s.RU);
+    for (int u = tid; u < s.NU; u += BLOCK, k.step(s)) {
+        const size_t e = chan + k.at<V>(s);
+        Vec<V> r = ldv<V>(slab + (size_t)u * V);
+        Vec<V> q = {};
+        if (a.res) q = ldv<V>(a.res + e);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            float y = tt_act(r.v[j], mean, invstd, gamma, beta);
+            if (a.res) y += q.v[j];
+            r.v[j] = a.relu ? fmaxf(y, 0.0f) : y;
+        }
+        stv<V>(a.y + e, r);
+        stv<V>(slab + (size_t)u * V, r);
+    }
+    __syncthreads();                                  // from here a work-item reads what others wrote to the slab
+    tt_row_means<BLOCK>(slab, t.B, s.HW, t.LG, m + c, (size_t)s.C);
+}
+
+// ---- forward, split regime launch 2 (a.ws: merge the partials of tn_stats_kernel) and the eval forward (a.ws == NULL):
+// grid (C, ceil(B / RPB)), a workgroup owns the batch rows blockIdx.y * RPB ... of its channel.  HW <= TN_SLICE: RPB =
+// TN_SLICE / HW rows, y staged in LDS and summed as above.  Longer rows: RPB = 1, a work-item adds its elements in unit
+// order, then the workgroup's sum (block_sum2).
+template <int V>
+__global__ __launch_bounds__(TN_BLOCK) void tt_fwd_apply_kernel(TnShape s, TtRows t, TnFwd a, float* m) {
+    __shared__ __attribute__((aligned(16))) float slab[TN_SLICE];
+    __shared__ float red[2 * (TN_BLOCK / 64)];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    const int b0 = blockIdx.y * t.RPB, b1 = b0 + t.RPB < t.B ? b0 + t.RPB : t.B;
+    if (b0 >= t.B) return;
+    const bool staged = s.HW <= TN_SLICE;
+    if (staged && (b1 - b0) * s.HW > TN_SLICE) return;          // the host never asks: nothing outside the slab either way
+    float mean, invstd;
+    if (a.ws) {
+        float var;
+        tn_merge_stats(s, a.ws + (size_t)c * s.S * 2, a.eps, mean, var, invstd);
+        if (blockIdx.y == 0 && tid == 0) tn_publish(a, c, s.N, mean, var, invstd);
+    } else {
+        mean = a.rm[c];
+        invstd = 1.0f / sqrtf(a.rv[c] + a.eps);
+    }
+    const float gamma = a.w ? a.w[c] : 1.0f, beta = a.b ? a.b[c] : 0.0f;
+    const size_t chan = (size_t)c * s.HW;
+    const int u0 = b0 * s.RU, u1 = b1 * s.RU;
+    float acc = 0.0f;
+    TnWalk k(u0 + tid, s.RU);
+    for (int u = u0 + tid; u < u1; u += TN_BLOCK, k.step(s)) {
+        const size_t e = chan + k.at<V>(s);
+        Vec<V> r = ldv<V>(a.x + e);
+        Vec<V> q = {};
+        if (a.res) q = ldv<V>(a.res + e);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            float y = tt_act(r.v[j], mean, invstd, gamma, beta);
+            if (a.res) y += q.v[j];
+            r.v[j] = a.relu ? fmaxf(y, 0.0f) : y;
+        }
+        stv<V>(a.y + e, r);
+        if (staged) {
+            stv<V>(slab + (size_t)(u - u0) * V, r);
+        } else {
+#pragma unroll
+            for (int j = 0; j < V; ++j) acc += r.v[j];
+        }
+    }
+    float* mr = m + (size_t)b0 * s.C + c;
+    if (staged) {
+        __syncthreads();
+        tt_row_means<TN_BLOCK>(slab, b1 - b0, s.HW, t.LG, mr, (size_t)s.C);
+    } else {
+        float none = 0.0f;
+        block_sum2<TN_BLOCK>(acc, none, red);
+        if (tid == 0) mr[0] = acc / (float)s.HW;
+    }
+}
+
+// g and xhat of the V elements of unit k of channel c, at element e: tn_bwd_load with the upstream gradient dy + dm[b,c] / HW
+// (a.dy or dm may be NULL: the other one alone)
+template <int V>
+__device__ inline void tt_bwd_load(const TnShape& s, const TnBwd& a, const float* dm, int c, const TnWalk& k, size_t e, float mean,
+                                   float invstd, Vec<V>& g, Vec<V>& xh) {
+    g = Vec<V>{};
+    if (a.dy) g = ldv<V>(a.dy + e);
+    if (dm) {
+        const float q = dm[(size_t)k.b * s.C + c] / (float)s.HW;
+#pragma unroll
+        for (int j = 0; j < V; ++j) g.v[j] = a.dy ? g.v[j] + q : q;
+    }
+    xh = ldv<V>(a.x + e);
+    if (a.y) {
+        const Vec<V> y = ldv<V>(a.y + e);
+#pragma unroll
+        for (int j = 0; j < V; ++j) g.v[j] = y.v[j] <= 0.0f ? 0.0f : g.v[j];
+    }
+#pragma unroll
+    for (int j = 0; j < V; ++j) xh.v[j] = (xh.v[j] - mean) * invstd;
+}
+
+// ---- backward, one-pass regime: tn_bwd_onepass_kernel on the upstream gradient of tt_bwd_load
+template <int BLOCK, int V>
+__global__ __launch_bounds__(BLOCK) void tt_bwd_onepass_kernel(TnShape s, TnBwd a, const float* dm) {
+    constexpr int SLAB = BLOCK == 64 ? TN_SMALL : TN_MAX;
+    __shared__ __attribute__((aligned(16))) float gs[SLAB];
+    __shared__ __attribute__((aligned(16))) float xs[SLAB];
+    __shared__ float red[2 * (TN_BLOCK / 64)];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    if (s.N > SLAB) return;
+    float mean, invstd;
+    tn_bwd_stats(a, c, mean, invstd);
+    const size_t chan = (size_t)c * s.HW;
+    float sg = 0.0f, sgx = 0.0f;
+    {
+        TnWalk k(tid, s.RU);
+        for (int u = tid; u < s.NU; u += BLOCK, k.step(s)) {
+            const size_t e = chan + k.at<V>(s);
+            Vec<V> g, xh;
+            tt_bwd_load<V>(s, a, dm, c, k, e, mean, invstd, g, xh);
+            stv<V>(gs + (size_t)u * V, g);
+            stv<V>(xs + (size_t)u * V, xh);
+            if (a.dres) stv<V>(a.dres + e, g);
+#pragma unroll
+            for (int j = 0; j < V; ++j) { sg += g.v[j]; sgx += g.v[j] * xh.v[j]; }
+        }
+    }
+    block_sum2<BLOCK>(sg, sgx, red);
+    if (tid == 0) {
+        if (a.db) a.db[c] = sg;
+        if (a.dw) a.dw[c] = sgx;
+    }
+    if (!a.dx) return;
+    const float kk = (a.w ? a.w[c] : 1.0f) * invstd;
+    const float mg = a.eval ? 0.0f : sg / (float)s.N, mgx = a.eval ? 0.0f : sgx / (float)s.N;
+    TnWalk k(tid, s.RU);
+    for (int u = tid; u < s.NU; u += BLOCK, k.step(s)) {
+        Vec<V> g = ldv<V>(gs + (size_t)u * V);
+        const Vec<V> xh = ldv<V>(xs + (size_t)u * V);
+#pragma unroll
+        for (int j = 0; j < V; ++j) g.v[j] = kk * (g.v[j] - mg - xh.v[j] * mgx);
+        stv<V>(a.dx + chan + k.at<V>(s), g);
+    }
+}
+
+// ---- backward, split regime launch 1: tn_bwd_partial_kernel on the upstream gradient of tt_bwd_load
+template <int V>
+__global__ __launch_bounds__(TN_BLOCK) void tt_bwd_partial_kernel(TnShape s, TnBwd a, const float* dm) {
+    __shared__ float red[2 * (TN_BLOCK / 64)];
+    const int c = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
+    constexpr int SU = TN_SLICE / V, PER = TN_PER / V;
+    const int u0 = sl * SU, u1 = u0 + SU < s.NU ? u0 + SU : s.NU;
+    if (sl >= s.S || u0 >= s.NU) return;
+    float mean, invstd;
+    tn_bwd_stats(a, c, mean, invstd);
+    const size_t chan = (size_t)c * s.HW;
+    float sg = 0.0f, sgx = 0.0f;
+    TnWalk k(u0 + tid, s.RU);
+    for (int p = 0; p < PER; ++p, k.step(s)) {
+        if (u0 + tid + p * TN_BLOCK >= u1) break;
+        const size_t e = chan + k.at<V>(s);
+        Vec<V> g, xh;
+        tt_bwd_load<V>(s, a, dm, c, k, e, mean, invstd, g, xh);
+        if (a.dres) stv<V>(a.dres + e, g);
+#pragma unroll
+        for (int j = 0; j < V; ++j) { sg += g.v[j]; sgx += g.v[j] * xh.v[j]; }
+    }
+    block_sum2<TN_BLOCK>(sg, sgx, red);
+    if (tid == 0) {
+        a.ws[((size_t)c * s.S + sl) * 2] = sg;
+        a.ws[((size_t)c * s.S + sl) * 2 + 1] = sgx;
+    }
+}
+
+// ---- backward, split regime launch 2, and the eval backward without affine gradients (a.sums == 0): tn_bwd_apply_kernel
+// on the upstream gradient of tt_bwd_load
+template <int V>
+__global__ __launch_bounds__(TN_BLOCK) void tt_bwd_apply_kernel(TnShape s, TnBwd a, const float* dm) {
+    const int c = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
+    constexpr int SU = TN_SLICE / V, PER = TN_PER / V;
+    const int u0 = sl * SU, u1 = u0 + SU < s.NU ? u0 + SU : s.NU;
+    if (sl >= s.S || u0 >= s.NU) return;
+    float sg = 0.0f, sgx = 0.0f;
+    if (a.sums) {
+        tn_merge_sums(s, a.ws + (size_t)c * s.S * 2, sg, sgx);
+        if (sl == 0 && tid == 0) {
+            if (a.db) a.db[c] = sg;
+            if (a.dw) a.dw[c] = sgx;
+        }
+    }
+    if (!a.dx) return;
+    float mean, invstd;
+    tn_bwd_stats(a, c, mean, invstd);
+    const float kk = (a.w ? a.w[c] : 1.0f) * invstd;
+    const float mg = a.eval ? 0.0f : sg / (float)s.N, mgx = a.eval ? 0.0f : sgx / (float)s.N;
+    const size_t chan = (size_t)c * s.HW;
+    TnWalk k(u0 + tid, s.RU);
+    for (int p = 0; p < PER; ++p, k.step(s)) {
+        if (u0 + tid + p * TN_BLOCK >= u1) break;
+        const size_t e = chan + k.at<V>(s);
+        Vec<V> g, xh;
+        tt_bwd_load<V>(s, a, dm, c, k, e, mean, invstd, g, xh);
+#pragma unroll
+        for (int j = 0; j < V; ++j) g.v[j] = kk * (g.v[j] - mg - xh.v[j] * mgx);
+        stv<V>(a.dx + e, g);
+    }
+}
+
 static bool tn_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // shape checks shared by the entry points; fills `s` for accesses of V floats and workgroups of `block` work-items
@@ -820,5 +1067,120 @@ extern "C" int vpn_bn_pool_bwd(const float* dp, const float* x, const float* p, 
     if (vec) VPN_LAUNCH_AS("tp_bwd_apply_kernel", (tp_bwd_apply_kernel<4>), g2, dim3(TN_BLOCK), 0, st, s, g, a, idx);
     else VPN_LAUNCH_AS("tp_bwd_apply_kernel", (tp_bwd_apply_kernel<1>), g2, dim3(TN_BLOCK), 0, st, s, g, a, idx);
     VPN_LAUNCH_CHECK();
+    return 0;
+}
+
+// the rows of the tail's entry points on top of tn_shape: whole batch rows per workgroup of tt_fwd_apply_kernel
+static int tt_shape(int B, int C, int H, int W, TnShape* s, TtRows* t) {
+    const int rc = tn_shape(B, C, H, W, s);
+    if (rc) return rc;
+    t->B = B;
+    t->RPB = s->HW <= TN_SLICE ? TN_SLICE / s->HW : 1;
+    if ((B + t->RPB - 1) / t->RPB > 65535) return VPN_E_TOOBIG;
+    t->LG = 0;
+    while (t->LG < 6 && (1 << t->LG) < s->HW) ++t->LG;
+    return 0;
+}
+
+extern "C" size_t vpn_bn_tail_workspace(int B, int C, int H, int W) {
+    TnShape s;
+    TtRows t;
+    if (tt_shape(B, C, H, W, &s, &t) != 0 || s.N <= TN_MAX) return 0;
+    return (size_t)C * s.S * 2 * sizeof(float);
+}
+
+extern "C" int vpn_bn_tail_fwd(const float* x, const float* residual, const float* weight, const float* bias, float* running_mean,
+                               float* running_var, long long* num_batches_tracked, int B, int C, int H, int W, int training,
+                               float momentum, float eps, int relu, float* y, float* m, float* save_mean, float* save_invstd,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    TnShape s;
+    TtRows t;
+    const int rc = tt_shape(B, C, H, W, &s, &t);
+    if (rc) return rc;
+    if (!x || !y || !m || !(eps >= 0.0f)) return VPN_E_BADARG;
+    if (training ? (!save_mean || !save_invstd || s.N < 2 || !(momentum >= 0.0f && momentum <= 1.0f)) : (!running_mean || !running_var))
+        return VPN_E_BADARG;
+    const bool split = training && s.N > TN_MAX;
+    if (split && (!workspace || workspace_bytes < vpn_bn_tail_workspace(B, C, H, W) || ((uintptr_t)workspace & 3))) return VPN_E_BADARG;
+    const bool vec = s.HW % 4 == 0 && tn_aligned16(x) && tn_aligned16(y) && tn_aligned16(residual);
+    hipStream_t st = (hipStream_t)stream;
+    TnFwd a{x, residual, weight, bias, running_mean, running_var, training ? num_batches_tracked : nullptr, y, save_mean,
+            save_invstd, split ? (float*)workspace : nullptr, momentum, eps, relu != 0};
+    if (training && !split) {
+        const int block = s.N <= TN_SMALL ? 64 : TN_BLOCK;
+        tn_units(&s, vec ? 4 : 1, block);
+        const dim3 grid((unsigned)C);
+        if (block == 64) {
+            if (vec) VPN_LAUNCH_AS("tt_fwd_onepass_kernel", (tt_fwd_onepass_kernel<64, 4>), grid, dim3(64), 0, st, s, t, a, m);
+            else VPN_LAUNCH_AS("tt_fwd_onepass_kernel", (tt_fwd_onepass_kernel<64, 1>), grid, dim3(64), 0, st, s, t, a, m);
+        } else {
+            if (vec) VPN_LAUNCH_AS("tt_fwd_onepass_kernel", (tt_fwd_onepass_kernel<TN_BLOCK, 4>), grid, dim3(TN_BLOCK), 0, st, s, t, a, m);
+            else VPN_LAUNCH_AS("tt_fwd_onepass_kernel", (tt_fwd_onepass_kernel<TN_BLOCK, 1>), grid, dim3(TN_BLOCK), 0, st, s, t, a, m);
+        }
+        VPN_LAUNCH_CHECK();
+        return 0;
+    }
+    tn_units(&s, vec ? 4 : 1, TN_BLOCK);
+    if (split) {                                   // the statistics launch of vpn_bn_act_fwd
+        const dim3 grid((unsigned)C, (unsigned)s.S);
+        if (vec) VPN_LAUNCH_AS("tn_stats_kernel", (tn_stats_kernel<4>), grid, dim3(TN_BLOCK), 0, st, s, a);
+        else VPN_LAUNCH_AS("tn_stats_kernel", (tn_stats_kernel<1>), grid, dim3(TN_BLOCK), 0, st, s, a);
+        VPN_LAUNCH_CHECK();
+    }
+    const dim3 grid((unsigned)C, (unsigned)((B + t.RPB - 1) / t.RPB));
+    if (vec) VPN_LAUNCH_AS("tt_fwd_apply_kernel", (tt_fwd_apply_kernel<4>), grid, dim3(TN_BLOCK), 0, st, s, t, a, m);
+    else VPN_LAUNCH_AS("tt_fwd_apply_kernel", (tt_fwd_apply_kernel<1>), grid, dim3(TN_BLOCK), 0, st, s, t, a, m);
+    VPN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vpn_bn_tail_bwd(const float* dy, const float* dm, const float* x, const float* y, const float* weight,
+                               const float* stat_mean, const float* stat_var, int B, int C, int H, int W, int training, float eps,
+                               int relu, float* dx, float* d_residual, float* d_weight, float* d_bias, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    TnShape s;
+    TtRows t;
+    const int rc = tt_shape(B, C, H, W, &s, &t);
+    if (rc) return rc;
+    if ((!dy && !dm) || !x || !stat_mean || !stat_var || (relu && !y) || !(eps >= 0.0f) || (training && s.N < 2)) return VPN_E_BADARG;
+    const bool affine = d_weight || d_bias;
+    if (!dx && !d_residual && !affine) return 0;                     // nothing is wanted
+    const bool sums = training || affine;                            // eval: dx needs no sum
+    const bool split = s.N > TN_MAX;
+    const bool partial = sums || d_residual;                         // split regime: launch 1 forms the sums and writes d_residual
+    if (split && partial && (!workspace || workspace_bytes < vpn_bn_tail_workspace(B, C, H, W) || ((uintptr_t)workspace & 3)))
+        return VPN_E_BADARG;
+    const bool vec = s.HW % 4 == 0 && tn_aligned16(dy) && tn_aligned16(x) && tn_aligned16(relu ? y : nullptr) && tn_aligned16(dx) &&
+                     tn_aligned16(d_residual);
+    hipStream_t st = (hipStream_t)stream;
+    TnBwd a{dy, x, relu ? y : nullptr, weight, stat_mean, stat_var, dx, d_residual, d_weight, d_bias,
+            split && partial ? (float*)workspace : nullptr, eps, training ? 0 : 1, split && sums ? 1 : 0};
+    if (!split) {
+        const int block = s.N <= TN_SMALL ? 64 : TN_BLOCK;
+        tn_units(&s, vec ? 4 : 1, block);
+        const dim3 grid((unsigned)C);
+        if (block == 64) {
+            if (vec) VPN_LAUNCH_AS("tt_bwd_onepass_kernel", (tt_bwd_onepass_kernel<64, 4>), grid, dim3(64), 0, st, s, a, dm);
+            else VPN_LAUNCH_AS("tt_bwd_onepass_kernel", (tt_bwd_onepass_kernel<64, 1>), grid, dim3(64), 0, st, s, a, dm);
+        } else {
+            if (vec) VPN_LAUNCH_AS("tt_bwd_onepass_kernel", (tt_bwd_onepass_kernel<TN_BLOCK, 4>), grid, dim3(TN_BLOCK), 0, st, s, a, dm);
+            else VPN_LAUNCH_AS("tt_bwd_onepass_kernel", (tt_bwd_onepass_kernel<TN_BLOCK, 1>), grid, dim3(TN_BLOCK), 0, st, s, a, dm);
+        }
+        VPN_LAUNCH_CHECK();
+        return 0;
+    }
+    tn_units(&s, vec ? 4 : 1, TN_BLOCK);
+    const dim3 grid((unsigned)C, (unsigned)s.S);
+    if (partial) {
+        if (vec) VPN_LAUNCH_AS("tt_bwd_partial_kernel", (tt_bwd_partial_kernel<4>), grid, dim3(TN_BLOCK), 0, st, s, a, dm);
+        else VPN_LAUNCH_AS("tt_bwd_partial_kernel", (tt_bwd_partial_kernel<1>), grid, dim3(TN_BLOCK), 0, st, s, a, dm);
+        VPN_LAUNCH_CHECK();
+    }
+    if (dx || affine) {
+        const dim3 g2 = dx ? grid : dim3((unsigned)C, 1u);
+        if (vec) VPN_LAUNCH_AS("tt_bwd_apply_kernel", (tt_bwd_apply_kernel<4>), g2, dim3(TN_BLOCK), 0, st, s, a, dm);
+        else VPN_LAUNCH_AS("tt_bwd_apply_kernel", (tt_bwd_apply_kernel<1>), g2, dim3(TN_BLOCK), 0, st, s, a, dm);
+        VPN_LAUNCH_CHECK();
+    }
     return 0;
 }

@@ -4,7 +4,8 @@ sdnet.py), with the same attribute and `state_dict` names, so that a reference c
 around them by default; with `hip_conv` the 3x3 stride-1 convolutions of the chosen stages run on csrc/trunkconv.hip, with
 `hip_conv_strided` the seven stride-2 ones (the stem, layerN.0.conv1, layerN.0.downsample.0) on csrc/trunkstride.hip (the
 nn.Conv2d modules then only HOLD the weights); with `fused_norm=True` each batch norm, with the residual add and the ReLU that follow it, is one
-op on csrc/trunknorm.hip (the nn.BatchNorm2d modules then only HOLD parameters and buffers); the FC heads, the one part of the networks that is nothing but weight traffic, run on csrc/fcstack.hip: their
+op on csrc/trunknorm.hip (the nn.BatchNorm2d modules then only HOLD parameters and buffers), with `fused_pool` / `fused_tail` the
+stem's max pool and the global average pool are part of the norm site before them; the FC heads, the one part of the networks that is nothing but weight traffic, run on csrc/fcstack.hip: their
 nn.Linear modules only HOLD the parameters, the forward hands the tensors to FcStackFunction, which also applies what
 follows the last layer (restrict_range + split + restrict_volumes into packed rows, or SDNet's tanh).  GCNModel (gcn.py,
 the refinement stage of train_gcn.py / test_gcn.py) is re-exported from modules/gcn.py, so that
@@ -13,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from .. import config
-from ..ops import HeadPackFunction, FcStackFunction, BatchNormActFunction, BatchNormPoolFunction, Conv3x3Function, Conv2dFunction
+from ..ops import HeadPackFunction, FcStackFunction, BatchNormActFunction, BatchNormPoolFunction, BatchNormMeanFunction, Conv3x3Function, Conv2dFunction
 from .gcn import GCNModel, GCNConv  # noqa: F401
 
 
@@ -49,6 +50,25 @@ def batch_norm_relu_pool(x, bn: nn.BatchNorm2d):
     the running statistics and num_batches_tracked in place on the device, as nn.BatchNorm2d does."""
     return BatchNormPoolFunction.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
                                        bn.training, bn.momentum, bn.eps)
+
+
+def batch_norm_act_mean(x, bn: nn.BatchNorm2d, residual=None, relu=True):
+    """(y, m) with y = relu?(bn(x) + residual?) and m = y.mean((2, 3)), the global average pool, in one op on
+    csrc/trunknorm.hip, with the parameters, buffers, momentum, eps and mode of `bn`, which is not called.  y
+    and what training mode updates in place are batch_norm_act's bit for bit; both outputs are differentiable."""
+    return BatchNormMeanFunction.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
+                                       residual, bn.training, bn.momentum, bn.eps, relu)
+
+
+def _is_tail_pool(pool):
+    """AdaptiveAvgPool2d to 1x1, or SDNet's nn.Sequential that holds exactly one: the one pool the tail of
+    csrc/trunknorm.hip holds."""
+    if isinstance(pool, nn.Sequential) and len(pool) == 1:
+        pool = pool[0]
+    if not isinstance(pool, nn.AdaptiveAvgPool2d):
+        return False
+    size = pool.output_size
+    return tuple(size) == (1, 1) if isinstance(size, (tuple, list)) else size == 1
 
 
 def _is_stem_pool(pool):
@@ -132,6 +152,22 @@ class BasicBlock(nn.Module):
             return _conv_strided(conv, x)
         return conv(x)
 
+    def forward_tail(self, x):
+        """forward with the global average pool: (relu(bn2(conv2(.)) + identity), its mean over (H, W)), the last site as
+        one op on csrc/trunknorm.hip whatever fused_norm says."""
+        if self.fused_norm:
+            out = batch_norm_act(self._conv(self.conv1, x), self.bn1, relu=True)
+            identity = x if self.downsample is None else batch_norm_act(self._conv(self.downsample[0], x), self.downsample[1], relu=False)
+        else:
+            out = self.relu(self.bn1(self._conv(self.conv1, x)))
+            if self.downsample is None:
+                identity = x
+            elif self.hip_conv_strided and _is_trunk_conv_strided(self.downsample[0]):
+                identity = self.downsample[1](_conv_strided(self.downsample[0], x))
+            else:
+                identity = self.downsample(x)
+        return batch_norm_act_mean(self._conv(self.conv2, out), self.bn2, residual=identity, relu=True)
+
     def forward(self, x):
         if self.fused_norm:
             out = batch_norm_act(self._conv(self.conv1, x), self.bn1, relu=True)
@@ -157,13 +193,17 @@ class ResNet18(nn.Module):
     hip_conv_strided=True: those seven (conv1, every layerN.0.conv1 and layerN.0.downsample[0] with stride 2) run on
     csrc/trunkstride.hip; with hip_conv=True as well no library convolution is left in the trunk, forward or backward.
     fused_pool=True: the stem's maxpool(relu(bn1(.))) is one op on csrc/trunknorm.hip (batch_norm_relu_pool) whatever
-    fused_norm says; self.maxpool stays registered and is not called.  The four keywords are independent; the state_dict is
-    the same either way."""
+    fused_norm says; self.maxpool stays registered and is not called.
+    fused_tail=True: layer4[1]'s relu(bn2(conv2(.)) + identity) and the global average pool are one op on csrc/trunknorm.hip
+    (batch_norm_act_mean) whatever fused_norm says; self.avgpool stays registered and is not called.  The five keywords are
+    independent; the state_dict is the same either way."""
 
-    def __init__(self, num_classes=1000, fused_norm=False, hip_conv=False, hip_conv_strided=False, fused_pool=False):
+    def __init__(self, num_classes=1000, fused_norm=False, hip_conv=False, hip_conv_strided=False, fused_pool=False,
+                 fused_tail=False):
         super().__init__()
         f = self.fused_norm = bool(fused_norm)
         self.fused_pool = bool(fused_pool)
+        self.fused_tail = bool(fused_tail)
         g = self.hip_conv_strided = bool(hip_conv_strided)
         self.hip_conv = _hip_conv_stages(hip_conv)
         h = {s: s in self.hip_conv for s in TRUNK_STAGES}
@@ -202,10 +242,22 @@ class ResNet18(nn.Module):
     def _stem(self, x):
         return self._stem_tail(self._conv1(x))
 
+    def _check_tail_pool(self):
+        if not _is_tail_pool(self.avgpool):
+            raise ValueError('fused_tail: csrc/trunknorm.hip holds AdaptiveAvgPool2d to 1x1 only, self.avgpool is %r' % (self.avgpool,))
+
+    def _layer4_tail(self, x):
+        """(layer4(x), its global average pool [B,512]) with fused_tail: layer4[1]'s last site writes both."""
+        self._check_tail_pool()
+        for block in self.layer4[:-1]:
+            x = block(x)
+        return self.layer4[-1].forward_tail(x)
+
     def forward(self, x):
-        x = self._stem(x)
-        x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
-        return self.fc(torch.flatten(self.avgpool(x), 1))
+        x = self.layer3(self.layer2(self.layer1(self._stem(x))))
+        if self.fused_tail:
+            return self.fc(self._layer4_tail(x)[1])
+        return self.fc(torch.flatten(self.avgpool(self.layer4(x)), 1))
 
 
 def _trunk_maps(model, imgs):
@@ -219,6 +271,27 @@ def _trunk_maps(model, imgs):
     l2 = model.layer2(l1)
     l3 = model.layer3(l2)
     return [l1, l2, l3, model.layer4(l3)]
+
+
+def _trunk_features(model, imgs, pool=None):
+    """(maps, feats): the four residual stages' outputs as _trunk_maps gives them, and the global average pool of the last
+    one as [B,512].  `pool`: the pool of the model that owns the trunk (default: the trunk's own avgpool).  A trunk with
+    fused_tail forms feats in layer4's last site: no pool is called, and one that is not the global average is refused
+    before anything runs.  For any other trunk feats is pool(maps[3]), flattened."""
+    pool = model.avgpool if pool is None else pool
+    if not getattr(model, 'fused_tail', False):
+        maps = _trunk_maps(model, imgs)
+        out = pool(maps[3])
+        return maps, out.view(out.size(0), -1)
+    if not _is_tail_pool(pool):
+        raise ValueError('fused_tail: csrc/trunknorm.hip holds AdaptiveAvgPool2d to 1x1 only, the pool is %r' % (pool,))
+    model._check_tail_pool()
+    stem = model._conv1(imgs) if model.hip_conv_strided else model.conv1(imgs)
+    l1 = model.layer1(model._stem_tail(stem))
+    l2 = model.layer2(l1)
+    l3 = model.layer3(l2)
+    l4, feats = model._layer4_tail(l3)
+    return [l1, l2, l3, l4], feats
 
 
 # ---- the heads
@@ -325,9 +398,8 @@ class VPNetOneRes(_VPNet):
         self.resnet = ResNet18() if trunk is None else trunk
 
     def extract_feature(self, imgs):
-        maps = _trunk_maps(self.resnet, imgs)
-        out = self.avgpool(maps[3])
-        return out.view(out.size(0), -1), maps
+        maps, feats = _trunk_features(self.resnet, imgs, self.avgpool)
+        return feats, maps
 
     def fix_volume_weight(self):
         for p in self.volume_fc.parameters():
@@ -356,8 +428,7 @@ class VPNetTwoRes(_VPNet):
         self.transform_resnet = tt
 
     def extract_feature(self, model, imgs):
-        out = self.avgpool(_trunk_maps(model, imgs)[3])
-        return out.view(out.size(0), -1)
+        return _trunk_features(model, imgs, self.avgpool)[1]
 
     def fix_volume_weight(self):
         for p in self.volume_resnet.parameters():
@@ -388,8 +459,7 @@ class SDNet(FcHeads):
         self._head_paths = ['_model.deform']
 
     def extract_feature(self, imgs):
-        out = self._model.avgpool(_trunk_maps(self._model, imgs)[3])
-        return out.view(out.size(0), -1)
+        return _trunk_features(self._model, imgs)[1]
 
     def forward(self, imgs):
         offsets = self.run_heads([self.extract_feature(imgs)], 'tanh')

@@ -2087,6 +2087,68 @@ class BatchNormActFunction(Function):
         return dx, dw, db, None, None, None, dres, None, None, None, None
 
 
+class BatchNormMeanFunction(Function):
+    """(y, m) = (relu?(batch_norm(x) + residual?), y.mean((2, 3))) on the tt_ kernels of csrc/trunknorm.hip:
+    the last norm site of the ResNet-18 trunk with the global average pool.  apply(x, weight, bias, running_mean, running_var,
+    num_batches_tracked, residual | None, training, momentum, eps, relu) -> (y [B,C,H,W], m [B,C]), both differentiable.  y,
+    the statistics and the counter are BatchNormActFunction's bit for bit, and what it saves is saved here (m is not needed
+    backward).  Gradients for x, weight, bias and residual; each is skipped when not needed, and a gradient of y or m that
+    autograd does not have is not read."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, num_batches_tracked, residual, training, momentum, eps, relu):
+        training, relu = bool(training), bool(relu)
+        _bn_act_check(x, weight, bias, running_mean, running_var, num_batches_tracked, residual, training, momentum)
+        x = x.contiguous()
+        res = None if residual is None else residual.contiguous()
+        weight = None if weight is None else weight.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        B, C, H, W = x.shape
+        dev = x.device
+        y = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
+        m = torch.empty((B, C), dtype=torch.float32, device=dev)
+        save_mean = save_invstd = ws = None
+        if training:
+            save_mean = torch.empty((C,), dtype=torch.float32, device=dev)
+            save_invstd = torch.empty((C,), dtype=torch.float32, device=dev)
+            ws = _workspace('vpn_bn_tail_workspace', B, C, H, W, dev=dev)
+        _lib.call('vpn_bn_tail_fwd', x, res, weight, bias, running_mean, running_var, num_batches_tracked, B, C, H, W,
+                  int(training), float(momentum), float(eps), int(relu), y, m, save_mean, save_invstd,
+                  ws if ws is not None and ws.numel() else None, 0 if ws is None else ws.numel() * 4, _lib.stream())
+        stats = (save_mean, save_invstd) if training else (running_mean, running_var)
+        ctx.save_for_backward(x, y if relu else None, weight, *stats)
+        ctx.cfg = (training, float(eps), relu, residual is not None)
+        ctx.set_materialize_grads(False)      # a gradient that does not exist arrives as None and travels as NULL
+        return y, m
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y, grad_m):
+        x, y, weight, stat_a, stat_b = ctx.saved_tensors
+        training, eps, relu, has_res = ctx.cfg
+        none = (None,) * 11
+        if grad_y is None and grad_m is None:
+            return none
+        need_x, need_w, need_b, need_r = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2],
+                                          has_res and ctx.needs_input_grad[6])
+        B, C, H, W = x.shape
+        dev = x.device
+        dy = None if grad_y is None else grad_y.contiguous()
+        dm = None if grad_m is None else grad_m.contiguous()
+        dx = torch.empty_like(x) if need_x else None
+        dw = torch.empty((C,), dtype=torch.float32, device=dev) if need_w else None
+        db = torch.empty((C,), dtype=torch.float32, device=dev) if need_b else None
+        # without a ReLU and without a gradient of m the residual's gradient IS dy: returned as it is, nothing written
+        dres = torch.empty_like(x) if need_r and (relu or dm is not None) else None
+        if dx is not None or dw is not None or db is not None or dres is not None:
+            ws = _workspace('vpn_bn_tail_workspace', B, C, H, W, dev=dev)
+            _lib.call('vpn_bn_tail_bwd', dy, dm, x, y, weight, stat_a, stat_b, B, C, H, W, int(training), eps, int(relu), dx,
+                      dres, dw, db, ws if ws.numel() else None, ws.numel() * 4, _lib.stream())
+        if need_r and dres is None:
+            dres = dy
+        return dx, dw, db, None, None, None, dres, None, None, None, None
+
+
 def pool_out_size(H, W):
     """(PH, PW) of MaxPool2d(3, 2, 1): ((H - 1) // 2 + 1, (W - 1) // 2 + 1)."""
     return (H - 1) // 2 + 1, (W - 1) // 2 + 1
