@@ -1,6 +1,6 @@
 """The refinement step of the reference's train_gcn.py (:119-138) on the drop-in surface, with synthetic inputs.
 
-    python examples/train_gcn_step.py [--steps 5] [--batch 8] [--net standin|vpnet_oneres] [--vpn CKPT]
+    python examples/train_gcn_step.py [--steps 5] [--batch 8] [--net standin|vpnet_oneres] [--vpn CKPT] [--gcn-input plain|factored]
 
 --net vpnet_oneres runs the reference's frozen VPNetOneRes (modules/network.py; --vpn CKPT loads a reference checkpoint
 into it as train_gcn.py:100-102 does, otherwise it is randomly initialised).  By default a stand-in
@@ -80,6 +80,9 @@ def main(argv=None):
     ap.add_argument('--trunk-conv', default='torch', choices=('torch', 'hip', 'all'),
                     help='hip: the 13 stride-1 3x3 convolutions of the ResNet-18 trunk run on the f32-input MFMA (csrc/trunkconv.hip); '
                          'all: the seven stride-2 ones as well (csrc/trunkstride.hip): no library convolution is left in the trunk')
+    ap.add_argument('--gcn-input', default='plain', choices=('plain', 'factored'),
+                    help='factored: conv1 projects the maps and the global features and every vertex gathers from the '
+                         'projected maps (GCNModel(factored_input=True), csrc/gcn.hip); its [B,N,1511] input is never formed')
     args = ap.parse_args(argv)
     dev = torch.device('cuda')
     torch.manual_seed(1234)
@@ -90,7 +93,7 @@ def main(argv=None):
         vpn = vpn.to(dev).eval()
     else:
         vpn = StandInVPN().to(dev).eval()
-    gcn = GCNModel().to(dev)
+    gcn = GCNModel(factored_input=args.gcn_input == 'factored').to(dev)
     adam = vpn_amd.Adam if args.optimizer == 'hip' else torch.optim.Adam
     optimizer = adam(params=gcn.parameters(), lr=args.lr, betas=(0.9, 0.99), weight_decay=1e-6)      # train_gcn.py:105
     cd_loss_func = vpn_amd.ChamferDistanceLoss()

@@ -521,6 +521,33 @@ int vpn_gcn_input_bwd(const float* grad, const float* verts, const float* bounds
                       void* workspace, float* grad_verts, float* gf0, float* gf1, float* gf2, float* gf3,
                       void* stream);
 
+/* ---- conv1 of the GCN in factored form: h = [encoding | pooled | global] Theta without the row.
+ * Theta [venc + sum C_l + G, Cout] splits row-wise into Theta_e, Theta_l, Theta_g.  The caller projects the maps, proj
+ * [B, sum H_l W_l, Cout] = map_l (NHWC) Theta_l level after level (vpn_gcn_factored_proj_workspace bytes), and the global
+ * features, gtheta [B,Cout] = g Theta_g (NULL: no global block); theta_e [venc,Cout] are Theta's first rows (NULL with
+ * venc = 0).  Cout % 4 == 0; out, proj, gtheta and theta_e are 16-byte aligned.
+ * vpn_gcn_factored_fwd: out [B,N,Cout] = sum_k enc_k(v) Theta_e[k] + sum_l sum_corner w proj_l[b,pix] + gtheta[b], summed
+ *   in that order (corners nw, ne, sw, se) with the grid, corner, weight and validity rules of vpn_gcn_input_fwd; writes
+ *   ext, ext_idx and grid like it (NULL allowed with L = 0).
+ * vpn_gcn_factored_bwd: from grad [B,N,Cout], each skipped when its pointer is NULL: grad_proj [B, sum H_l W_l, Cout] (per
+ *   pixel the weighted sum of grad over the vertices touching it, sorted by cell as in vpn_gcn_input_bwd; N <= 8192),
+ *   grad_theta_e [venc,Cout] = sum_{b,v} enc_k(v) grad (partial sums over 128 rows, then those in order) and grad_verts
+ *   [B,N,3] through the encoding (grad Theta_e^T), the grid and the min / max.  No atomics.  The gradients of Theta_l,
+ *   Theta_g, the maps and the global features are dense products of grad_proj and the column sum of grad with the
+ *   caller's tensors.  workspace: vpn_gcn_factored_bwd_workspace bytes. */
+size_t vpn_gcn_factored_proj_workspace(int B, int Cout, int L, int H0, int W0, int H1, int W1, int H2, int W2, int H3,
+                                       int W3);
+int vpn_gcn_factored_fwd(const float* verts, const float* bounds, const float* gtheta, const float* theta_e,
+                         const float* proj, int B, int N, int Cout, int venc, int L, int H0, int W0, int H1, int W1,
+                         int H2, int W2, int H3, int W3, float* ext, int32_t* ext_idx, float* grid, float* out,
+                         void* stream);
+size_t vpn_gcn_factored_bwd_workspace(int B, int N, int Cout, int venc, int L, int H0, int W0, int H1, int W1, int H2,
+                                      int W2, int H3, int W3);
+int vpn_gcn_factored_bwd(const float* grad, const float* verts, const float* bounds, const float* theta_e,
+                         const float* proj, int B, int N, int Cout, int venc, int L, int H0, int W0, int H1, int W1,
+                         int H2, int W2, int H3, int W3, const float* ext, const int32_t* ext_idx, const float* grid,
+                         void* workspace, float* grad_verts, float* grad_proj, float* grad_theta_e, void* stream);
+
 /* ---- the batch augmentation stage (train.py:232-237): CutMix and the point mix-up.  Outputs are data: no backward.
  * vpn_cutmix_points: cut_mix_batch_points + adjust_point_num (modules/augmentation/cutmix.py:24-50).  points [B,N,3];
  *   indices [B] = the partner of each sample (NULL: every sample is its own partner; a value outside [0,B) is read as

@@ -13,6 +13,9 @@
 //   gcn_pool_bwd_kernel    every feature-map pixel sums the vertices that touch it in a fixed order: no atomics
 //   gcn_vertex_bwd_kernel  backward to the vertices through the encoding and the grid
 //   gcn_extent_bwd_kernel  ... and through the min / max (to the arg-extreme vertex, as torch.max(0) backward)
+//   gcn_factored_*         conv1's product x Theta without the input row: every vertex gathers from the maps
+//                          projected by Theta's row blocks; backward to Theta's encoding rows and to the vertices, the
+//                          projected maps' gradient by gcn_pool_sort_kernel / gcn_pool_bwd_kernel with Cout channels a level
 //
 // Feature maps are read NHWC (one transpose per call, gcn_nhwc_kernel): a vertex's channels are then contiguous and a
 // wave's 64 lanes read two 128-byte lines per corner instead of 64.
@@ -522,6 +525,290 @@ __global__ __launch_bounds__(256) void gcn_extent_bwd_kernel(const float* __rest
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// conv1 in factored form: h = x Theta without x.  proj [B, sum H_l W_l, Cout] holds the projected maps
+// P_l = map_l(NHWC) Theta_l, level after level (a GcnLevels with C[l] = Cout, coff[l] = 0), gtheta [B, Cout] = g Theta_g,
+// theta_e [venc, Cout] the encoding rows of Theta.
+constexpr int GCNF_TV = 32;              // vertices per workgroup of the forward
+constexpr int GCNF_CH = 128;             // channels per workgroup of the forward: 32 lanes of dwordx4 per vertex
+constexpr int GCNF_ENC = 39;             // widest encoding
+constexpr int GCNF_ENC_LD = 40;
+constexpr int GCNF_ENC_ROWS = 128;       // rows per partial sum of dTheta_e
+constexpr int GCNF_BT = 16;              // vertices per workgroup of the vertex backward
+constexpr int GCNF_BC = 512;             // channels per pass of the vertex backward: 4 waves x 64 lanes x 2
+
+// channel k of the encoding of vertex v3 (venc = 3: the vertex itself), as gcn_input_kernel forms it
+__device__ inline float gcn_enc(const float* v3, int k) {
+    if (k < 3) return v3[k];
+    const int kk = (k - 3) / 3, d = k - 3 - kk * 3;
+    const float a = v3[d] * (float)(1 << (kk >> 1));
+    return (kk & 1) ? cosf(a) : sinf(a);
+}
+
+// d enc_k / d v3[k % 3]
+__device__ inline float gcn_enc_deriv(const float* v3, int k) {
+    if (k < 3) return 1.0f;
+    const int kk = (k - 3) / 3, d = k - 3 - kk * 3;
+    const float f = (float)(1 << (kk >> 1));
+    const float a = v3[d] * f;
+    return (kk & 1) ? -f * sinf(a) : f * cosf(a);
+}
+
+// h[b,v,c] = sum_k enc_k(v) Theta_e[k,c] + sum_l sum_corner w P_l[b,pix,c] + gTheta[b,c], summed in that order (corners
+// nw, ne, sw, se).  One workgroup per (32 vertices, 128 channels, sample): Theta_e's chunk and the tile's encodings in LDS,
+// then 32 lanes per vertex, each with 4 channels: every corner is one 512-byte run of dwordx4 loads.
+__global__ __launch_bounds__(256) void gcn_factored_fwd_kernel(const float* __restrict__ verts,
+                                                               const float* __restrict__ grid,
+                                                               const float* __restrict__ proj,
+                                                               const float* __restrict__ gtheta,
+                                                               const float* __restrict__ theta_e, GcnLevels lv, int N,
+                                                               int venc, int Cout, float* __restrict__ out) {
+    __shared__ float s_th[GCNF_ENC * GCNF_CH] __attribute__((aligned(16)));
+    __shared__ float s_enc[GCNF_TV * GCNF_ENC_LD];
+    const int b = blockIdx.z, c0 = blockIdx.y * GCNF_CH, v0 = blockIdx.x * GCNF_TV, t = threadIdx.x;
+    for (int i = t; i < venc * GCNF_CH; i += 256) {
+        const int k = i / GCNF_CH, c = i - k * GCNF_CH;
+        s_th[i] = c0 + c < Cout ? theta_e[(long long)k * Cout + c0 + c] : 0.0f;
+    }
+    for (int i = t; i < GCNF_TV * venc; i += 256) {
+        const int vi = i / venc, k = i - vi * venc, v = v0 + vi;
+        s_enc[vi * GCNF_ENC_LD + k] = v < N ? gcn_enc(verts + ((long long)b * N + v) * 3, k) : 0.0f;
+    }
+    __syncthreads();
+    const int q = t & 31, c = c0 + q * 4;
+    if (c >= Cout) return;                                  // after the only barrier
+    for (int vi = t >> 5; vi < GCNF_TV; vi += 8) {
+        const int v = v0 + vi;
+        if (v >= N) break;
+        const long long row = (long long)b * N + v;
+        float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int k = 0; k < venc; ++k) {
+            const float e = s_enc[vi * GCNF_ENC_LD + k];
+            const float4 th = *reinterpret_cast<const float4*>(&s_th[k * GCNF_CH + q * 4]);
+            acc[0] = fmaf(e, th.x, acc[0]); acc[1] = fmaf(e, th.y, acc[1]);
+            acc[2] = fmaf(e, th.z, acc[2]); acc[3] = fmaf(e, th.w, acc[3]);
+        }
+        if (lv.L > 0) {
+            const float gx = grid[row * 2], gy = grid[row * 2 + 1];
+            for (int l = 0; l < lv.L; ++l) {
+                const int H = lv.H[l], W = lv.W[l];
+                const Bilin qd = bilin(gx, gy, H, W);
+                if (!qd.inside) continue;
+                const float* m = proj + (long long)b * lv.msize + lv.moff[l] + c;
+                const int x1 = qd.x0 + 1, y1 = qd.y0 + 1;
+                const bool vx0 = qd.x0 >= 0, vx1 = x1 < W, vy0 = qd.y0 >= 0, vy1 = y1 < H;
+                float wnw, wne, wsw, wse;
+                {
+#pragma clang fp contract(off)
+                    const float fx1 = (float)x1 - qd.ix, fx0 = qd.ix - (float)qd.x0;
+                    const float fy1 = (float)y1 - qd.iy, fy0 = qd.iy - (float)qd.y0;
+                    wnw = fx1 * fy1; wne = fx0 * fy1; wsw = fx1 * fy0; wse = fx0 * fy0;
+                }
+                // all four loads go out together from addresses clamped into the map; a corner outside it is not added
+                const int xa = vx0 ? qd.x0 : 0, xb = vx1 ? x1 : W - 1, ya = vy0 ? qd.y0 : 0, yb = vy1 ? y1 : H - 1;
+                const float4 pnw = *reinterpret_cast<const float4*>(m + (long long)(ya * W + xa) * Cout);
+                const float4 pne = *reinterpret_cast<const float4*>(m + (long long)(ya * W + xb) * Cout);
+                const float4 psw = *reinterpret_cast<const float4*>(m + (long long)(yb * W + xa) * Cout);
+                const float4 pse = *reinterpret_cast<const float4*>(m + (long long)(yb * W + xb) * Cout);
+                if (vx0 && vy0) {
+                    acc[0] = fmaf(wnw, pnw.x, acc[0]); acc[1] = fmaf(wnw, pnw.y, acc[1]);
+                    acc[2] = fmaf(wnw, pnw.z, acc[2]); acc[3] = fmaf(wnw, pnw.w, acc[3]);
+                }
+                if (vx1 && vy0) {
+                    acc[0] = fmaf(wne, pne.x, acc[0]); acc[1] = fmaf(wne, pne.y, acc[1]);
+                    acc[2] = fmaf(wne, pne.z, acc[2]); acc[3] = fmaf(wne, pne.w, acc[3]);
+                }
+                if (vx0 && vy1) {
+                    acc[0] = fmaf(wsw, psw.x, acc[0]); acc[1] = fmaf(wsw, psw.y, acc[1]);
+                    acc[2] = fmaf(wsw, psw.z, acc[2]); acc[3] = fmaf(wsw, psw.w, acc[3]);
+                }
+                if (vx1 && vy1) {
+                    acc[0] = fmaf(wse, pse.x, acc[0]); acc[1] = fmaf(wse, pse.y, acc[1]);
+                    acc[2] = fmaf(wse, pse.z, acc[2]); acc[3] = fmaf(wse, pse.w, acc[3]);
+                }
+            }
+        }
+        if (gtheta) {
+            const float4 gt = *reinterpret_cast<const float4*>(gtheta + (long long)b * Cout + c);
+            acc[0] += gt.x; acc[1] += gt.y; acc[2] += gt.z; acc[3] += gt.w;
+        }
+        *reinterpret_cast<float4*>(out + row * Cout + c) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    }
+}
+
+// dTheta_e[k,c] = sum_rows enc_k(row) g[row,c] in a fixed order, in the pattern of gcn_colsum_*: partial sums over chunks of
+// 128 rows, then the chunks in order.  One workgroup per (64 channels, chunk): the chunk's encodings in LDS (rows of 40,
+// read four at a time), one thread per channel with the 39 running sums in registers; wave w takes rows w, w + 4, ... and
+// the four waves are added in a fixed order through LDS (the encodings' space, once every wave has read them).
+__global__ __launch_bounds__(256) void gcn_factored_enc_partial_kernel(const float* __restrict__ g,
+                                                                       const float* __restrict__ verts, long long rows,
+                                                                       int venc, int Cout, float* __restrict__ ws) {
+    __shared__ float s_buf[3 * GCNF_ENC * 64] __attribute__((aligned(16)));
+    static_assert(3 * GCNF_ENC * 64 >= GCNF_ENC_ROWS * GCNF_ENC_LD, "the encodings of a chunk fit");
+    const int t = threadIdx.x, w = t >> 6, lane = t & 63, c = blockIdx.x * 64 + lane, p = blockIdx.y;
+    const long long r0 = (long long)p * GCNF_ENC_ROWS;
+    const int nr = (int)(rows - r0 < GCNF_ENC_ROWS ? rows - r0 : GCNF_ENC_ROWS);
+    for (int i = t; i < GCNF_ENC_ROWS * GCNF_ENC_LD; i += 256) {
+        const int r = i / GCNF_ENC_LD, k = i - r * GCNF_ENC_LD;
+        s_buf[i] = (r < nr && k < venc) ? gcn_enc(verts + (r0 + r) * 3, k) : 0.0f;
+    }
+    __syncthreads();
+    const bool live = c < Cout;
+    float acc[GCNF_ENC_LD];                                 // entry 39 pairs with the rows' zero padding
+#pragma unroll
+    for (int k = 0; k < GCNF_ENC_LD; ++k) acc[k] = 0.0f;
+    for (int r = w; r < nr; r += 16) {                     // four rows' gradients in flight; rows past nr are zeros in LDS
+        float gv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) gv[u] = (live && r + 4 * u < nr) ? g[(r0 + r + 4 * u) * Cout + c] : 0.0f;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int k4 = 0; k4 < GCNF_ENC_LD / 4; ++k4) {
+                const float4 e = *reinterpret_cast<const float4*>(&s_buf[(r + 4 * u) * GCNF_ENC_LD + k4 * 4]);
+                acc[k4 * 4 + 0] = fmaf(e.x, gv[u], acc[k4 * 4 + 0]); acc[k4 * 4 + 1] = fmaf(e.y, gv[u], acc[k4 * 4 + 1]);
+                acc[k4 * 4 + 2] = fmaf(e.z, gv[u], acc[k4 * 4 + 2]); acc[k4 * 4 + 3] = fmaf(e.w, gv[u], acc[k4 * 4 + 3]);
+            }
+        }
+    }
+    __syncthreads();
+    if (w > 0) {
+#pragma unroll
+        for (int k = 0; k < GCNF_ENC; ++k) s_buf[((w - 1) * GCNF_ENC + k) * 64 + lane] = acc[k];
+    }
+    __syncthreads();
+    if (w == 0 && live) {
+#pragma unroll
+        for (int k = 0; k < GCNF_ENC; ++k)
+            if (k < venc)
+                ws[((long long)p * venc + k) * Cout + c] =
+                    ((acc[k] + s_buf[(0 * GCNF_ENC + k) * 64 + lane]) + s_buf[(1 * GCNF_ENC + k) * 64 + lane]) +
+                    s_buf[(2 * GCNF_ENC + k) * 64 + lane];
+    }
+}
+
+__global__ __launch_bounds__(256) void gcn_factored_enc_final_kernel(const float* __restrict__ ws, int n, int P,
+                                                                     float* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float acc = 0.0f;
+#pragma unroll 8
+    for (int p = 0; p < P; ++p) acc += ws[(long long)p * n + i];
+    out[i] = acc;
+}
+
+// d/d(vertex) from g = dh: the encoding term g Theta_e^T d enc, and the grid term of gcn_vertex_bwd_kernel with the
+// projected maps in place of the maps and g in place of the per-level columns.  One workgroup per 16 vertices; wave w and
+// lane i own channels 128 w + 2 i (+ 512 per pass), with Theta_e's 39 x 2 entries in registers for the whole tile; the
+// five sums of a vertex are reduced per wave, then over the four waves in a fixed order.
+__global__ __launch_bounds__(256) void gcn_factored_vertex_bwd_kernel(const float* __restrict__ g,
+                                                                      const float* __restrict__ verts,
+                                                                      const float* __restrict__ bounds,
+                                                                      const float* __restrict__ ext,
+                                                                      const float* __restrict__ grid,
+                                                                      const float* __restrict__ proj,
+                                                                      const float* __restrict__ theta_e, GcnLevels lv,
+                                                                      int B, int N, int venc, int Cout,
+                                                                      float* __restrict__ qbuf,
+                                                                      float* __restrict__ dverts) {
+    __shared__ float s_der[GCNF_BT * GCNF_ENC_LD];
+    __shared__ float s_part[4 * GCNF_BT * 5];
+    const long long rows = (long long)B * N, r0 = (long long)blockIdx.x * GCNF_BT;
+    const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+    for (int i = t; i < GCNF_BT * GCNF_ENC_LD; i += 256) {
+        const int vi = i / GCNF_ENC_LD, k = i - vi * GCNF_ENC_LD;
+        s_der[i] = (k < venc && r0 + vi < rows) ? gcn_enc_deriv(verts + (r0 + vi) * 3, k) : 0.0f;
+    }
+    for (int i = t; i < 4 * GCNF_BT * 5; i += 256) s_part[i] = 0.0f;
+    __syncthreads();
+    for (int cp = 0; cp < Cout; cp += GCNF_BC) {
+        const int c = cp + w * 128 + lane * 2;
+        const bool live = c < Cout;                         // Cout is even: c + 1 is a channel when c is
+        float th[GCNF_ENC][2];
+#pragma unroll
+        for (int k = 0; k < GCNF_ENC; ++k) {
+            const bool on = live && k < venc;
+            th[k][0] = on ? theta_e[(long long)k * Cout + c] : 0.0f;
+            th[k][1] = on ? theta_e[(long long)k * Cout + c + 1] : 0.0f;
+        }
+        for (int vi = 0; vi < GCNF_BT; ++vi) {
+            const long long row = r0 + vi;
+            if (row >= rows) break;                         // uniform per workgroup
+            const int b = (int)(row / N);
+            const float* gr = g + row * Cout + c;
+            const float g0 = live ? gr[0] : 0.0f, g1 = live ? gr[1] : 0.0f;
+            float td[3][2] = {{0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}};
+#pragma unroll
+            for (int k = 0; k < GCNF_ENC; ++k) {
+                const float dk = s_der[vi * GCNF_ENC_LD + k];
+                td[k % 3][0] = fmaf(dk, th[k][0], td[k % 3][0]);
+                td[k % 3][1] = fmaf(dk, th[k][1], td[k % 3][1]);
+            }
+            float s[5];
+            s[0] = g0 * td[0][0] + g1 * td[0][1];
+            s[1] = g0 * td[1][0] + g1 * td[1][1];
+            s[2] = g0 * td[2][0] + g1 * td[2][1];
+            s[3] = 0.0f; s[4] = 0.0f;
+            if (lv.L > 0) {
+                const float gxv = grid[row * 2], gyv = grid[row * 2 + 1];
+                for (int l = 0; l < lv.L; ++l) {
+                    const int H = lv.H[l], W = lv.W[l];
+                    const Bilin q = bilin(gxv, gyv, H, W);
+                    if (!q.inside || !live) continue;
+                    const float* m = proj + (long long)b * lv.msize + lv.moff[l] + c;
+                    const int x1 = q.x0 + 1, y1 = q.y0 + 1;
+                    const bool vx0 = q.x0 >= 0, vx1 = x1 < W, vy0 = q.y0 >= 0, vy1 = y1 < H;
+                    const float fx1 = (float)x1 - q.ix, fx0 = q.ix - (float)q.x0;
+                    const float fy1 = (float)y1 - q.iy, fy0 = q.iy - (float)q.y0;
+                    float gix = 0.0f, giy = 0.0f;
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        const float go = j ? g1 : g0;
+                        const float nw = (vx0 && vy0) ? m[(long long)(q.y0 * W + q.x0) * Cout + j] : 0.0f;
+                        const float ne = (vx1 && vy0) ? m[(long long)(q.y0 * W + x1) * Cout + j] : 0.0f;
+                        const float sw = (vx0 && vy1) ? m[(long long)(y1 * W + q.x0) * Cout + j] : 0.0f;
+                        const float se = (vx1 && vy1) ? m[(long long)(y1 * W + x1) * Cout + j] : 0.0f;
+                        gix += ((ne - nw) * fy1 + (se - sw) * fy0) * go;
+                        giy += ((sw - nw) * fx1 + (se - ne) * fx0) * go;
+                    }
+                    s[3] += gix * ((float)(W - 1) * 0.5f);
+                    s[4] += giy * ((float)(H - 1) * 0.5f);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 5; ++j) s[j] = wave_sum(s[j]);
+            if (lane == 0) {                                // this wave's own slots: passes add up in order
+#pragma unroll
+                for (int j = 0; j < 5; ++j) s_part[(w * GCNF_BT + vi) * 5 + j] += s[j];
+            }
+        }
+    }
+    __syncthreads();
+    if (t < GCNF_BT && r0 + t < rows) {
+        const long long row = r0 + t;
+        float s[5];
+#pragma unroll
+        for (int j = 0; j < 5; ++j)
+            s[j] = ((s_part[(0 * GCNF_BT + t) * 5 + j] + s_part[(1 * GCNF_BT + t) * 5 + j]) +
+                    s_part[(2 * GCNF_BT + t) * 5 + j]) + s_part[(3 * GCNF_BT + t) * 5 + j];
+        if (lv.L == 0) {
+            dverts[row * 3 + 0] = s[0];
+            dverts[row * 3 + 1] = s[1];
+            dverts[row * 3 + 2] = s[2];
+        } else {
+            const int b = (int)(row / N);
+            const float* bd = bounds + b * 4;
+            const float* e = ext + b * 4;
+            const float qx = s[3] * -(bd[1] - bd[0]), qy = s[4] * -(bd[3] - bd[2]);
+            qbuf[row * 2] = qx;
+            qbuf[row * 2 + 1] = qy;
+            dverts[row * 3 + 0] = s[0];
+            dverts[row * 3 + 1] = s[1] + qy / (e[3] - e[2]);
+            dverts[row * 3 + 2] = s[2] + qx / (e[1] - e[0]);
+        }
+    }
+}
+
 }  // namespace vpn
 
 using namespace vpn;
@@ -694,6 +981,118 @@ extern "C" int vpn_gcn_input_bwd(const float* grad, const float* verts, const fl
         const long long rows = (long long)B * N;
         VPN_LAUNCH(gcn_vertex_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, grad, verts, bounds, ext,
                    grid, (const float*)maps_ws, lv, B, N, (int)ctot, venc, qbuf, grad_verts);
+        if (L > 0)
+            VPN_LAUNCH(gcn_extent_bwd_kernel, dim3(B), dim3(256), 0, s, verts, ext, (const int*)ext_idx,
+                       (const float*)qbuf, N, grad_verts);
+    }
+    VPN_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- conv1 in factored form
+// the levels of the projected maps: Cout channels each, every level reading the same gradient columns
+static int gcnf_levels(int L, int Cout, int H0, int W0, int H1, int W1, int H2, int W2, int H3, int W3, GcnLevels* lv) {
+    if (Cout <= 0 || (Cout % 4) != 0) return VPN_E_BADARG;
+    const int rc = gcn_levels(L, nullptr, nullptr, nullptr, nullptr, Cout, H0, W0, Cout, H1, W1, Cout, H2, W2, Cout, H3, W3, lv);
+    if (rc) return rc;
+    for (int l = 0; l < L; ++l) lv->coff[l] = 0;
+    return 0;
+}
+
+static bool gcnf_aligned(const void* p) { return ((uintptr_t)p % 16) == 0; }
+
+extern "C" size_t vpn_gcn_factored_proj_workspace(int B, int Cout, int L, int H0, int W0, int H1, int W1, int H2, int W2,
+                                                  int H3, int W3) {
+    GcnLevels lv;
+    if (B <= 0 || gcnf_levels(L, Cout, H0, W0, H1, W1, H2, W2, H3, W3, &lv)) return 0;
+    return (size_t)B * lv.msize * sizeof(float);
+}
+
+extern "C" int vpn_gcn_factored_fwd(const float* verts, const float* bounds, const float* gtheta, const float* theta_e,
+                                    const float* proj, int B, int N, int Cout, int venc, int L, int H0, int W0, int H1,
+                                    int W1, int H2, int W2, int H3, int W3, float* ext, int32_t* ext_idx, float* grid,
+                                    float* out, void* stream) {
+    if (!verts || !out || B <= 0 || N <= 0) return VPN_E_BADARG;
+    if (venc != 0 && venc != 3 && venc != 39) return VPN_E_BADARG;
+    if (venc > 0 && !theta_e) return VPN_E_BADARG;
+    GcnLevels lv;
+    const int rc = gcnf_levels(L, Cout, H0, W0, H1, W1, H2, W2, H3, W3, &lv);
+    if (rc) return rc;
+    if (L > 0 && (!bounds || !ext || !ext_idx || !grid || !proj)) return VPN_E_BADARG;
+    if (!gcnf_aligned(out) || !gcnf_aligned(proj) || !gcnf_aligned(gtheta) || !gcnf_aligned(theta_e)) return VPN_E_BADARG;
+    if ((long long)B * N > 0x7fffffffLL || (long long)B * N * Cout > 0x7fffffffLL * 4 || B > 65535) return VPN_E_TOOBIG;
+    const int cblk = (Cout + GCNF_CH - 1) / GCNF_CH;
+    if (cblk > 65535) return VPN_E_TOOBIG;
+    hipStream_t s = (hipStream_t)stream;
+    if (L > 0) VPN_LAUNCH(gcn_extent_kernel, dim3(B), dim3(1024), 0, s, verts, bounds, N, ext, (int*)ext_idx, grid);
+    VPN_LAUNCH(gcn_factored_fwd_kernel, dim3((N + GCNF_TV - 1) / GCNF_TV, cblk, B), dim3(256), 0, s, verts,
+               (const float*)grid, proj, gtheta, theta_e, lv, N, venc, Cout, out);
+    VPN_LAUNCH_CHECK();
+    return 0;
+}
+
+// workspace of vpn_gcn_factored_bwd: sorted records [B,L,N] float4, cell starts [B, cs_size] int, q [B,N,2], the partial
+// sums of dTheta_e [ceil(B N / 128), venc, Cout]
+static size_t gcnf_bwd_ws(int B, int N, int Cout, int venc, const GcnLevels& lv) {
+    const size_t P = ((size_t)B * N + GCNF_ENC_ROWS - 1) / GCNF_ENC_ROWS;
+    return ((size_t)B * lv.L * N * 4 + (size_t)B * lv.cs_size + (size_t)B * N * 2 + P * venc * Cout) * 4;
+}
+
+extern "C" size_t vpn_gcn_factored_bwd_workspace(int B, int N, int Cout, int venc, int L, int H0, int W0, int H1, int W1,
+                                                 int H2, int W2, int H3, int W3) {
+    GcnLevels lv;
+    if (B <= 0 || N <= 0 || (venc != 0 && venc != 3 && venc != 39) ||
+        gcnf_levels(L, Cout, H0, W0, H1, W1, H2, W2, H3, W3, &lv))
+        return 0;
+    return gcnf_bwd_ws(B, N, Cout, venc, lv);
+}
+
+extern "C" int vpn_gcn_factored_bwd(const float* grad, const float* verts, const float* bounds, const float* theta_e,
+                                    const float* proj, int B, int N, int Cout, int venc, int L, int H0, int W0, int H1,
+                                    int W1, int H2, int W2, int H3, int W3, const float* ext, const int32_t* ext_idx,
+                                    const float* grid, void* workspace, float* grad_verts, float* grad_proj,
+                                    float* grad_theta_e, void* stream) {
+    if (!grad || !verts || B <= 0 || N <= 0) return VPN_E_BADARG;
+    if (venc != 0 && venc != 3 && venc != 39) return VPN_E_BADARG;
+    GcnLevels lv;
+    const int rc = gcnf_levels(L, Cout, H0, W0, H1, W1, H2, W2, H3, W3, &lv);
+    if (rc) return rc;
+    const bool want_proj = grad_proj && L > 0, want_enc = grad_theta_e && venc > 0;
+    if (!want_proj && !want_enc && !grad_verts) return 0;
+    if (!workspace) return VPN_E_BADARG;
+    if (L > 0 && (want_proj || grad_verts) && !grid) return VPN_E_BADARG;
+    if (grad_verts && venc > 0 && !theta_e) return VPN_E_BADARG;
+    if (grad_verts && L > 0 && (!bounds || !ext || !ext_idx || !proj)) return VPN_E_BADARG;
+    if ((long long)B * N > 0x7fffffffLL || (long long)B * N * Cout > 0x7fffffffLL * 4 || B > 65535) return VPN_E_TOOBIG;
+    const long long rows = (long long)B * N;
+    hipStream_t s = (hipStream_t)stream;
+    float4* order = (float4*)workspace;
+    int* cstart = (int*)(order + (size_t)B * L * N);
+    float* qbuf = (float*)(cstart + (size_t)B * lv.cs_size);
+    float* encws = qbuf + (size_t)B * N * 2;
+    if (want_proj) {
+        if (N > GCN_SORT_MAX_N) return VPN_E_TOOBIG;
+        for (int l = 0; l < L; ++l)
+            if ((long long)(lv.H[l] + 1) * (lv.W[l] + 1) >= (1LL << (32 - GCN_SORT_VBITS)) - 1) return VPN_E_TOOBIG;
+        int P2 = 1;
+        while (P2 < N) P2 <<= 1;
+        VPN_LAUNCH(gcn_pool_sort_kernel, dim3(L, B), dim3(1024), 0, s, grid, lv, N, P2, order, cstart);
+        int nblk = 0;
+        for (int l = 0; l < L; ++l) nblk += lv.H[l] * lv.W[l] * ((Cout + 63) / 64);
+        VPN_LAUNCH(gcn_pool_bwd_kernel, dim3(nblk, B), dim3(256), 0, s, grad, (const float4*)order, (const int*)cstart,
+                   lv, N, Cout, 0, grad_proj);
+    }
+    if (want_enc) {
+        const long long P = (rows + GCNF_ENC_ROWS - 1) / GCNF_ENC_ROWS;
+        if (P > 65535) return VPN_E_TOOBIG;
+        VPN_LAUNCH(gcn_factored_enc_partial_kernel, dim3((Cout + 63) / 64, (unsigned)P), dim3(256), 0, s, grad, verts,
+                   rows, venc, Cout, encws);
+        VPN_LAUNCH(gcn_factored_enc_final_kernel, dim3((venc * Cout + 255) / 256), dim3(256), 0, s, (const float*)encws,
+                   venc * Cout, (int)P, grad_theta_e);
+    }
+    if (grad_verts) {
+        VPN_LAUNCH(gcn_factored_vertex_bwd_kernel, dim3((unsigned)((rows + GCNF_BT - 1) / GCNF_BT)), dim3(256), 0, s,
+                   grad, verts, bounds, ext, grid, proj, theta_e, lv, B, N, venc, Cout, qbuf, grad_verts);
         if (L > 0)
             VPN_LAUNCH(gcn_extent_bwd_kernel, dim3(B), dim3(256), 0, s, verts, ext, (const int*)ext_idx,
                        (const float*)qbuf, N, grad_verts);

@@ -12,7 +12,7 @@ import math
 import torch
 import torch.nn as nn
 
-from ..ops import GcnAggregateFunction, GcnInputFunction, gcn_bounds, gcn_edges, gcn_edge_index, gcn_graph
+from ..ops import GcnAggregateFunction, GcnFactoredInputFunction, GcnInputFunction, gcn_bounds, gcn_edges, gcn_edge_index, gcn_graph
 
 
 class GCNConv(nn.Module):
@@ -66,12 +66,18 @@ def to_pyg2_state_dict(state_dict):
 class GCNModel(nn.Module):
     """gcn.py:7-58: same constructor, forward, layers (conv1..conv6, fc) and output
     predict_vertices [B,N,3] = vertices + 0.1 * fc(conv stack).  The graph of meshes[0]'s faces is built once per face
-    topology (ops.gcn_graph) and the image bounds are computed on the device: a step makes no host synchronisation."""
+    topology (ops.gcn_graph) and the image bounds are computed on the device: a step makes no host synchronisation.
 
-    def __init__(self, n_dim=3, img_feature_dim=960 + 512, v_num=2048, use_position_encoding=True):
+    factored_input=True computes conv1's product in factored form (ops.GcnFactoredInputFunction): the
+    maps and the global features are projected by conv1.weight's row blocks and every vertex gathers from the projected
+    maps, so conv1's [B,N,1511] input is never formed.  Parameters, state_dict and both checkpoint layouts are those of
+    the plain model; the result differs from it by fp32 rounding."""
+
+    def __init__(self, n_dim=3, img_feature_dim=960 + 512, v_num=2048, use_position_encoding=True, factored_input=False):
         super().__init__()
         conv = GCNConv
         self.use_position_encoding = use_position_encoding
+        self.factored_input = bool(factored_input)
         self.relu = nn.ReLU()
         n_dim = n_dim + n_dim * 12 if use_position_encoding else n_dim
         self.venc = n_dim
@@ -94,8 +100,13 @@ class GCNModel(nn.Module):
         if self.venc not in (0, 3, 39):
             raise ValueError('GCNModel: the vertex encoding has %d channels; the kernels take 3 (n_dim = 3)' % self.venc)
         bounds = gcn_bounds(rgbs)
-        x = GcnInputFunction.apply(batch_vertices, bounds, global_features, self.venc, *perceptual_features)
-        x = self.conv1(x, graph)
+        if self.factored_input:
+            h = GcnFactoredInputFunction.apply(batch_vertices, bounds, global_features, self.conv1.weight, self.venc,
+                                               *perceptual_features)
+            x = GcnAggregateFunction.apply(h, self.conv1.bias, graph.row_ptr, graph.col, graph.w, False)
+        else:
+            x = GcnInputFunction.apply(batch_vertices, bounds, global_features, self.venc, *perceptual_features)
+            x = self.conv1(x, graph)
         x = self.conv2(x, graph, relu=True)
         x = self.conv3(x, graph)
         x = self.conv4(x, graph, relu=True)

@@ -1266,6 +1266,129 @@ class GcnInputFunction(Function):
         return (gv, None, gg, None) + (tuple(gm) if need_m else (None,) * L)
 
 
+GCN_SORT_MAX_N = 8192           # csrc/gcn.hip: the vertices per sample the pooling backward sorts in LDS
+
+
+def _gcn_factored_check(verts, global_features, weight, venc, maps):
+    """The contract of gcn_factored_input, from shapes alone: ValueError before any launch."""
+    if venc not in (0, 3, 39):
+        raise ValueError('gcn_factored_input: venc is %r; the kernels take 0, 3 or 39' % (venc,))
+    if len(maps) > 4:
+        raise ValueError('gcn_factored_input: %d maps; at most 4' % len(maps))
+    if verts.dim() != 3 or verts.shape[2] != 3 or verts.shape[0] < 1 or verts.shape[1] < 1:
+        raise ValueError('gcn_factored_input: verts must be [B,N,3], got %r' % (tuple(verts.shape),))
+    B, N = int(verts.shape[0]), int(verts.shape[1])
+    if N > GCN_SORT_MAX_N:
+        raise ValueError('gcn_factored_input: N = %d vertices; at most %d' % (N, GCN_SORT_MAX_N))
+    for m in maps:
+        if m.dim() != 4 or m.shape[0] != B or min(m.shape[1:]) < 1:
+            raise ValueError('gcn_factored_input: a map must be [B,C,H,W] with B = %d, got %r' % (B, tuple(m.shape)))
+    G = 0
+    if global_features is not None:
+        if global_features.dim() != 2 or global_features.shape[0] != B:
+            raise ValueError('gcn_factored_input: global_features must be [B,G] with B = %d, got %r'
+                             % (B, tuple(global_features.shape)))
+        G = int(global_features.shape[1])
+    if weight.dim() != 2:
+        raise ValueError('gcn_factored_input: weight must be [ctot,Cout], got %r' % (tuple(weight.shape),))
+    ctot = int(venc) + sum(int(m.shape[1]) for m in maps) + G
+    if int(weight.shape[0]) != ctot:
+        raise ValueError('gcn_factored_input: weight has %d rows; venc + sum C_l + G = %d' % (weight.shape[0], ctot))
+    if int(weight.shape[1]) < 4 or int(weight.shape[1]) % 4:
+        raise ValueError('gcn_factored_input: Cout = %d is not a positive multiple of 4' % weight.shape[1])
+    return B, N, G, int(weight.shape[1])
+
+
+class GcnFactoredInputFunction(Function):
+    """h [B,N,Cout] = [encoding | pooled | global] weight, the product GcnInputFunction + torch.matmul form, without the
+    [B,N,ctot] row: the maps and the global features are projected first (small dense GEMMs, here and
+    not on the autograd tape), then every vertex gathers its 4 corners per level from the projected maps.  weight
+    [venc + sum C_l + G, Cout] is conv1's parameter as it stands and receives one full gradient.  Differentiable w.r.t.
+    verts, global_features, weight and each map; a gradient nobody needs is not computed."""
+
+    @staticmethod
+    def forward(ctx, verts, bounds, global_features, weight, venc, *maps):
+        venc = int(venc)
+        B, N, G, Cout = _gcn_factored_check(verts, global_features, weight, venc, maps)
+        verts, weight = _f32c(verts), _f32c(weight)
+        maps = tuple(_f32c(m) for m in maps)
+        gf = _f32c(global_features) if G else None
+        L, dev = len(maps), verts.device
+        hw = []
+        for m in maps:
+            hw += [int(m.shape[2]), int(m.shape[3])]
+        hw += [0] * (8 - len(hw))
+        rows = [venc]                                        # first weight row of every level, then of the global block
+        for m in maps:
+            rows.append(rows[-1] + int(m.shape[1]))
+        ext = ext_idx = grid = proj = gth = None
+        if L:
+            bounds = _f32c(bounds)
+            ext = torch.empty((B, 4), dtype=torch.float32, device=dev)
+            ext_idx = torch.empty((B, 4), dtype=torch.int32, device=dev)
+            grid = torch.empty((B, N, 2), dtype=torch.float32, device=dev)
+            proj = _workspace('vpn_gcn_factored_proj_workspace', B, Cout, L, *hw, dev=dev).view(B, -1, Cout)
+            p0 = 0
+            for l, m in enumerate(maps):                     # P_l = map_l (NHWC) Theta_l, straight into its pixels
+                n = hw[2 * l] * hw[2 * l + 1]
+                torch.bmm(m.flatten(2).transpose(1, 2), weight[rows[l]:rows[l + 1]].expand(B, -1, -1),
+                          out=proj[:, p0:p0 + n])
+                p0 += n
+        if G:
+            gth = torch.mm(gf, weight[rows[L]:])
+        out = torch.empty((B, N, Cout), dtype=torch.float32, device=dev)
+        _lib.call('vpn_gcn_factored_fwd', verts, bounds if L else None, gth, weight if venc else None, proj, B, N, Cout,
+                  venc, L, *hw, ext, ext_idx, grid, out, _lib.stream())
+        ctx.save_for_backward(verts, bounds if L else None, gf, weight, ext, ext_idx, grid, proj, *maps)
+        ctx.meta = (B, N, G, Cout, venc, L, hw, rows)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        verts, bounds, gf, weight, ext, ext_idx, grid, proj = ctx.saved_tensors[:8]
+        maps = ctx.saved_tensors[8:]
+        B, N, G, Cout, venc, L, hw, rows = ctx.meta
+        g = _f32c(g)
+        dev = g.device
+        need_v, need_g, need_w = ctx.needs_input_grad[0], bool(G) and ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        need_m = [bool(x) for x in ctx.needs_input_grad[5:5 + L]]
+        gv = torch.empty((B, N, 3), dtype=torch.float32, device=dev) if need_v else None
+        gw = torch.empty_like(weight) if need_w else None
+        gproj = None
+        if L and (need_w or any(need_m)):
+            gproj = _workspace('vpn_gcn_factored_proj_workspace', B, Cout, L, *hw, dev=dev).view(B, -1, Cout)
+        if need_v or gproj is not None or (need_w and venc):
+            ws = _workspace('vpn_gcn_factored_bwd_workspace', B, N, Cout, venc, L, *hw, dev=dev, floor=1)
+            _lib.call('vpn_gcn_factored_bwd', g, verts, bounds, weight if venc else None, proj, B, N, Cout, venc, L, *hw,
+                      ext, ext_idx, grid, ws, gv, gproj, gw if venc else None, _lib.stream())   # dTheta_e: gw's first rows
+        gm = [None] * L
+        p0 = 0
+        for l, m in enumerate(maps):
+            n = hw[2 * l] * hw[2 * l + 1]
+            if need_w:                                       # dTheta_l = sum_b map_l^T dP_l
+                torch.sum(torch.bmm(m.flatten(2), gproj[:, p0:p0 + n]), 0, out=gw[rows[l]:rows[l + 1]])
+            if need_m[l]:                                    # dmap_l = Theta_l dP_l^T, NCHW as it comes out
+                gm[l] = torch.bmm(weight[rows[l]:rows[l + 1]].expand(B, -1, -1),
+                                  gproj[:, p0:p0 + n].transpose(1, 2)).view(m.shape)
+            p0 += n
+        gg = None
+        if G and (need_w or need_g):
+            gsum = _colsum(g, None, B, N, Cout, 0, Cout)     # d(g Theta_g) [B,Cout]
+            if need_w:
+                torch.mm(gf.t(), gsum, out=gw[rows[L]:])
+            if need_g:
+                gg = torch.mm(gsum, weight[rows[L]:].t())
+        return (gv, None, gg, gw, None) + tuple(gm)
+
+
+def gcn_factored_input(verts, bounds, global_features, weight, venc, maps):
+    """[encoding(verts) | pooled(maps at the grid of verts and bounds) | global_features] @ weight -> [B,N,Cout] in factored
+    form (GcnFactoredInputFunction).  venc in {0, 3, 39}; at most 4 maps [B,C_l,H_l,W_l] (none allowed: bounds is then
+    unused); global_features [B,G] or None; N <= 8192; weight [venc + sum C_l + G, Cout] with Cout % 4 == 0.  Anything else
+    raises ValueError before any launch."""
+    return GcnFactoredInputFunction.apply(verts, bounds, global_features, weight, venc, *maps)
+
+
 # ---- the batch augmentation stage (csrc/augment.hip).  Plain functions: the augmented tensors are data, nothing here is
 # differentiable and no output requires grad.
 
