@@ -1056,6 +1056,7 @@ struct ScanJob {          // one direction of a Chamfer call
     int cand;                                     // fp16 filter: each workgroup scans its candidate targets only
     const float* qboxes;                          // candidate form: box per 256-row tile of the QUERY cloud in its natural order
                                                   // (= per workgroup; the centre of the ball comes from it), null: computed
+    int walk;                                     // fp16 filter, with tboxes: each wave walks the tiles on its own
 };
 
 // Both directions of a Chamfer call in ONE launch: workgroups [0, j0.G) run job 0, the rest job 1.  Launched
@@ -1106,6 +1107,7 @@ __global__ __launch_bounds__(cm_block<PREC>(), PREC == 1 ? 5 : CM_WAVES_PER_EU) 
     const float* __restrict__ tboxes = PREC == 2 ? (other ? j1.tboxes : j0.tboxes) : nullptr;
     const int cand = PREC == 2 ? (other ? j1.cand : j0.cand) : 0;
     const float* __restrict__ qboxes = PREC == 2 ? (other ? j1.qboxes : j0.qboxes) : nullptr;
+    const int walk = PREC == 2 ? (other ? j1.walk : j0.walk) : 0;
     // The workgroup's list of undecided queries (epilogue): (query, sqrt(m2)) and (query number, index).  A candidate
     // workgroup keeps the fp32 planes of its candidates in the same bytes until its exact finish has read them.
     constexpr int QPW = cm_block<PREC>() / 2;                       // queries per workgroup = capacity of the list
@@ -1422,6 +1424,119 @@ __global__ __launch_bounds__(cm_block<PREC>(), PREC == 1 ? 5 : CM_WAVES_PER_EU) 
                 const unsigned char* T = &tileH16[(t0 + jq) * CM_ROWB + half * 16];
                 CM_SCAN_TILE_Q(T, t0, nblk)
             }
+        } else if (tbox && walk) {
+            // ---- wave walk: with two thirds of the (wave, tile) pairs skipped the shared LDS tile was a
+            // fetch, a stash and a barrier per tile for every wave, needed or not.  Here each wave visits the tiles on its
+            // own, in the same order and with the same test immediately before a tile's MFMAs, so it scans the same tiles
+            // with the same `best` as in the loop below.  Its operands come straight from the row buffer (the sample's
+            // rows sit in this XCD's L2): block k of tile t0 is one contiguous 1-KB run for the 64 lanes.  The first half
+            // of the NEXT wanted tile is requested in the middle of the current one, chosen with the `best` of that
+            // moment: `best` only falls, so that choice is a superset of what the fresh test admits; a tile it admits and
+            // the fresh test rejects is dropped.  Six operand registers in a ring (a tile takes eight): three phases.
+            __syncthreads();                                       // s_cnt is zero for everybody (this loop has no barrier)
+            const unsigned loff = (unsigned)(jq * CM_ROWB16 + half * 16);
+            // The sample's rows as a buffer: descriptor and tile offset are wave-uniform and live in scalar registers, so the
+            // lane offset is the only address VGPR of the loop.  The descriptor ends with the rows: what a short last tile
+            // requests behind them reads as zero and is never used.
+            const __amdgpu_buffer_rsrc_t rows =
+                __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(Hb), 0, Ntp * CM_ROWB16, 0x00020000);   // raw, 32-bit data
+            auto ldb = [&](int t0, int k) -> float4 {              // this lane's 16 bytes of block k of tile t0
+                return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
+                    rows, loff, (t0 + 32 * k) * CM_ROWB16, 0));
+            };
+            // The boxes were written by an earlier launch: read through the constant address space they are scalar loads
+            // (counted apart from the row loads in flight; as ordinary loads each test waited for every row requested before it).
+            typedef float cbox4 __attribute__((ext_vector_type(4)));
+            typedef float cbox2 __attribute__((ext_vector_type(2)));
+            const __attribute__((address_space(4))) float* cbox = (const __attribute__((address_space(4))) float*)(uintptr_t)tbox;
+            auto wanted = [&](int t0) -> bool {                    // the test of the loop below, with this moment's `best`
+                const cbox4 bl = *(const __attribute__((address_space(4))) cbox4*)(cbox + (t0 >> 8) * CFEAT_BOXF);
+                const cbox2 bh = *(const __attribute__((address_space(4))) cbox2*)(cbox + (t0 >> 8) * CFEAT_BOXF + 4);
+                const float dx = fmaxf(fmaxf(bl.x - ax, ax - bl.w), 0.0f);
+                const float dy = fmaxf(fmaxf(bl.y - ay, ay - bh.x), 0.0f);
+                const float dz = fmaxf(fmaxf(bl.z - az, az - bh.y), 0.0f);
+                const float L = ((dx * dx + dy * dy) + dz * dz) * (1.0f - 1.0e-6f);
+                return __ballot(!(L > __builtin_fmaf(best, CM_INV_S16SQ, skipc))) != 0ull;
+            };
+            auto next = [&](int t0) -> int {                       // first wanted tile at or behind t0, Ntp: none
+                while (t0 < Ntp && !wanted(t0)) t0 += CM_TILE16;
+                return t0;
+            };
+#ifdef VPN_CHAMFER_DEBUG
+            int nscan = 0;
+#define CM_WALK_COUNT ++nscan;
+#else
+#define CM_WALK_COUNT
+#endif
+// CM_PAIR with the update of `second` pinned in place: left to the scheduler it sinks behind later pairs and keeps
+// their minima alive, in a loop that has no register to spare
+#define CM_PAIR_W(oa, ob, J)                                                                   \
+    {                                                                                          \
+        const f16v accA = block(oa), accB = block(ob);                                         \
+        const float mAB = min32(accA, accB);                                                   \
+        unsigned long long k1_;                                                                \
+        asm volatile("v_cmp_lt_f32 %0, %1, %2" : "=s"(k1_) : "v"(mAB), "v"(best));             \
+        asm volatile("v_med3_f32 %0, %1, %0, %2" : "+v"(second) : "v"(best), "v"(mAB));        \
+        asm volatile("v_cndmask_b32 %0, %1, " #J ", %2" : "=v"(blkc) : "v"(blkc), "s"(k1_));   \
+        asm volatile("v_min_f32 %0, %1, %2" : "=v"(best) : "v"(best), "v"(mAB));               \
+    }
+// One scanned tile of the full ones (rows below Nfull).  On entry blocks 0..3 of tile tc are in, or on their way to,
+// A B C D; on exit the same blocks of the next wanted tile are in C D E F, which the next phase calls A B C D.  Every
+// load is issued on every path (with no tile to come the current one is requested again and never used), so the
+// compiler counts exactly how many loads may stay in flight at each wait.
+#define CM_WALK_TILE(A, B, C, D, E, F)                                                         \
+    {                                                                                          \
+        if (!wanted(tc)) {                       /* fresh test: the tile was requested on a stale bound */ \
+            tc = next(tc + CM_TILE16);                                                         \
+            if (tc >= Nfull) break;                                                            \
+            A = ldb(tc, 0); B = ldb(tc, 1); C = ldb(tc, 2); D = ldb(tc, 3);                    \
+        }                                                                                      \
+        CM_WALK_COUNT                                                                          \
+        blkc = -1;                               /* no pair of this tile has improved the minimum yet */ \
+        E = ldb(tc, 4); F = ldb(tc, 5);                                                        \
+        CM_PAIR_W(A, B, 0)                                                                     \
+        A = ldb(tc, 6); B = ldb(tc, 7);                                                        \
+        CM_PAIR_W(C, D, 1)                                                                     \
+        const int tn = next(tc + CM_TILE16);     /* stale bound: two pairs of this tile are still to come */ \
+        const int tl = tn < Nfull ? tn : tc;                                                   \
+        C = ldb(tl, 0); D = ldb(tl, 1);                                                        \
+        CM_PAIR_W(E, F, 2)                                                                     \
+        E = ldb(tl, 2); F = ldb(tl, 3);                                                        \
+        CM_PAIR_W(A, B, 3)                                                                     \
+        blk = blkc >= 0 ? tc + (blkc << 6) : blk;       /* the tile improved this lane's minimum */ \
+        tc = tn;                                                                               \
+        if (tc >= Nfull) break;                                                                \
+    }
+            const int Nfull = Ntp & ~(CM_TILE16 - 1);
+            int tc = next(0);
+            if (tc < Nfull) {
+                float4 r0 = ldb(tc, 0), r1 = ldb(tc, 1), r2 = ldb(tc, 2), r3 = ldb(tc, 3);
+                float4 r4 = make_float4(0.f, 0.f, 0.f, 0.f), r5 = r4;
+                for (;;) {
+                    CM_WALK_TILE(r0, r1, r2, r3, r4, r5)
+                    CM_WALK_TILE(r2, r3, r4, r5, r0, r1)
+                    CM_WALK_TILE(r4, r5, r0, r1, r2, r3)
+                }
+            }
+            if (tc < Ntp && wanted(tc)) {        // the short last tile (2, 4 or 6 blocks), if a wave wants it: nothing to overlap with
+                const int nblk = (Ntp - tc) >> 5;
+                CM_WALK_COUNT
+                const float before = best;
+                float4 a0 = ldb(tc, 0), a1 = ldb(tc, 1), b0 = ldb(tc, 2), b1 = ldb(tc, 3);
+                CM_PAIR(a0, a1, 0)
+                if (nblk > 2) {
+                    a0 = ldb(tc, 4); a1 = ldb(tc, 5);
+                    CM_PAIR(b0, b1, 1)
+                    if (nblk > 4) CM_PAIR(a0, a1, 2)
+                }
+                blk = best < before ? tc + (blkc << 6) : blk;
+            }
+#ifdef VPN_CHAMFER_DEBUG
+            if (lane == 0) atomicAdd(&g_dbg[3], (unsigned long long)((Ntp + CM_TILE16 - 1) / CM_TILE16 - nscan));   // skipped (wave, tile) pairs
+#endif
+#undef CM_WALK_TILE
+#undef CM_PAIR_W
+#undef CM_WALK_COUNT
         } else {
         Pre pre = fetch(0);
         stash(0, pre);
@@ -2127,6 +2242,16 @@ static int chamfer_cand() {
     return on;
 }
 
+// VPN_CHAMFER_WAVEWALK=0 puts direction 2 of the fp16 scan back on the shared LDS tile loop (A/B runs and tests of one build)
+static int chamfer_wavewalk() {
+    static int on = -1;
+    if (on < 0) {
+        const char* e = getenv("VPN_CHAMFER_WAVEWALK");
+        on = !(e && e[0] == '0') ? 1 : 0;
+    }
+    return on;
+}
+
 static inline int pad32(int n) { return (n + 63) & ~63; }   // feature planes padded to 64 targets (blocks are processed in pairs)
 // one direction: fp32 planes + bf16 rows of the targets + one tile of slack (the row tiles are fetched without
 // bounds checks) + nmax[B][CFEAT_SLOTS] + the lists of undecided queries (count[pad4(B)], 16-byte entries[B][Nq])
@@ -2185,9 +2310,9 @@ static int mfma_both(const float* p1, const float* p2, int B, int N, int M, floa
         const int gx1 = (N + qpw - 1) / qpw, gx2 = (M + qpw - 1) / qpw;
         // (its queries are p1 in natural order: the tile boxes of p1, written for direction 2's skipping, are its workgroups')
         const ScanJob s1{p1, w2.F, w2.H, w2.nmax, N, M, w2.Ntp, gx1, gx1 * B, d1, i1, w2.wgsum, nullptr, nullptr,   // p1 against p2
-                         cand(N, M, nullptr), f1.tboxes};
+                         cand(N, M, nullptr), f1.tboxes, 0};
         const ScanJob s2{p2, w1.F, w1.H, w1.nmax, M, N, w1.Ntp, gx2, gx2 * B, d2, i2, w1.wgsum,                     // p2 against p1
-                         f2.perm, f1.tboxes, cand(M, N, f1.tboxes), nullptr};
+                         f2.perm, f1.tboxes, cand(M, N, f1.tboxes), nullptr, chamfer_wavewalk()};
         const bool long_first = (long long)N > (long long)M;       // direction 2 scans the N targets: more work per workgroup
         const ScanJob& ja = long_first ? s2 : s1;
         const ScanJob& jb = long_first ? s1 : s2;
