@@ -52,6 +52,16 @@ def test_encoding_and_pooling_against_g7(vpn):
     assert rel_err(v.grad.cpu(), z['grad_verts']) <= 1e-4
     for i, m in enumerate(maps):
         assert rel_err(m.grad.cpu(), z['grad_map%d' % i]) <= 1e-4, i
+    # the rows that hold an extent carry a sum over all vertices and set the norm-wise scale: the others, and they, each
+    # element-wise against float64, no worse than 1e-3 nor than 4 x the fixture's own fp32 error (tests/gcn_input_ref.py)
+    import gcn_input_ref as G
+    fm = [z['map%d' % i] for i in range(4)]
+    rows = dict(masked=G.undecidable_rows(z['verts'], z['bounds'], fm), extent=G.extent_rows(z['verts']))
+    v64 = z['verts'].double().requires_grad_(True)
+    (R.pooling([m.double() for m in fm], v64, z['bounds'].double()) * z['W'].double()).sum().backward()
+    mine, own = G.split_errors(v.grad.cpu(), v64.grad, rows), G.split_errors(z['grad_verts'], v64.grad, rows)
+    print('g7_gcn_pooling dverts split (O, E): kernel %.2e %.2e, fixture %.2e %.2e' % (mine + own))
+    assert mine[0] <= G.split_bar(own[0]) and mine[1] <= G.split_bar(own[1]), (mine, own)
 
 
 @pytest.mark.parametrize('C', [3, 64, 512, 1511])

@@ -50,6 +50,16 @@ def test_op_against_float64(vpn, name):
     assert errs.pop('h') <= 1e-5
     for k, e in errs.items():
         assert e <= 1e-4, (k, e)
+    # dverts again, split into the rows that hold an extent and the others (tests/gcn_input_ref.py): each element-wise, no
+    # worse than 1e-3 nor than 4 x the error of the plain form evaluated in fp32 on the CPU
+    import gcn_input_ref as G
+    v32, w32 = c['verts'].clone().requires_grad_(True), c['weight'].clone()
+    (F.plain(v32, c['bounds'], c['glob'], w32, c['venc'], c['maps']) * c['R']).sum().backward()
+    masked = G.undecidable_rows(c['verts'], c['bounds'], c['maps']) if c['maps'] else torch.zeros(dv.shape[:2], dtype=torch.bool)
+    rows = dict(masked=masked, extent=G.extent_rows(c['verts']))
+    mine, own = G.split_errors(dv.cpu(), dv64, rows), G.split_errors(v32.grad, dv64, rows)
+    print(name, 'dverts split (O, E): kernel %.2e %.2e, fp32 restatement %.2e %.2e' % (mine + own))
+    assert mine[0] <= G.split_bar(own[0]) and mine[1] <= G.split_bar(own[1]), (mine, own)
 
 
 def test_gradients_nobody_needs_are_skipped(vpn):

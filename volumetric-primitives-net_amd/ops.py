@@ -1208,12 +1208,17 @@ def _gcn_dims(maps):
     return dims + [0] * (12 - len(dims))
 
 
+GCN_SORT_MAX_N = 8192           # csrc/gcn.hip: the vertices per sample the pooling backward sorts in LDS
+
+
 class GcnInputFunction(Function):
     """conv1's input [B,N,venc + sum C_l + G] = [encoding | pooled | global] (gcn.py:36-42) in one pass, no torch.cat:
     venc = 39 (positional encoding, gcn.py:73-82), 3 (the vertices) or 0; pooled = perceptual_feature_pooling
     (gcn.py:135-164) of the L <= 4 NCHW maps at the grid given by bounds [B,4] and the per-sample z / y extents of
     verts [B,N,3]; global_features [B,G] (or None) repeated over the vertices.  Differentiable w.r.t. verts (through
-    the encoding, the grid and the min / max), the maps and the global features."""
+    the encoding, the grid and the min / max), the maps and the global features.  The maps' gradient sorts the vertices
+    of a sample in LDS: with N > GCN_SORT_MAX_N a map that requires a gradient is a ValueError here, before any launch
+    (the forward and the vertices' gradient take any N)."""
 
     @staticmethod
     def forward(ctx, verts, bounds, global_features, venc, *maps):
@@ -1221,6 +1226,9 @@ class GcnInputFunction(Function):
         B, N, _ = verts.shape
         L = len(maps)
         assert L <= 4 and verts.shape[2] == 3
+        if N > GCN_SORT_MAX_N and any(ctx.needs_input_grad[4:4 + L]):
+            raise ValueError('GcnInputFunction: N = %d vertices and a map requires a gradient; its backward sorts at most '
+                             '%d per sample' % (N, GCN_SORT_MAX_N))
         maps = tuple(_f32c(m) for m in maps)
         for m in maps:
             assert m.dim() == 4 and m.shape[0] == B, m.shape
@@ -1264,9 +1272,6 @@ class GcnInputFunction(Function):
             ctot = g.shape[2]
             gg = _colsum(g, None, B, N, ctot, ctot - G, G)
         return (gv, None, gg, None) + (tuple(gm) if need_m else (None,) * L)
-
-
-GCN_SORT_MAX_N = 8192           # csrc/gcn.hip: the vertices per sample the pooling backward sorts in LDS
 
 
 def _gcn_factored_check(verts, global_features, weight, venc, maps):
