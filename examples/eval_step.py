@@ -1,7 +1,7 @@
 """The evaluation loops of the reference on the drop-in surface, with stand-in networks and synthetic data.
 
     python examples/eval_step.py [--batches 6] [--batch 8]          # test.py:68-135: Chamfer only
-    python examples/eval_step.py --gcn [--gcn-input factored]       # test_gcn.py:115-178: Chamfer + EMD on refined vertices
+    python examples/eval_step.py --gcn [--gcn-input factored] [--gcn-collapse]     # test_gcn.py:115-178: Chamfer + EMD on refined vertices
 
     python examples/eval_step.py --dump DIR [--three-elev] [--gcn]  # also write the visual dump of sample 0 every third batch
 
@@ -63,7 +63,7 @@ def test(args, dev):
 @torch.no_grad()
 def test_gcn(args, dev):
     vpn = StandInVPN().to(dev).eval()
-    gcn = GCNModel(factored_input=args.gcn_input == 'factored').to(dev).eval()
+    gcn = GCNModel(factored_input=args.gcn_input == 'factored', collapse_pairs=args.gcn_collapse).to(dev).eval()
     meter = vpn_amd.EvaluationMeter(CLASS_NAMES, dev, emd=True)
     for it, (b, class_indices) in enumerate(batches(args.batches, args.batch)):
         rgbs = torch.zeros(b, 3, 128, 128, device=dev)
@@ -85,6 +85,8 @@ def main(argv=None):
     ap.add_argument('--gcn', action='store_true', help='the test_gcn.py loop (Chamfer + EMD on the refined vertices)')
     ap.add_argument('--gcn-input', default='plain', choices=('plain', 'factored'),
                     help='with --gcn: conv1 of the GCN in factored form (GCNModel(factored_input=True))')
+    ap.add_argument('--gcn-collapse', action='store_true',
+                    help='with --gcn: every pair of GCN layers as one linear map (GCNModel(collapse_pairs=True))')
     ap.add_argument('--batches', type=int, default=6)
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--epoch', type=int, default=0)

@@ -1,6 +1,6 @@
 """The refinement step of the reference's train_gcn.py (:119-138) on the drop-in surface, with synthetic inputs.
 
-    python examples/train_gcn_step.py [--steps 5] [--batch 8] [--net standin|vpnet_oneres] [--vpn CKPT] [--gcn-input plain|factored]
+    python examples/train_gcn_step.py [--steps 5] [--batch 8] [--net standin|vpnet_oneres] [--vpn CKPT] [--gcn-input plain|factored] [--gcn-collapse]
 
 --net vpnet_oneres runs the reference's frozen VPNetOneRes (modules/network.py; --vpn CKPT loads a reference checkpoint
 into it as train_gcn.py:100-102 does, otherwise it is randomly initialised).  By default a stand-in
@@ -83,6 +83,9 @@ def main(argv=None):
     ap.add_argument('--gcn-input', default='plain', choices=('plain', 'factored'),
                     help='factored: conv1 projects the maps and the global features and every vertex gathers from the '
                          'projected maps (GCNModel(factored_input=True), csrc/gcn.hip); its [B,N,1511] input is never formed')
+    ap.add_argument('--gcn-collapse', action='store_true',
+                    help='every pair of layers without a ReLU between them as one linear map: one long product a pair, both '
+                         'propagations in one launch (GCNModel(collapse_pairs=True), csrc/gcnpair.hip)')
     args = ap.parse_args(argv)
     dev = torch.device('cuda')
     torch.manual_seed(1234)
@@ -93,7 +96,7 @@ def main(argv=None):
         vpn = vpn.to(dev).eval()
     else:
         vpn = StandInVPN().to(dev).eval()
-    gcn = GCNModel(factored_input=args.gcn_input == 'factored').to(dev)
+    gcn = GCNModel(factored_input=args.gcn_input == 'factored', collapse_pairs=args.gcn_collapse).to(dev)
     adam = vpn_amd.Adam if args.optimizer == 'hip' else torch.optim.Adam
     optimizer = adam(params=gcn.parameters(), lr=args.lr, betas=(0.9, 0.99), weight_decay=1e-6)      # train_gcn.py:105
     cd_loss_func = vpn_amd.ChamferDistanceLoss()

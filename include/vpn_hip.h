@@ -548,6 +548,28 @@ int vpn_gcn_factored_bwd(const float* grad, const float* verts, const float* bou
                          int H2, int W2, int H3, int W3, const float* ext, const int32_t* ext_idx, const float* grid,
                          void* workspace, float* grad_verts, float* grad_proj, float* grad_theta_e, void* stream);
 
+/* ---- the GCN's layer pairs as one linear map each (csrc/gcnpair.hip).
+ * vpn_gcn_aggregate2: out [B,N,C] = A( A h + 1 (x) u ) + 1 (x) bias, then max(., 0) when relu != 0; u and bias [C] may be
+ *   NULL.  A in CSR form as for vpn_gcn_aggregate.  blocks [nblocks + 1] int32: ascending starts of index ranges of at
+ *   most 128 rows that cover [0, N) and that no entry of A crosses (blocks[0] = 0, blocks[nblocks] = N); both hops of a
+ *   range run in LDS.  An entry that leaves its range is not added; a range that is empty, longer than 128 or outside
+ *   [0, N] is not computed.  Each hop sums a row in CSR order as vpn_gcn_aggregate does and the intermediate is rounded
+ *   to fp32: out equals two calls of vpn_gcn_aggregate bit for bit.  mask != NULL ([B,N,C]): h counts only where mask > 0
+ *   (the backward of a ReLU'd pair: out = the gradient of h).  du_partial != NULL ([B, nblocks, C],
+ *   vpn_gcn_aggregate2_workspace bytes): the sum over each range's rows, in row order, of the intermediate A h + u; its
+ *   column sum over (b, range) is the gradient of u when the call is a backward.  No atomics.
+ * vpn_gcn_project_fwd: out [R,Co] = x [R,Ci] theta [Ci,Co] for Co <= 4 and Ci <= 1024, every result the fixed-order sum of
+ *   a wave.  vpn_gcn_project_bwd: dx [R,Ci] = grad theta^T (NULL: skipped) and dtheta [Ci,Co] = x^T grad (NULL: skipped)
+ *   as partial sums over 64-row chunks (workspace: vpn_gcn_project_bwd_workspace bytes) added in chunk order.  No atomics. */
+size_t vpn_gcn_aggregate2_workspace(int B, int nblocks, int C);
+int vpn_gcn_aggregate2(const float* h, const float* mask, const int32_t* row_ptr, const int32_t* col, const float* w,
+                       const int32_t* blocks, int nblocks, const float* u, const float* bias, int B, int N, int C,
+                       int relu, float* out, float* du_partial, void* stream);
+size_t vpn_gcn_project_bwd_workspace(int R, int Ci, int Co);
+int vpn_gcn_project_fwd(const float* x, const float* theta, int R, int Ci, int Co, float* out, void* stream);
+int vpn_gcn_project_bwd(const float* grad, const float* x, const float* theta, int R, int Ci, int Co, void* workspace,
+                        float* dx, float* dtheta, void* stream);
+
 /* ---- the batch augmentation stage (train.py:232-237): CutMix and the point mix-up.  Outputs are data: no backward.
  * vpn_cutmix_points: cut_mix_batch_points + adjust_point_num (modules/augmentation/cutmix.py:24-50).  points [B,N,3];
  *   indices [B] = the partner of each sample (NULL: every sample is its own partner; a value outside [0,B) is read as

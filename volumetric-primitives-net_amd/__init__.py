@@ -9,7 +9,8 @@ from .ops import (SPHERE, CUBOID, SampleFunction, TransformFunction, ChamferFunc
                   RasterLossFunction, RasterTotalFunction, HotPathLossFunction, TrainStepLossFunction, chamfer_nn, kinds_tensor,
                   emd_recovered_samples, emd_last_group, eval_step, vis_primitives, vis_mesh, phong_mesh,
                   cluster_points, support_hulls, hull_meshes, hull_augment, union_surface, acd_mix_points,
-                  GcnFactoredInputFunction, gcn_factored_input)
+                  GcnFactoredInputFunction, gcn_factored_input,
+                  GcnAggregate2Function, gcn_aggregate2, GcnProjectFunction, gcn_project, gcn_blocks)
 from .primitives import PrimitivePack, pack_primitives, kinds_from_counts
 from .modules import (Sampling, ChamferDistanceLoss, EarthMoverDistanceLoss, SilhouetteLoss, VPDiverseLoss, VertexRenderer, PhongRenderer,
                       transform_points, rotate_points, translate_points, view_to_obj_points,

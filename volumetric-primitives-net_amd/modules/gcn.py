@@ -12,7 +12,8 @@ import math
 import torch
 import torch.nn as nn
 
-from ..ops import GcnAggregateFunction, GcnFactoredInputFunction, GcnInputFunction, gcn_bounds, gcn_edges, gcn_edge_index, gcn_graph
+from ..ops import (GcnAggregateFunction, GcnFactoredInputFunction, GcnInputFunction, gcn_aggregate2, gcn_blocks, gcn_bounds,
+                   gcn_edges, gcn_edge_index, gcn_graph, gcn_project)
 
 
 class GCNConv(nn.Module):
@@ -71,13 +72,22 @@ class GCNModel(nn.Module):
     factored_input=True computes conv1's product in factored form (ops.GcnFactoredInputFunction): the
     maps and the global features are projected by conv1.weight's row blocks and every vertex gathers from the projected
     maps, so conv1's [B,N,1511] input is never formed.  Parameters, state_dict and both checkpoint layouts are those of
-    the plain model; the result differs from it by fp32 rounding."""
+    the plain model; the result differs from it by fp32 rounding.
 
-    def __init__(self, n_dim=3, img_feature_dim=960 + 512, v_num=2048, use_position_encoding=True, factored_input=False):
+    collapse_pairs=True computes every pair of layers without a ReLU between them (conv1 conv2, conv3 conv4, conv5 conv6)
+    as one linear map: A_hat and Theta act on different axes, so conv_b(conv_a(x)) =
+    A_hat(A_hat(x Theta_a Theta_b) + b_a Theta_b) + b_b.  The weight products are small dense GEMMs on the autograd tape,
+    the two propagations one launch (ops.gcn_aggregate2), and conv5 conv6's 512 -> 3 product ops.gcn_project.  With
+    factored_input the product Theta_1 Theta_2 takes conv1.weight's place in the factored op.  Parameters, state_dict and
+    both checkpoint layouts are again those of the plain model; the result differs from it by fp32 rounding."""
+
+    def __init__(self, n_dim=3, img_feature_dim=960 + 512, v_num=2048, use_position_encoding=True, factored_input=False,
+                 collapse_pairs=False):
         super().__init__()
         conv = GCNConv
         self.use_position_encoding = use_position_encoding
         self.factored_input = bool(factored_input)
+        self.collapse_pairs = bool(collapse_pairs)
         self.relu = nn.ReLU()
         n_dim = n_dim + n_dim * 12 if use_position_encoding else n_dim
         self.venc = n_dim
@@ -100,21 +110,42 @@ class GCNModel(nn.Module):
         if self.venc not in (0, 3, 39):
             raise ValueError('GCNModel: the vertex encoding has %d channels; the kernels take 3 (n_dim = 3)' % self.venc)
         bounds = gcn_bounds(rgbs)
-        if self.factored_input:
-            h = GcnFactoredInputFunction.apply(batch_vertices, bounds, global_features, self.conv1.weight, self.venc,
-                                               *perceptual_features)
-            x = GcnAggregateFunction.apply(h, self.conv1.bias, graph.row_ptr, graph.col, graph.w, False)
+        if self.collapse_pairs:
+            x = self._forward_collapsed(meshes[0].faces, batch_vertices, graph, bounds, perceptual_features, global_features)
         else:
-            x = GcnInputFunction.apply(batch_vertices, bounds, global_features, self.venc, *perceptual_features)
-            x = self.conv1(x, graph)
-        x = self.conv2(x, graph, relu=True)
-        x = self.conv3(x, graph)
-        x = self.conv4(x, graph, relu=True)
-        x = self.conv5(x, graph)
-        x = self.conv6(x, graph, relu=True)
+            if self.factored_input:
+                h = GcnFactoredInputFunction.apply(batch_vertices, bounds, global_features, self.conv1.weight, self.venc,
+                                                   *perceptual_features)
+                x = GcnAggregateFunction.apply(h, self.conv1.bias, graph.row_ptr, graph.col, graph.w, False)
+            else:
+                x = GcnInputFunction.apply(batch_vertices, bounds, global_features, self.venc, *perceptual_features)
+                x = self.conv1(x, graph)
+            x = self.conv2(x, graph, relu=True)
+            x = self.conv3(x, graph)
+            x = self.conv4(x, graph, relu=True)
+            x = self.conv5(x, graph)
+            x = self.conv6(x, graph, relu=True)
         x = x.reshape(x.size(0), -1)
         deformations = self.fc(x).view(x.size(0), -1, 3) * 0.1
         return batch_vertices + deformations
+
+    @staticmethod
+    def _pair(a, b):
+        """(Theta_a Theta_b, b_a Theta_b) of two layers in a row: their one weight and the bias between the two hops."""
+        return torch.matmul(a.weight, b.weight), torch.matmul(a.bias, b.weight)
+
+    def _forward_collapsed(self, faces, verts, graph, bounds, maps, glob):
+        blocks = gcn_blocks(faces, verts.size(1), verts.device)
+        theta, u = self._pair(self.conv1, self.conv2)
+        if self.factored_input:
+            h = GcnFactoredInputFunction.apply(verts, bounds, glob, theta, self.venc, *maps)
+        else:
+            h = torch.matmul(GcnInputFunction.apply(verts, bounds, glob, self.venc, *maps), theta)
+        x = gcn_aggregate2(h, u, self.conv2.bias, graph, blocks, relu=True)
+        theta, u = self._pair(self.conv3, self.conv4)
+        x = gcn_aggregate2(torch.matmul(x, theta), u, self.conv4.bias, graph, blocks, relu=True)
+        theta, u = self._pair(self.conv5, self.conv6)
+        return gcn_aggregate2(gcn_project(x, theta), u, self.conv6.bias, graph, blocks, relu=True)
 
     @staticmethod
     def get_edge_indices(mesh):

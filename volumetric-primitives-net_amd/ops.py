@@ -1394,6 +1394,187 @@ def gcn_factored_input(verts, bounds, global_features, weight, venc, maps):
     return GcnFactoredInputFunction.apply(verts, bounds, global_features, weight, venc, *maps)
 
 
+# ---- the layer pairs of the GCN as one linear map each (csrc/gcnpair.hip)
+
+GCN_HOP2_MAX_ROWS = 128         # csrc/gcnpair.hip: the rows of a block, both hops of which run in LDS
+GCN_PROJECT_MAX_CI = 1024       # csrc/gcnpair.hip: the rows of Theta the skinny projection stages in LDS
+GCN_PROJECT_MAX_CO = 4
+
+_GCN_BLOCKS = {}
+
+
+def gcn_closed_ranges(edges, n):
+    """Starts (ascending, the first is 0) of the finest split of [0, n) into consecutive index ranges that no edge of
+    `edges` (E, 2) crosses: i starts a range when no edge (a, b), a < b, has a < i <= b.  Host list of ints."""
+    e = edges.long().reshape(-1, 2)
+    d = torch.zeros(n + 1, dtype=torch.long)
+    if e.numel():
+        lo, hi = e.min(1)[0], e.max(1)[0]
+        d.index_add_(0, lo + 1, torch.ones_like(lo))
+        d.index_add_(0, hi + 1, -torch.ones_like(hi))
+    cover = torch.cumsum(d, 0)[:n]
+    return torch.nonzero(cover == 0).flatten().tolist()
+
+
+def gcn_block_starts(edges, n, limit=GCN_HOP2_MAX_ROWS):
+    """The block table of `edges` over n vertices as a host list [0, ..., n]: consecutive closed ranges
+    (gcn_closed_ranges) merged left to right while a block keeps at most `limit` rows.  None when a closed range alone
+    has more."""
+    closed = gcn_closed_ranges(edges, n) + [n]
+    starts = [0]
+    for i in range(1, len(closed)):
+        if closed[i] - closed[i - 1] > limit:
+            return None
+        if closed[i] - starts[-1] > limit:
+            starts.append(closed[i - 1])
+    return starts + [n]
+
+
+def gcn_blocks(faces, n, device):
+    """The block table of a face topology for gcn_aggregate2: int32 [nblocks + 1] starts on `device` of index ranges of at
+    most GCN_HOP2_MAX_ROWS vertices that cover [0, n) and that no edge crosses, or None when the mesh has no such table
+    (gcn_aggregate2 then takes two one-hop launches).  Built on the host once per (face content, n, device), like
+    gcn_graph: a repeated step does no host work, no device read and no synchronisation."""
+    key = (faces_fingerprint(faces), int(n), str(torch.device(device)))
+    if key not in _GCN_BLOCKS:
+        if len(_GCN_BLOCKS) > 64:
+            _GCN_BLOCKS.clear()
+        edges = gcn_edges(faces)
+        if edges.numel() and int(edges.max()) >= n:
+            raise ValueError('faces index vertex %d of a %d-vertex mesh' % (int(edges.max()), n))
+        starts = gcn_block_starts(edges, int(n))
+        _GCN_BLOCKS[key] = None if starts is None else torch.tensor(starts, dtype=torch.int32).to(device)
+    return _GCN_BLOCKS[key]
+
+
+def _gcn_aggregate2_check(h, u, bias, graph, blocks):
+    """The contract of gcn_aggregate2, from shapes alone: ValueError before any launch."""
+    if h.dim() != 3 or min(h.shape) < 1:
+        raise ValueError('gcn_aggregate2: h must be [B,N,C], got %r' % (tuple(h.shape),))
+    B, N, C = (int(s) for s in h.shape)
+    if graph.row_ptr.numel() != N + 1:
+        raise ValueError('gcn_aggregate2: the graph has %d vertices, h has %d' % (graph.row_ptr.numel() - 1, N))
+    for name, v in (('u', u), ('bias', bias)):
+        if v is not None and tuple(v.shape) != (C,):
+            raise ValueError('gcn_aggregate2: %s must be [C] with C = %d, got %r' % (name, C, tuple(v.shape)))
+    if blocks is not None and (blocks.dim() != 1 or blocks.dtype != torch.int32 or not 2 <= blocks.numel() <= N + 1):
+        raise ValueError('gcn_aggregate2: blocks must be int32 [nblocks + 1] with 1 <= nblocks <= N = %d (ops.gcn_blocks), '
+                         'got %s %r' % (N, blocks.dtype, tuple(blocks.shape)))
+    return B, N, C
+
+
+class GcnAggregate2Function(Function):
+    """y [B,N,C] = A_hat (A_hat h + u) + bias (ReLU'd when relu): two propagations of GcnAggregateFunction back to back,
+    bit-equal to them.  With a block table (ops.gcn_blocks) both hops of a block run in LDS in one launch and the
+    intermediate never reaches memory; with blocks = None they are two one-hop launches through a scratch buffer.  Backward:
+    dh = A_hat A_hat (g * [y > 0]) by the same launch on the masked gradient, du = the column sum of its intermediate (per
+    block in row order, then the blocks in order), dbias = the column sum of the masked gradient.  No atomics; only y is
+    saved, and only when relu."""
+
+    @staticmethod
+    def forward(ctx, h, u, bias, row_ptr, col, w, blocks, relu=False):
+        h = _f32c(h)
+        B, N, C = h.shape
+        uu = _f32c(u) if u is not None else None
+        bb = _f32c(bias) if bias is not None else None
+        y = torch.empty_like(h)
+        if blocks is not None:
+            _lib.call('vpn_gcn_aggregate2', h, None, row_ptr, col, w, blocks, blocks.numel() - 1, uu, bb, B, N, C,
+                      int(bool(relu)), y, None, _lib.stream())
+        else:
+            t = torch.empty_like(h)
+            _lib.call('vpn_gcn_aggregate', h, row_ptr, col, w, uu, None, B, N, C, 0, t, _lib.stream())
+            _lib.call('vpn_gcn_aggregate', t, row_ptr, col, w, bb, None, B, N, C, int(bool(relu)), y, _lib.stream())
+        ctx.save_for_backward(row_ptr, col, w, blocks, y if relu else None)
+        ctx.meta = (B, N, C, u is not None, bias is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        row_ptr, col, w, blocks, y = ctx.saved_tensors
+        B, N, C, has_u, has_bias = ctx.meta
+        g = _f32c(g)
+        need_h, need_u = ctx.needs_input_grad[0], has_u and ctx.needs_input_grad[1]
+        gh = gu = gb = None
+        if (need_h or need_u) and blocks is not None:
+            nb = blocks.numel() - 1
+            gh = torch.empty_like(g)
+            part = _workspace('vpn_gcn_aggregate2_workspace', B, nb, C, dev=g.device) if need_u else None
+            _lib.call('vpn_gcn_aggregate2', g, y, row_ptr, col, w, blocks, nb, None, None, B, N, C, 0, gh, part, _lib.stream())
+            if need_u:
+                gu = _colsum(part, None, 1, B * nb, C, 0, C).reshape(C)
+        elif need_h or need_u:
+            t = torch.empty_like(g)
+            _lib.call('vpn_gcn_aggregate', g, row_ptr, col, w, None, y, B, N, C, 0, t, _lib.stream())
+            if need_h:
+                gh = torch.empty_like(g)
+                _lib.call('vpn_gcn_aggregate', t, row_ptr, col, w, None, None, B, N, C, 0, gh, _lib.stream())
+            if need_u:
+                gu = _colsum(t, None, 1, B * N, C, 0, C).reshape(C)
+        if has_bias and ctx.needs_input_grad[2]:
+            gb = _colsum(g, y, 1, B * N, C, 0, C).reshape(C)
+        return gh if need_h else None, gu, gb, None, None, None, None, None
+
+
+def gcn_aggregate2(h, u, bias, graph, blocks=None, relu=False):
+    """A_hat (A_hat h + u) + bias, ReLU'd when relu (GcnAggregate2Function): h [B,N,C], u and bias [C] or None, graph a
+    GcnGraph over N vertices, blocks the table ops.gcn_blocks gives for the same faces (None: two one-hop launches, the
+    same bits).  Anything else raises ValueError before any launch."""
+    _gcn_aggregate2_check(h, u, bias, graph, blocks)
+    return GcnAggregate2Function.apply(h, u, bias, graph.row_ptr, graph.col, graph.w, blocks, relu)
+
+
+def _gcn_project_check(x, theta):
+    """The contract of gcn_project, from shapes alone: ValueError before any launch."""
+    if theta.dim() != 2 or min(theta.shape) < 1:
+        raise ValueError('gcn_project: theta must be [Ci,Co], got %r' % (tuple(theta.shape),))
+    Ci, Co = int(theta.shape[0]), int(theta.shape[1])
+    if Co > GCN_PROJECT_MAX_CO:
+        raise ValueError('gcn_project: Co = %d output columns; at most %d (wider products are torch.matmul)'
+                         % (Co, GCN_PROJECT_MAX_CO))
+    if Ci > GCN_PROJECT_MAX_CI:
+        raise ValueError('gcn_project: Ci = %d; at most %d' % (Ci, GCN_PROJECT_MAX_CI))
+    if x.dim() < 1 or int(x.shape[-1]) != Ci or x.numel() == 0:
+        raise ValueError('gcn_project: x must be [..., Ci] with Ci = %d and at least one row, got %r' % (Ci, tuple(x.shape)))
+    return x.numel() // Ci, Ci, Co
+
+
+class GcnProjectFunction(Function):
+    """out [..., Co] = x [..., Ci] theta [Ci, Co] for Co <= 4: the memory-bound product no GEMM tile fits (conv5 . conv6
+    of the collapsed GCN is 512 -> 3).  x is read once, every result is the fixed-order sum of a wave.  Backward: dx =
+    g theta^T and dtheta = x^T g as 64-row partial sums added in chunk order, one launch plus the final sum; either is
+    skipped when nobody needs it.  No atomics."""
+
+    @staticmethod
+    def forward(ctx, x, theta):
+        R, Ci, Co = _gcn_project_check(x, theta)
+        x, theta = _f32c(x), _f32c(theta)
+        out = torch.empty(x.shape[:-1] + (Co,), dtype=torch.float32, device=x.device)
+        _lib.call('vpn_gcn_project_fwd', x, theta, R, Ci, Co, out, _lib.stream())
+        ctx.save_for_backward(x, theta)
+        ctx.meta = (R, Ci, Co)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, theta = ctx.saved_tensors
+        R, Ci, Co = ctx.meta
+        g = _f32c(g)
+        need_x, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gx = torch.empty_like(x) if need_x else None
+        gt = torch.empty_like(theta) if need_t else None
+        if need_x or need_t:
+            ws = _workspace('vpn_gcn_project_bwd_workspace', R, Ci, Co, dev=g.device) if need_t else None
+            _lib.call('vpn_gcn_project_bwd', g, x, theta, R, Ci, Co, ws, gx, gt, _lib.stream())
+        return gx, gt
+
+
+def gcn_project(x, theta):
+    """x [..., Ci] @ theta [Ci, Co] -> [..., Co] for Co <= 4 and Ci <= 1024 (GcnProjectFunction).  Anything else raises
+    ValueError before any launch."""
+    return GcnProjectFunction.apply(x, theta)
+
+
 # ---- the batch augmentation stage (csrc/augment.hip).  Plain functions: the augmented tensors are data, nothing here is
 # differentiable and no output requires grad.
 
