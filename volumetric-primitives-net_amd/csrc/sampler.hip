@@ -26,8 +26,11 @@ struct PrimLds {
 };
 
 // face quotas of cuboid.py:30-53: round-half-even(n * area_f / total) for faces 0..4,
-// remainder to face 5.  Same fp32 operation order as the reference.
+// remainder to face 5.  Same fp32 operation order as the reference, every product and sum rounded by itself: with
+// h * d + d * w contracted to an FMA the total of a cube of half extent 1e-4 came out one ulp high, its weights one
+// ulp under 1/6, and the exact ties n / 6 = 1.5, 3.5 (n = 9, 21) rounded down where the reference rounds to even.
 __device__ inline void cuboid_quota(const float v[3], int n, int cum[7]) {
+#pragma clang fp contract(off)
     float w = v[0], h = v[1], d = v[2];
     float hd = h * d, dw = d * w, wh = w * h;
     float total = (hd + dw + wh) * 2.0f;
@@ -52,8 +55,14 @@ __device__ inline void canonical_coeff(const PrimLds& P, int p, const float u[3]
         // transcendental calls of a point: the kernel is bound by instruction issue).  The reference's own chain carries
         // the rounding of pi/2 - acos(w) (6e-8 absolute in the angle); the closed form is within that of it, i.e. 1e-7
         // of a coefficient that is then scaled by the primitive's extent (the parity bar is 1e-4).
-        const float w = 1.0f - 2.0f * u[0];
-        const float ce = 2.0f * sqrtf(u[0] * (1.0f - u[0]));
+        // The reference's pi/2 is half the fp32 pi, 4.37e-8 above pi/2: its elevation is the exact one plus that, so its
+        // (cos, sin) are the closed form turned by 4.37e-8 (first order; the next term is 1e-15).  At a pole that is a
+        // cos(elev) of -4.37e-8 where the closed form alone has 0 -- the whole gradient of a primitive turning about its
+        // own polar axis, which is held to its own scale like any other.
+        const float w0 = 1.0f - 2.0f * u[0];
+        const float ce0 = 2.0f * sqrtf(u[0] * (1.0f - u[0]));
+        const float w = fmaf(VPN_HALF_PI_EXCESS, ce0, w0);
+        const float ce = fmaf(-VPN_HALF_PI_EXCESS, w0, ce0);
         const float azim = u[1] * 2.0f * VPN_PI;                    // sphere.py:27
         float sa, ca;
         sincosf(azim, &sa, &ca);                                    // one range reduction for both
@@ -360,14 +369,17 @@ __global__ __launch_bounds__(SCB_BLOCK) void sample_chamfer_bwd_kernel(
     // The canonical coefficient c of a point (p = R (c * v) + t) is RECOVERED from the point the forward pass wrote,
     // c = R^T (p - t) / v: 12 instructions instead of redrawing the Philox uniforms and redoing acos / sin / cos
     // (~300: two thirds of this kernel's instructions).  It differs from the forward's c by rounding only (1e-7
-    // relative; the gradient is a 1e-4 contract).  The error of a recovered c_a is ~2^-24 |p| / |v_a| (p - t cancels):
-    // a THIN primitive (smallest extent below 1e-3 of the size of the numbers it is subtracted from; the network's
-    // range, vpnet_one_resnet.py:71,84, stays 10x above that) falls back to the exact recomputation from the uniforms /
-    // the Philox counter, uniformly for the workgroup.
+    // relative; the gradient is a 1e-4 contract, held per primitive).  The error of a recovered c_a is ~2^-24 |p| / |v_a|
+    // (p - t cancels) and goes straight into grad_v.  Measured per primitive against float64 (tests/test_pose_domain.py,
+    // |t| = 1), largest of the draws tried: 1.5e-4 with the smallest extent at 1e-3 of the size of the numbers it is subtracted from, 1.2e-5 at
+    // 2e-3, 3.3e-6 at 1e-2, 1.2e-6 at 1e-1; the redrawn coefficient is at 5e-7 throughout.  So a THIN primitive --
+    // smallest extent below 1e-2 of that size, which the clamp head reaches (extent 0.01 / 10 against |t| = 1,
+    // vpnet_one_resnet.py:71,84), the sigmoid head does not -- falls back to the exact recomputation from the uniforms
+    // / the Philox counter, uniformly for the workgroup.
     const float tx = prm[7], ty = prm[8], tz = prm[9];
     const float vmin = fminf(fminf(fabsf(P.v[0]), fabsf(P.v[1])), fabsf(P.v[2]));
     const float big = fmaxf(fmaxf(fmaxf(fabsf(tx), fabsf(ty)), fabsf(tz)), fmaxf(fmaxf(fabsf(P.v[0]), fabsf(P.v[1])), fabsf(P.v[2])));
-    const bool recover = vmin >= 1.0e-3f * big && vmin > 1e-20f;
+    const bool recover = vmin >= 1.0e-2f * big && vmin > 1e-20f;
     const float iv0 = recover ? 1.0f / P.v[0] : 0.0f, iv1 = recover ? 1.0f / P.v[1] : 0.0f, iv2 = recover ? 1.0f / P.v[2] : 0.0f;
     auto add = [&](int pl, float gx, float gy, float gz) {              // point pl of this primitive gets gradient g
         float c[3];

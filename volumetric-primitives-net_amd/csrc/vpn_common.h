@@ -6,6 +6,7 @@
 #include "../../include/vpn_hip.h"
 
 #define VPN_PI 3.1415927410125732f   // fp32 pi of modules/sampling/sphere.py:7, transform/rotate.py:4
+#define VPN_HALF_PI_EXCESS 4.371139e-8f   // VPN_PI / 2 - pi / 2: how far the reference's pi * 0.5 (sphere.py:26) lies above pi/2
 
 #define VPN_LAUNCH_CHECK()                                  \
     do {                                                    \
