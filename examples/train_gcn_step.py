@@ -1,6 +1,6 @@
 """The refinement step of the reference's train_gcn.py (:119-138) on the drop-in surface, with synthetic inputs.
 
-    python examples/train_gcn_step.py [--steps 5] [--batch 8] [--net standin|vpnet_oneres] [--vpn CKPT] [--gcn-input plain|factored] [--gcn-collapse]
+    python examples/train_gcn_step.py [--steps 5] [--batch 8] [--net standin|vpnet_oneres] [--vpn CKPT] [--gcn-input plain|factored] [--gcn-collapse] [--vpn-fold]
 
 --net vpnet_oneres runs the reference's frozen VPNetOneRes (modules/network.py; --vpn CKPT loads a reference checkpoint
 into it as train_gcn.py:100-102 does, otherwise it is randomly initialised).  By default a stand-in
@@ -86,7 +86,13 @@ def main(argv=None):
     ap.add_argument('--gcn-collapse', action='store_true',
                     help='every pair of layers without a ReLU between them as one linear map: one long product a pair, both '
                          'propagations in one launch (GCNModel(collapse_pairs=True), csrc/gcnpair.hip)')
+    ap.add_argument('--vpn-fold', action='store_true',
+                    help='the frozen VPNetOneRes runs its trunk in the inference form: every batch norm folded into the convolution '
+                         'before it, bias, residual add and ReLU in the convolution\'s epilogue (ResNet18.fold(), csrc/trunkfold.hip); '
+                         'needs --net vpnet_oneres; the --trunk-* choices select nothing then')
     args = ap.parse_args(argv)
+    if args.vpn_fold and not (args.vpn or args.net == 'vpnet_oneres'):
+        ap.error('--vpn-fold needs --net vpnet_oneres (or --vpn CKPT): the stand-in has no trunk to fold')
     dev = torch.device('cuda')
     torch.manual_seed(1234)
     if args.vpn or args.net == 'vpnet_oneres':
@@ -94,6 +100,8 @@ def main(argv=None):
         if args.vpn:
             vpn.load_state_dict(torch.load(args.vpn, map_location='cpu'))
         vpn = vpn.to(dev).eval()
+        if args.vpn_fold:
+            vpn.resnet.fold()
     else:
         vpn = StandInVPN().to(dev).eval()
     gcn = GCNModel(factored_input=args.gcn_input == 'factored', collapse_pairs=args.gcn_collapse).to(dev)

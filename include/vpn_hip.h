@@ -1107,6 +1107,23 @@ int vpn_conv2d_fwd(const float* x, const float* w, float* y, int B, int C_in, in
 int vpn_conv2d_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, int B, int C_in, int C_out, int H, int W,
                    int R, int stride, int pad, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the trunk's convolutions for eval-mode inference (csrc/trunkfold.hip): vpn_conv2d_fwd's product with
+ * an epilogue, forward only:  y = act(conv(x, w) + bias[c_out] + residual), act the ReLU when relu = 1, the identity when 0.
+ * It replaces nn.Conv2d + nn.BatchNorm2d (eval) + add + ReLU reached through the reference's vpnet_one_resnet.py:45-57 once the
+ * norm's fixed scale has been multiplied into w and its shift is `bias` (a fold the caller makes once; all 20 convolution sites
+ * of the ResNet-18 trunk when nothing is trained: train_gcn.py:100-125, test.py, test_gcn.py).
+ * x, w, y as vpn_conv2d_fwd; bias DEVICE fp32 [C_out] or NULL; residual DEVICE fp32 of y's shape, contiguous, or NULL; it may
+ * not overlap y.  Per element, in this order: v = conv + bias[c_out]; v += residual; v = v < 0 ? 0 : v (a NaN stays a NaN).
+ * With bias and residual NULL and relu 0 the result equals vpn_conv2d_fwd's bit for bit.
+ * The slices and the workspace are vpn_conv2d_splits(..., VPN_CONV_FWD) and vpn_conv2d_workspace(..., VPN_CONV_FWD): an unsplit
+ * product applies the epilogue at its store (one launch); a split one writes raw partials and the launch that adds them in the
+ * order 0 .. S - 1 applies it (two launches).  No host synchronisation, nothing allocated, no atomics: bit-equal from run to
+ * run, capturable.  Added without a change of VPN_ABI_VERSION.
+ * Every rejection of vpn_conv2d_fwd, with its code; relu not 0 or 1: VPN_E_BADARG.  All before any HIP call. */
+int vpn_conv2d_bias_act_fwd(const float* x, const float* w, const float* bias, const float* residual, float* y, int B, int C_in,
+                            int C_out, int H, int W, int R, int stride, int pad, int relu, void* workspace, size_t workspace_bytes,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,5 +19,5 @@ from .modules import (Sampling, ChamferDistanceLoss, EarthMoverDistanceLoss, Sil
                       points_to_meshes_and_colors, points_to_mesh_batch, meshes_to_imgs, generate_point_mixup_data, acd, augment,
                       acd_mix_meshes, acd_mix_data, EvaluationMeter, prepare_images,
                       MeshBatch, sample_gt_points, gt_points, view_center_xforms, genre_xforms,
-                      Visualizer, FcHeads, batch_norm_act, batch_norm_relu_pool, batch_norm_act_mean, conv3x3, conv2d, ResNet18, VPNetOneRes, VPNetTwoRes, SDNet, Adam)
+                      Visualizer, FcHeads, batch_norm_act, batch_norm_relu_pool, batch_norm_act_mean, conv3x3, conv2d, conv2d_bias_act, fold_batch_norm, ResNet18, VPNetOneRes, VPNetTwoRes, SDNet, Adam)
 from . import modules

@@ -1,5 +1,5 @@
-// vpn_conv_gemm.h — the implicit GEMM D[m][n] = sum_k A[m][k] B[k][n] on the f32-input MFMA that csrc/trunkconv.hip and
-// csrc/trunkstride.hip share: everything that does not depend on how an operand element is found.
+// vpn_conv_gemm.h — the implicit GEMM D[m][n] = sum_k A[m][k] B[k][n] on the f32-input MFMA that csrc/trunkconv.hip,
+// csrc/trunkstride.hip and csrc/trunkfold.hip share: everything that does not depend on how an operand element is found.
 //   * cg_tile: a workgroup of 256 (4 waves, 2 x 2) owns a 64 x 64 tile of D, every wave a 32 x 32 quarter in 16 accumulator
 //     registers of v_mfma_f32_32x32x2_f32; K is walked in chunks of 16 through LDS ([k][m] and [k][n], so a wave reads its
 //     operands along consecutive lanes), the next chunk's global loads are issued before the current chunk's MFMAs.  Where
@@ -47,10 +47,17 @@ __device__ __forceinline__ void cg_store(const CgStage& st, float (*As)[CG_LD], 
     }
 }
 
+// What cg_tile does with a finished element: `v` belongs at out[idx], row m of D.  The default stores it as it is; a kernel
+// with more to do at the store (csrc/trunkfold.hip: bias, residual, ReLU) names its own.
+struct CgPlainStore {
+    template <class Args>
+    __device__ static __forceinline__ void store(const Args&, float* out, size_t idx, unsigned, float v) { out[idx] = v; }
+};
+
 // One tile of one slice; grid (tiles of N, tiles of M, S).  PIXELS: column n of D is pixel n % PHW of image n / PHW of an
 // NCHW result with M channels (forward, data gradient); otherwise D is stored row-major (weight gradient).  Forced inline
 // with the args by value, as the kernel holds them: behind a reference the compiler schedules the loop differently.
-template <class Map, bool PIXELS, class Args>
+template <class Map, bool PIXELS, class Epilogue = CgPlainStore, class Args>
 __device__ __forceinline__ void cg_tile(const Args g) {
     __shared__ float As[CG_K][CG_LD];
     __shared__ float Bs[CG_K][CG_LD];
@@ -89,7 +96,7 @@ __device__ __forceinline__ void cg_tile(const Args g) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const unsigned m = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * half;
-        if (m < g.M) out[base + (size_t)m * pitch] = acc[r];
+        if (m < g.M) Epilogue::store(g, out, base + (size_t)m * pitch, m, acc[r]);
     }
 }
 
@@ -143,8 +150,10 @@ static void cg_fill(Args& g, const CgPlan& p, const float* a, const float* b, fl
     g.M = p.M; g.N = p.N; g.K = p.K; g.chunks = p.chunks; g.S = p.S; g.total = p.total;
 }
 
-// after the GEMM launch of a split product: the partials of the workspace into `out`
-static int cg_merge(const CgPlan& p, const void* ws, float* out, hipStream_t st) {
+// after the GEMM launch of a split product: the partials of the workspace into `out`.  A template (Plan is CgPlan) so that
+// only a file that calls it instantiates cg_merge_kernel: csrc/trunkfold.hip merges with an epilogue of its own
+template <class Plan>
+static int cg_merge(const Plan& p, const void* ws, float* out, hipStream_t st) {
     if (p.S == 1) return 0;
     const bool vec = p.total % 4 == 0 && ((uintptr_t)out & 15) == 0;          // the workspace is 16-byte aligned (checked)
     const long long units = vec ? p.total / 4 : p.total;

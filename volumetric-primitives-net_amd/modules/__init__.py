@@ -5,7 +5,7 @@ from .loss import ChamferDistanceLoss, EarthMoverDistanceLoss, SilhouetteLoss, V
 from .render import VertexRenderer, PhongRenderer
 from .transform import (transform_points, rotate_points, translate_points, view_to_obj_points,
                         obj_to_view_points, rotate_points_forward_x_axis)
-from .network import (pack_head_outputs, split_primitives, batch_norm_act, batch_norm_relu_pool, batch_norm_act_mean, conv3x3, conv2d, GCNModel, GCNConv, FcHeads, ResNet18, VPNetOneRes, VPNetTwoRes,
+from .network import (pack_head_outputs, split_primitives, batch_norm_act, batch_norm_relu_pool, batch_norm_act_mean, conv3x3, conv2d, conv2d_bias_act, fold_batch_norm, GCNModel, GCNConv, FcHeads, ResNet18, VPNetOneRes, VPNetTwoRes,
                       SDNet)
 from .meshing import Meshing, TriangleMesh, load_obj, merge_meshes
 from .dataset import (parse_split_csv, parse_rendering_metadata, split_rgba, prepare_images, resized_size, MeshBatch,

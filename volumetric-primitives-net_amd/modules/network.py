@@ -5,7 +5,9 @@ around them by default; with `hip_conv` the 3x3 stride-1 convolutions of the cho
 `hip_conv_strided` the seven stride-2 ones (the stem, layerN.0.conv1, layerN.0.downsample.0) on csrc/trunkstride.hip (the
 nn.Conv2d modules then only HOLD the weights); with `fused_norm=True` each batch norm, with the residual add and the ReLU that follow it, is one
 op on csrc/trunknorm.hip (the nn.BatchNorm2d modules then only HOLD parameters and buffers), with `fused_pool` / `fused_tail` the
-stem's max pool and the global average pool are part of the norm site before them; the FC heads, the one part of the networks that is nothing but weight traffic, run on csrc/fcstack.hip: their
+stem's max pool and the global average pool are part of the norm site before them; ResNet18.fold() makes the inference form
+for a trunk that is not trained (eval mode under no_grad: train_gcn.py's frozen VPN, test.py): every batch norm folded into
+the convolution before it, bias, residual add and ReLU in the convolution's epilogue on csrc/trunkfold.hip; the FC heads, the one part of the networks that is nothing but weight traffic, run on csrc/fcstack.hip: their
 nn.Linear modules only HOLD the parameters, the forward hands the tensors to FcStackFunction, which also applies what
 follows the last layer (restrict_range + split + restrict_volumes into packed rows, or SDNet's tanh).  GCNModel (gcn.py,
 the refinement stage of train_gcn.py / test_gcn.py) is re-exported from modules/gcn.py, so that
@@ -14,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from .. import config
-from ..ops import HeadPackFunction, FcStackFunction, BatchNormActFunction, BatchNormPoolFunction, BatchNormMeanFunction, Conv3x3Function, Conv2dFunction
+from ..ops import HeadPackFunction, FcStackFunction, BatchNormActFunction, BatchNormPoolFunction, BatchNormMeanFunction, Conv3x3Function, Conv2dFunction, conv2d_bias_act
 from .gcn import GCNModel, GCNConv  # noqa: F401
 
 
@@ -91,6 +93,41 @@ def conv2d(x, weight, stride=1, padding=0):
     stride and padding are ints (both directions alike).  With a 3x3 weight, stride 1 and padding 1 it equals conv3x3 bit
     for bit."""
     return Conv2dFunction.apply(x, weight, stride, padding)
+
+
+def fold_batch_norm(weight, bn: nn.BatchNorm2d):
+    """(w', b') with conv2d(x, w') + b' = bn(conv2d(x, weight)) in eval mode: the norm's fixed scale
+    s = gamma / sqrt(running_var + eps), formed in float64, multiplied into the rows of `weight` (C_out, C_in, R, R), and
+    its shift b' = beta - running_mean s; both rounded to fp32 once.  On the tensors' device, no host synchronisation.  The
+    mode of `bn` is not asked: the fold is the eval-mode norm.  A norm without affine parameters or without running
+    statistics is refused."""
+    if bn.weight is None or bn.bias is None:
+        raise ValueError('fold_batch_norm: the norm has no affine parameters (affine=False)')
+    if bn.running_mean is None or bn.running_var is None:
+        raise ValueError('fold_batch_norm: the norm has no running statistics (track_running_stats=False)')
+    if weight.dim() != 4 or weight.shape[0] != bn.weight.shape[0]:
+        raise ValueError('fold_batch_norm: weight must be (C_out, C_in, R, R) with C_out = %d, got %s' % (bn.weight.shape[0], tuple(weight.shape)))
+    with torch.no_grad():
+        s = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
+        return ((weight.double() * s.view(-1, 1, 1, 1)).float(), (bn.bias.double() - bn.running_mean.double() * s).float())
+
+
+def _is_fold_conv(conv):
+    """A convolution csrc/trunkfold.hip holds: square kernel of 1, 3 or 7, one stride and one padding, no bias."""
+    k, p = conv.kernel_size, conv.padding
+    return (k[0] == k[1] and k[0] in (1, 3, 7) and conv.stride[0] == conv.stride[1] and not isinstance(p, str) and p[0] == p[1] and
+            conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None and conv.padding_mode == 'zeros')
+
+
+def _fold_act(x, conv, folded, residual=None, relu=True):
+    """One folded site: `conv` gives the stride and the padding, `folded` = (w', b') the tensors."""
+    return conv2d_bias_act(x, folded[0], folded[1], residual, conv.stride[0], conv.padding[0], relu)
+
+
+def _use_fold(model):
+    """The folded path is taken when a fold exists, the trunk is not in training mode and grad mode is off: autograd needs
+    the unfolded graph."""
+    return getattr(model, '_fold', None) is not None and not model.training and not torch.is_grad_enabled()
 
 
 def _is_trunk_conv_strided(conv):
@@ -196,7 +233,9 @@ class ResNet18(nn.Module):
     fused_norm says; self.maxpool stays registered and is not called.
     fused_tail=True: layer4[1]'s relu(bn2(conv2(.)) + identity) and the global average pool are one op on csrc/trunknorm.hip
     (batch_norm_act_mean) whatever fused_norm says; self.avgpool stays registered and is not called.  The five keywords are
-    independent; the state_dict is the same either way."""
+    independent; the state_dict is the same either way.
+    fold() / unfold(): the inference form (every norm folded into its convolution, 20 launches of conv2d_bias_act on
+    csrc/trunkfold.hip and the two pools), taken only in eval mode with grad mode off; see fold()."""
 
     def __init__(self, num_classes=1000, fused_norm=False, hip_conv=False, hip_conv_strided=False, fused_pool=False,
                  fused_tail=False):
@@ -221,6 +260,7 @@ class ResNet18(nn.Module):
         self.layer4 = nn.Sequential(BasicBlock(256, 512, 2, **k), BasicBlock(512, 512, **k))
         self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
         self.fc = nn.Linear(512, num_classes)
+        self._fold = None                              # fold(): the inference form, a plain attribute
         for m in self.modules():                       # torchvision's initialisation
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
@@ -253,7 +293,71 @@ class ResNet18(nn.Module):
             x = block(x)
         return self.layer4[-1].forward_tail(x)
 
+    def _fold_sites(self):
+        """The 20 (convolution, norm) sites in the order the folded forward calls them: the stem, then per block conv1,
+        the downsample where there is one, conv2."""
+        sites = [(self.conv1, self.bn1)]
+        for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
+            for block in layer:
+                sites.append((block.conv1, block.bn1))
+                if block.downsample is not None:
+                    sites.append((block.downsample[0], block.downsample[1]))
+                sites.append((block.conv2, block.bn2))
+        return sites
+
+    @staticmethod
+    def _fold_sources(sites):
+        """The tensors a fold of `sites` reads."""
+        return [t for conv, bn in sites for t in (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+
+    def fold(self):
+        """The inference form of the trunk: every batch norm folded into the convolution before it
+        (fold_batch_norm), from the modules as they stand.  While the fold exists, the trunk is in eval mode and grad mode
+        is off, forward and the models' extract_feature run 20 conv2d_bias_act on csrc/trunkfold.hip (bias, residual add
+        and ReLU in the convolution's epilogue) and the two pools; the five keywords select nothing there.  In any other
+        setting the trunk runs as without a fold.  The folded tensors are a plain attribute: no parameter, buffer or
+        module is registered, the state_dict is unchanged.  The fold remembers the version of every tensor it read; a
+        forward after one of them changed (load_state_dict, an optimiser step, .to(device)) raises and asks for fold()
+        again.  Returns self."""
+        sites = self._fold_sites()
+        for conv, _bn in sites:
+            if not _is_fold_conv(conv):
+                raise ValueError('fold: csrc/trunkfold.hip holds square kernels of 1, 3 or 7 without bias only, got %r' % (conv,))
+        pairs = [fold_batch_norm(conv.weight, bn) for conv, bn in sites]
+        self._fold = (pairs, [(t, t._version) for t in self._fold_sources(sites)])
+        return self
+
+    def unfold(self):
+        """Drop the fold: the trunk runs by its modules and keywords again.  Returns self."""
+        self._fold = None
+        return self
+
+    def _fold_pairs(self):
+        """The 20 (w', b') of the fold, or RuntimeError when a tensor it was made from has changed since (another tensor,
+        another version, another device): host integers only, no synchronisation."""
+        pairs, seen = self._fold
+        now = self._fold_sources(self._fold_sites())
+        if len(now) != len(seen) or any(t is not u or t._version != v or t.device != pairs[0][0].device for t, (u, v) in zip(now, seen)):
+            raise RuntimeError('ResNet18: the fold is stale (a parameter or running statistic changed after fold(), e.g. by '
+                               'load_state_dict, an optimiser step or a move to another device): call fold() again')
+        return pairs
+
+    def _folded_maps(self, x):
+        """The four residual stages' outputs on the folded path."""
+        pairs = iter(self._fold_pairs())
+        out = self.maxpool(_fold_act(x, self.conv1, next(pairs)))
+        maps = []
+        for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
+            for block in layer:
+                mid = _fold_act(out, block.conv1, next(pairs))
+                identity = out if block.downsample is None else _fold_act(out, block.downsample[0], next(pairs), relu=False)
+                out = _fold_act(mid, block.conv2, next(pairs), residual=identity)
+            maps.append(out)
+        return maps
+
     def forward(self, x):
+        if _use_fold(self):
+            return self.fc(torch.flatten(self.avgpool(self._folded_maps(x)[3]), 1))
         x = self.layer3(self.layer2(self.layer1(self._stem(x))))
         if self.fused_tail:
             return self.fc(self._layer4_tail(x)[1])
@@ -261,7 +365,10 @@ class ResNet18(nn.Module):
 
 
 def _trunk_maps(model, imgs):
-    """conv1 .. layer4 of a trunk (extract_feature of the three models): the four residual stages' outputs."""
+    """conv1 .. layer4 of a trunk (extract_feature of the three models): the four residual stages' outputs.  A folded
+    trunk in eval mode with grad mode off (ResNet18.fold) forms them on csrc/trunkfold.hip."""
+    if _use_fold(model):
+        return model._folded_maps(imgs)
     stem = model._conv1(imgs) if getattr(model, 'hip_conv_strided', False) else model.conv1(imgs)
     if hasattr(model, '_stem_tail'):                      # ResNet18: by the form its keywords chose
         out = model._stem_tail(stem)
@@ -279,7 +386,7 @@ def _trunk_features(model, imgs, pool=None):
     fused_tail forms feats in layer4's last site: no pool is called, and one that is not the global average is refused
     before anything runs.  For any other trunk feats is pool(maps[3]), flattened."""
     pool = model.avgpool if pool is None else pool
-    if not getattr(model, 'fused_tail', False):
+    if _use_fold(model) or not getattr(model, 'fused_tail', False):      # the folded path ends in the owner's pool too
         maps = _trunk_maps(model, imgs)
         out = pool(maps[3])
         return maps, out.view(out.size(0), -1)

@@ -2571,8 +2571,9 @@ def _conv_check_gpu(name, x, weight):
             raise ValueError('%s runs on the GPU only (%s is a %s tensor); there is no CPU path' % (name, which, t.device.type))
 
 
-def _conv2d_check(x, weight, stride, padding):
-    """Everything Conv2dFunction refuses: the shared checks, then what only a general convolution can get wrong."""
+def _conv2d_check_args(x, weight, stride, padding):
+    """What Conv2dFunction refuses wherever its tensors live: the shared checks, then what only a general convolution can
+    get wrong."""
     _conv_check('conv2d', x, weight, 'R, R', lambda k: k[0] == k[1])
     R = weight.shape[2]
     if R not in CONV2D_KERNELS:
@@ -2584,6 +2585,11 @@ def _conv2d_check(x, weight, stride, padding):
     if x.shape[2] + 2 * padding < R or x.shape[3] + 2 * padding < R:
         raise ValueError('conv2d: the padded image (%d + 2 x %d) x (%d + 2 x %d) is smaller than the %d x %d kernel' %
                          (x.shape[2], padding, x.shape[3], padding, R, R))
+
+
+def _conv2d_check(x, weight, stride, padding):
+    """Everything Conv2dFunction refuses."""
+    _conv2d_check_args(x, weight, stride, padding)
     _conv_check_gpu('conv2d', x, weight)
 
 
@@ -2655,3 +2661,46 @@ class Conv2dFunction(Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_y):
         return _conv_backward(ctx, 'conv2d', grad_y) + (None, None)
+
+
+# ---- the trunk's convolutions for eval-mode inference (csrc/trunkfold.hip): nn.Conv2d + nn.BatchNorm2d (eval)
+# + add + ReLU reached through vpnet_one_resnet.py:45-57 as one op, the norm folded into the weights and a bias beforehand
+
+def conv2d_bias_act(x, weight, bias=None, residual=None, stride=1, padding=0, relu=True):
+    """relu?(conv2d(x, weight, stride, padding) + bias[c_out]? + residual?) on csrc/trunkfold.hip: Conv2dFunction's product
+    (a square kernel of 1, 3 or 7, exact fp32 products, one summation order) with the bias, the residual add and the ReLU in
+    its epilogue, in that order.  x (B, C_in, H, W), weight (C_out, C_in, R, R), bias (C_out,) or None, residual of the
+    result's shape or None, all fp32 on one GPU; strided and channels-last inputs are made NCHW-contiguous first.  Inference
+    only: it has no backward, and refuses an argument that requires grad while grad mode is on.  With bias=None,
+    residual=None, relu=False it equals Conv2dFunction's forward bit for bit."""
+    tensors = [('x', x), ('weight', weight), ('bias', bias), ('residual', residual)]
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for _n, t in tensors):
+        raise RuntimeError('conv2d_bias_act is inference only (no backward): run it under torch.no_grad(), or use conv2d + '
+                           'batch_norm_act, the differentiable form')
+    _conv2d_check_args(x, weight, stride, padding)
+    Co, R = weight.shape[0], weight.shape[2]
+    if bias is not None:
+        if bias.dtype != torch.float32:
+            raise NotImplementedError('conv2d_bias_act: fp32 only (bias is %s)' % (bias.dtype,))
+        if tuple(bias.shape) != (Co,):
+            raise ValueError('conv2d_bias_act: bias must be (C_out,) = (%d,), got %s' % (Co, tuple(bias.shape)))
+    if residual is not None and residual.dtype != torch.float32:
+        raise NotImplementedError('conv2d_bias_act: fp32 only (residual is %s)' % (residual.dtype,))
+    if not isinstance(relu, (bool, int)) or relu not in (0, 1):
+        raise ValueError('conv2d_bias_act: relu must be True or False, got %r' % (relu,))
+    out_shape = (x.shape[0], Co) + conv2d_out_size(x.shape[2], x.shape[3], R, stride, padding)
+    if residual is not None and tuple(residual.shape) != out_shape:
+        raise ValueError('conv2d_bias_act: residual must have the shape of the result %s, got %s' % (out_shape, tuple(residual.shape)))
+    for which, t in tensors[1:]:
+        if t is not None and t.device != x.device:
+            raise ValueError('conv2d_bias_act: %s is on %s, x is on %s' % (which, t.device, x.device))
+    _conv_check_gpu('conv2d_bias_act', x, weight)
+    x, weight = x.contiguous(), weight.contiguous()
+    bias = None if bias is None else bias.contiguous()
+    residual = None if residual is None else residual.contiguous()
+    B, Ci, H, W = x.shape
+    dims = (B, Ci, Co, H, W, R, stride, padding)
+    y = torch.empty(out_shape, dtype=torch.float32, device=x.device)
+    ws, nbytes = _conv2d_ws(dims, CONV_FWD, x.device)
+    _lib.call('vpn_conv2d_bias_act_fwd', x, weight, bias, residual, y, *dims, int(relu), ws, nbytes, _lib.stream())
+    return y
