@@ -20,7 +20,15 @@
 //     slices lane-strided, then the butterfly): bit-equal from run to run; no float atomics, no host synchronisation, nothing allocated;
 //   * save_mean / save_invstd, the running statistics and the int64 batch counter are written by ONE work-item per channel
 //     of the launch that knows the statistics.
+// The three forms share their pieces.  Forward: tn_slab_stats / tn_stats_kernel, the apply kernels' statistics prelude
+// (tn_apply_stats), the activation (tn_act) and the norm + residual + ReLU of a unit (tn_unit); what a form does with a unit
+// afterwards (store, pool window, row mean) is its own kernel: tn_fwd_*, tp_fwd_*, tt_fwd_*.  Backward: ONE set of kernels,
+// bwd_onepass_kernel / bwd_partial_kernel / bwd_apply_kernel, over a gradient source (ActGrad, TailGrad, PoolGrad) that
+// says how a unit's upstream gradient and xhat are loaded and whether the form has a d_residual.  Host: tn_fwd_plan and
+// tn_bwd hold the checks and the regime rules of all six entry points, tn_pick the <BLOCK, V> ladders.  The launch
+// labels keep the forms' names: tn_*, tp_*, tt_*.
 #include "vpn_common.h"
+#include <type_traits>
 
 namespace vpn {
 
@@ -101,8 +109,22 @@ __device__ inline void tn_publish(const TnFwd& a, int c, int N, float mean, floa
     if (a.nbt && c == 0) a.nbt[0] += 1;
 }
 
+// the activation of all three forms, its roundings pinned: the product with gamma and the sum with beta are one fma
 __device__ inline float tn_act(float x, float mean, float invstd, float gamma, float beta) {
-    return (x - mean) * invstd * gamma + beta;
+    return __builtin_fmaf((x - mean) * invstd, gamma, beta);
+}
+
+// norm + residual + ReLU of the unit at element e, on its V values r in place
+template <int V>
+__device__ inline void tn_unit(const TnFwd& a, size_t e, Vec<V>& r, float mean, float invstd, float gamma, float beta) {
+    Vec<V> q = {};
+    if (a.res) q = ldv<V>(a.res + e);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        float y = tn_act(r.v[j], mean, invstd, gamma, beta);
+        if (a.res) y += q.v[j];
+        r.v[j] = a.relu ? fmaxf(y, 0.0f) : y;
+    }
 }
 
 // the statistics of a channel whose slab fits LDS (xc: the channel's first element): the slab filled in unit order, then
@@ -156,14 +178,7 @@ __global__ __launch_bounds__(BLOCK) void tn_fwd_onepass_kernel(TnShape s, TnFwd 
     for (int u = tid; u < s.NU; u += BLOCK, k.step(s)) {
         const size_t e = chan + k.at<V>(s);
         Vec<V> r = ldv<V>(slab + (size_t)u * V);
-        Vec<V> q = {};
-        if (a.res) q = ldv<V>(a.res + e);
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-            float y = tn_act(r.v[j], mean, invstd, gamma, beta);
-            if (a.res) y += q.v[j];
-            r.v[j] = a.relu ? fmaxf(y, 0.0f) : y;
-        }
+        tn_unit<V>(a, e, r, mean, invstd, gamma, beta);
         stv<V>(a.y + e, r);
     }
 }
@@ -233,8 +248,20 @@ __device__ inline void tn_merge_stats(const TnShape& s, const float* part, float
     invstd = 1.0f / sqrtf(var + eps);
 }
 
-// ---- forward, split regime launch 2 (a.ws: merge the partials) and the eval forward (a.ws == NULL: running statistics):
-// grid (C, S), every workgroup normalises its slice
+// mean and invstd of channel c in the apply kernels (grid (C, any)).  a.ws: the split regime's launch 2 merges the partials,
+// and the workgroups with blockIdx.y == 0 publish; a.ws == NULL: the eval forward reads the running statistics
+__device__ inline void tn_apply_stats(const TnShape& s, const TnFwd& a, int c, float& mean, float& invstd) {
+    if (a.ws) {
+        float var;
+        tn_merge_stats(s, a.ws + (size_t)c * s.S * 2, a.eps, mean, var, invstd);
+        if (blockIdx.y == 0 && threadIdx.x == 0) tn_publish(a, c, s.N, mean, var, invstd);
+    } else {
+        mean = a.rm[c];
+        invstd = 1.0f / sqrtf(a.rv[c] + a.eps);
+    }
+}
+
+// ---- forward, split regime launch 2 and the eval forward: grid (C, S), every workgroup normalises its slice
 template <int V>
 __global__ __launch_bounds__(TN_BLOCK) void tn_fwd_apply_kernel(TnShape s, TnFwd a) {
     const int c = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
@@ -242,14 +269,7 @@ __global__ __launch_bounds__(TN_BLOCK) void tn_fwd_apply_kernel(TnShape s, TnFwd
     const int u0 = sl * SU, u1 = u0 + SU < s.NU ? u0 + SU : s.NU;
     if (sl >= s.S || u0 >= s.NU) return;
     float mean, invstd;
-    if (a.ws) {
-        float var;
-        tn_merge_stats(s, a.ws + (size_t)c * s.S * 2, a.eps, mean, var, invstd);
-        if (sl == 0 && tid == 0) tn_publish(a, c, s.N, mean, var, invstd);
-    } else {
-        mean = a.rm[c];
-        invstd = 1.0f / sqrtf(a.rv[c] + a.eps);
-    }
+    tn_apply_stats(s, a, c, mean, invstd);
     const float gamma = a.w ? a.w[c] : 1.0f, beta = a.b ? a.b[c] : 0.0f;
     const size_t chan = (size_t)c * s.HW;
     TnWalk k(u0 + tid, s.RU);
@@ -257,31 +277,32 @@ __global__ __launch_bounds__(TN_BLOCK) void tn_fwd_apply_kernel(TnShape s, TnFwd
         if (u0 + tid + p * TN_BLOCK >= u1) break;
         const size_t e = chan + k.at<V>(s);
         Vec<V> r = ldv<V>(a.x + e);
-        Vec<V> q = {};
-        if (a.res) q = ldv<V>(a.res + e);
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-            float y = tn_act(r.v[j], mean, invstd, gamma, beta);
-            if (a.res) y += q.v[j];
-            r.v[j] = a.relu ? fmaxf(y, 0.0f) : y;
-        }
+        tn_unit<V>(a, e, r, mean, invstd, gamma, beta);
         stv<V>(a.y + e, r);
     }
 }
 
-// g = dy [y > 0] (the mask from the saved output, ATen's threshold backward) and xhat of V elements
-template <int V>
-__device__ inline void tn_bwd_load(const TnBwd& a, size_t e, float mean, float invstd, Vec<V>& g, Vec<V>& xh) {
-    g = ldv<V>(a.dy + e);
-    xh = ldv<V>(a.x + e);
-    if (a.y) {
-        const Vec<V> y = ldv<V>(a.y + e);
+// ---- backward.  A gradient source says what differs between the forms: load<V>() gives g, the upstream gradient of y
+// before the norm, and xhat of the V elements of unit k of channel c, at element e; dres: the form has a d_residual (= g);
+// onepass: the form has a one-pass regime.  It travels to the kernels by value next to TnShape / TnBwd.
+
+// the ring: g = dy [y > 0] (the mask from the saved output, ATen's threshold backward)
+struct ActGrad {
+    static constexpr bool dres = true, onepass = true;
+    template <int V>
+    __device__ inline void load(const TnShape& s, const TnBwd& a, int c, const TnWalk& k, size_t e, float mean, float invstd,
+                                Vec<V>& g, Vec<V>& xh) const {
+        g = ldv<V>(a.dy + e);
+        xh = ldv<V>(a.x + e);
+        if (a.y) {
+            const Vec<V> y = ldv<V>(a.y + e);
 #pragma unroll
-        for (int j = 0; j < V; ++j) g.v[j] = y.v[j] <= 0.0f ? 0.0f : g.v[j];
+            for (int j = 0; j < V; ++j) g.v[j] = y.v[j] <= 0.0f ? 0.0f : g.v[j];
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j) xh.v[j] = (xh.v[j] - mean) * invstd;
     }
-#pragma unroll
-    for (int j = 0; j < V; ++j) xh.v[j] = (xh.v[j] - mean) * invstd;
-}
+};
 
 __device__ inline void tn_bwd_stats(const TnBwd& a, int c, float& mean, float& invstd) {
     mean = a.stat_a[c];
@@ -289,8 +310,8 @@ __device__ inline void tn_bwd_stats(const TnBwd& a, int c, float& mean, float& i
 }
 
 // ---- backward, one-pass regime: grid C; g and xhat of the channel stay in LDS between the two sums and dx
-template <int BLOCK, int V>
-__global__ __launch_bounds__(BLOCK) void tn_bwd_onepass_kernel(TnShape s, TnBwd a) {
+template <class SRC, int BLOCK, int V>
+__global__ __launch_bounds__(BLOCK) void bwd_onepass_kernel(TnShape s, TnBwd a, SRC src) {
     constexpr int SLAB = BLOCK == 64 ? TN_SMALL : TN_MAX;
     __shared__ __attribute__((aligned(16))) float gs[SLAB];
     __shared__ __attribute__((aligned(16))) float xs[SLAB];
@@ -306,10 +327,10 @@ __global__ __launch_bounds__(BLOCK) void tn_bwd_onepass_kernel(TnShape s, TnBwd 
         for (int u = tid; u < s.NU; u += BLOCK, k.step(s)) {
             const size_t e = chan + k.at<V>(s);
             Vec<V> g, xh;
-            tn_bwd_load<V>(a, e, mean, invstd, g, xh);
+            src.template load<V>(s, a, c, k, e, mean, invstd, g, xh);
             stv<V>(gs + (size_t)u * V, g);
             stv<V>(xs + (size_t)u * V, xh);
-            if (a.dres) stv<V>(a.dres + e, g);
+            if constexpr (SRC::dres) { if (a.dres) stv<V>(a.dres + e, g); }
 #pragma unroll
             for (int j = 0; j < V; ++j) { sg += g.v[j]; sgx += g.v[j] * xh.v[j]; }
         }
@@ -333,8 +354,8 @@ __global__ __launch_bounds__(BLOCK) void tn_bwd_onepass_kernel(TnShape s, TnBwd 
 }
 
 // ---- backward, split regime launch 1: grid (C, S); the two sums of a slice, and d_residual = g
-template <int V>
-__global__ __launch_bounds__(TN_BLOCK) void tn_bwd_partial_kernel(TnShape s, TnBwd a) {
+template <class SRC, int V>
+__global__ __launch_bounds__(TN_BLOCK) void bwd_partial_kernel(TnShape s, TnBwd a, SRC src) {
     __shared__ float red[2 * (TN_BLOCK / 64)];
     const int c = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
     constexpr int SU = TN_SLICE / V, PER = TN_PER / V;
@@ -349,8 +370,8 @@ __global__ __launch_bounds__(TN_BLOCK) void tn_bwd_partial_kernel(TnShape s, TnB
         if (u0 + tid + p * TN_BLOCK >= u1) break;
         const size_t e = chan + k.at<V>(s);
         Vec<V> g, xh;
-        tn_bwd_load<V>(a, e, mean, invstd, g, xh);
-        if (a.dres) stv<V>(a.dres + e, g);
+        src.template load<V>(s, a, c, k, e, mean, invstd, g, xh);
+        if constexpr (SRC::dres) { if (a.dres) stv<V>(a.dres + e, g); }
 #pragma unroll
         for (int j = 0; j < V; ++j) { sg += g.v[j]; sgx += g.v[j] * xh.v[j]; }
     }
@@ -379,8 +400,8 @@ __device__ inline void tn_merge_sums(const TnShape& s, const float* part, float&
 
 // ---- backward, split regime launch 2, and the eval backward without affine gradients (a.sums == 0): grid (C, S), or
 // (C, 1) when only the affine gradients are wanted (a.dx == NULL)
-template <int V>
-__global__ __launch_bounds__(TN_BLOCK) void tn_bwd_apply_kernel(TnShape s, TnBwd a) {
+template <class SRC, int V>
+__global__ __launch_bounds__(TN_BLOCK) void bwd_apply_kernel(TnShape s, TnBwd a, SRC src) {
     const int c = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
     constexpr int SU = TN_SLICE / V, PER = TN_PER / V;
     const int u0 = sl * SU, u1 = u0 + SU < s.NU ? u0 + SU : s.NU;
@@ -404,7 +425,7 @@ __global__ __launch_bounds__(TN_BLOCK) void tn_bwd_apply_kernel(TnShape s, TnBwd
         if (u0 + tid + p * TN_BLOCK >= u1) break;
         const size_t e = chan + k.at<V>(s);
         Vec<V> g, xh;
-        tn_bwd_load<V>(a, e, mean, invstd, g, xh);
+        src.template load<V>(s, a, c, k, e, mean, invstd, g, xh);
 #pragma unroll
         for (int j = 0; j < V; ++j) g.v[j] = kk * (g.v[j] - mg - xh.v[j] * mgx);
         stv<V>(a.dx + e, g);
@@ -421,9 +442,9 @@ static_assert(TP_SLICE % (2 * TN_BLOCK) == 0, "a workgroup takes whole pairs of 
 // NP = B PH PW pooled outputs per channel, in SP slices of TP_SLICE
 struct TpShape { int H, W, PH, PW, NP, SP; };
 
-// y of tn_fwd_apply_kernel with its roundings pinned: the product with gamma and the sum with beta contracted
+// the stem's activation: the ReLU is always on
 __device__ inline float tp_act(float x, float mean, float invstd, float gamma, float beta) {
-    return fmaxf(__builtin_fmaf((x - mean) * invstd, gamma, beta), 0.0f);
+    return fmaxf(tn_act(x, mean, invstd, gamma, beta), 0.0f);
 }
 
 // ATen's rule: a tap replaces the best so far only if it is greater or is NaN, so the first maximum wins
@@ -481,14 +502,7 @@ __global__ __launch_bounds__(TN_BLOCK) void tp_fwd_kernel(TnShape s, TpShape g, 
     const int o0 = sl * TP_SLICE, o1 = o0 + TP_SLICE < g.NP ? o0 + TP_SLICE : g.NP;
     if (sl >= g.SP || o0 >= g.NP) return;
     float mean, invstd;
-    if (a.ws) {
-        float var;
-        tn_merge_stats(s, a.ws + (size_t)c * s.S * 2, a.eps, mean, var, invstd);
-        if (sl == 0 && tid == 0) tn_publish(a, c, s.N, mean, var, invstd);
-    } else {
-        mean = a.rm[c];
-        invstd = 1.0f / sqrtf(a.rv[c] + a.eps);
-    }
+    tn_apply_stats(s, a, c, mean, invstd);
     const float gamma = a.w ? a.w[c] : 1.0f, beta = a.b ? a.b[c] : 0.0f;
     const int PHW = g.PH * g.PW;
     for (int o = o0 + tid * OUT; o < o1; o += TN_BLOCK * OUT) {
@@ -537,77 +551,25 @@ __device__ inline float tp_g(const TnBwd& a, const unsigned char* idx, const TpS
     return sum;
 }
 
-// g and xhat of the V elements of unit k of channel c (V = 4: W is a multiple of 4, the four share a row)
-template <int V>
-__device__ inline void tp_bwd_load(const TnShape& s, const TpShape& g, const TnBwd& a, const unsigned char* idx, int c,
-                                   const TnWalk& k, float mean, float invstd, Vec<V>& gr, Vec<V>& xh) {
-    const int i = k.i * V, h = i / g.W, w = i - h * g.W;
-    const size_t pc = ((size_t)k.b * s.C + c) * g.PH * g.PW;
-    xh = ldv<V>(a.x + (size_t)c * s.HW + k.at<V>(s));
+// the pool's gradient source: the input map is walked in slices at any N (no one-pass regime), a.dy is dp and a.y is p.
+// V = 4: W is a multiple of 4, the four elements share a row
+struct PoolGrad {
+    static constexpr bool dres = false, onepass = false;
+    TpShape g;
+    const unsigned char* idx;
+    template <int V>
+    __device__ inline void load(const TnShape& s, const TnBwd& a, int c, const TnWalk& k, size_t e, float mean, float invstd,
+                                Vec<V>& gr, Vec<V>& xh) const {
+        const int i = k.i * V, h = i / g.W, w = i - h * g.W;
+        const size_t pc = ((size_t)k.b * s.C + c) * g.PH * g.PW;
+        xh = ldv<V>(a.x + e);
 #pragma unroll
-    for (int j = 0; j < V; ++j) {
-        gr.v[j] = tp_g(a, idx, g, pc, h, w + j);
-        xh.v[j] = (xh.v[j] - mean) * invstd;
-    }
-}
-
-// ---- backward launch 1: grid (C, S); the two sums of a slice of the input map
-template <int V>
-__global__ __launch_bounds__(TN_BLOCK) void tp_bwd_partial_kernel(TnShape s, TpShape g, TnBwd a, const unsigned char* idx) {
-    __shared__ float red[2 * (TN_BLOCK / 64)];
-    const int c = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
-    constexpr int SU = TN_SLICE / V, PER = TN_PER / V;
-    const int u0 = sl * SU, u1 = u0 + SU < s.NU ? u0 + SU : s.NU;
-    if (sl >= s.S || u0 >= s.NU) return;
-    float mean, invstd;
-    tn_bwd_stats(a, c, mean, invstd);
-    float sg = 0.0f, sgx = 0.0f;
-    TnWalk k(u0 + tid, s.RU);
-    for (int p = 0; p < PER; ++p, k.step(s)) {
-        if (u0 + tid + p * TN_BLOCK >= u1) break;
-        Vec<V> gr, xh;
-        tp_bwd_load<V>(s, g, a, idx, c, k, mean, invstd, gr, xh);
-#pragma unroll
-        for (int j = 0; j < V; ++j) { sg += gr.v[j]; sgx += gr.v[j] * xh.v[j]; }
-    }
-    block_sum2<TN_BLOCK>(sg, sgx, red);
-    if (tid == 0) {
-        a.ws[((size_t)c * s.S + sl) * 2] = sg;
-        a.ws[((size_t)c * s.S + sl) * 2 + 1] = sgx;
-    }
-}
-
-// ---- backward launch 2, and the eval backward without affine gradients (a.sums == 0): grid (C, S), or (C, 1) when only
-// the affine gradients are wanted (a.dx == NULL); the merge of tn_bwd_apply_kernel
-template <int V>
-__global__ __launch_bounds__(TN_BLOCK) void tp_bwd_apply_kernel(TnShape s, TpShape g, TnBwd a, const unsigned char* idx) {
-    const int c = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
-    constexpr int SU = TN_SLICE / V, PER = TN_PER / V;
-    const int u0 = sl * SU, u1 = u0 + SU < s.NU ? u0 + SU : s.NU;
-    if (sl >= s.S || u0 >= s.NU) return;
-    float sg = 0.0f, sgx = 0.0f;
-    if (a.sums) {
-        tn_merge_sums(s, a.ws + (size_t)c * s.S * 2, sg, sgx);
-        if (sl == 0 && tid == 0) {
-            if (a.db) a.db[c] = sg;
-            if (a.dw) a.dw[c] = sgx;
+        for (int j = 0; j < V; ++j) {
+            gr.v[j] = tp_g(a, idx, g, pc, h, w + j);
+            xh.v[j] = (xh.v[j] - mean) * invstd;
         }
     }
-    if (!a.dx) return;
-    float mean, invstd;
-    tn_bwd_stats(a, c, mean, invstd);
-    const float kk = (a.w ? a.w[c] : 1.0f) * invstd;
-    const float mg = a.eval ? 0.0f : sg / (float)s.N, mgx = a.eval ? 0.0f : sgx / (float)s.N;
-    TnWalk k(u0 + tid, s.RU);
-    for (int p = 0; p < PER; ++p, k.step(s)) {
-        if (u0 + tid + p * TN_BLOCK >= u1) break;
-        Vec<V> gr, xh;
-        tp_bwd_load<V>(s, g, a, idx, c, k, mean, invstd, gr, xh);
-#pragma unroll
-        for (int j = 0; j < V; ++j) gr.v[j] = kk * (gr.v[j] - mg - xh.v[j] * mgx);
-        stv<V>(a.dx + (size_t)c * s.HW + k.at<V>(s), gr);
-    }
-}
+};
 
 // ---- the trunk's tail: the last norm site also writes m[b,c] = (sum_hw y[b,c,hw]) / HW, the global
 // average pool the heads read, and its backward takes m's gradient: upstream = dy + dm[b,c] / HW.  A row is the HW elements
@@ -615,11 +577,6 @@ __global__ __launch_bounds__(TN_BLOCK) void tp_bwd_apply_kernel(TnShape s, TpSha
 // two >= min(HW, 64)) owns a row, lane j of the group adds the elements j, j + G, ... in order, then the group's butterfly.
 // B: batch rows; RPB: rows a workgroup of tt_fwd_apply_kernel owns.
 struct TtRows { int B, RPB, LG; };
-
-// y with the roundings of tn_fwd_onepass_kernel / tn_fwd_apply_kernel pinned (tp_act says which), before the ReLU
-__device__ inline float tt_act(float x, float mean, float invstd, float gamma, float beta) {
-    return __builtin_fmaf((x - mean) * invstd, gamma, beta);
-}
 
 // the means of `rows` rows of HW floats that lie one after another in LDS; row r goes to m[r * stride]
 template <int BLOCK>
@@ -654,14 +611,7 @@ __global__ __launch_bounds__(BLOCK) void tt_fwd_onepass_kernel(TnShape s, TtRows
     for (int u = tid; u < s.NU; u += BLOCK, k.step(s)) {
         const size_t e = chan + k.at<V>(s);
         Vec<V> r = ldv<V>(slab + (size_t)u * V);
-        Vec<V> q = {};
-        if (a.res) q = ldv<V>(a.res + e);
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-            float y = tt_act(r.v[j], mean, invstd, gamma, beta);
-            if (a.res) y += q.v[j];
-            r.v[j] = a.relu ? fmaxf(y, 0.0f) : y;
-        }
+        tn_unit<V>(a, e, r, mean, invstd, gamma, beta);
         stv<V>(a.y + e, r);
         stv<V>(slab + (size_t)u * V, r);
     }
@@ -669,8 +619,7 @@ __global__ __launch_bounds__(BLOCK) void tt_fwd_onepass_kernel(TnShape s, TtRows
     tt_row_means<BLOCK>(slab, t.B, s.HW, t.LG, m + c, (size_t)s.C);
 }
 
-// ---- forward, split regime launch 2 (a.ws: merge the partials of tn_stats_kernel) and the eval forward (a.ws == NULL):
-// grid (C, ceil(B / RPB)), a workgroup owns the batch rows blockIdx.y * RPB ... of its channel.  HW <= TN_SLICE: RPB =
+// ---- forward, split regime launch 2 and the eval forward: grid (C, ceil(B / RPB)), a workgroup owns the batch rows blockIdx.y * RPB ... of its channel.  HW <= TN_SLICE: RPB =
 // TN_SLICE / HW rows, y staged in LDS and summed as above.  Longer rows: RPB = 1, a work-item adds its elements in unit
 // order, then the workgroup's sum (block_sum2).
 template <int V>
@@ -683,14 +632,7 @@ __global__ __launch_bounds__(TN_BLOCK) void tt_fwd_apply_kernel(TnShape s, TtRow
     const bool staged = s.HW <= TN_SLICE;
     if (staged && (b1 - b0) * s.HW > TN_SLICE) return;          // the host never asks: nothing outside the slab either way
     float mean, invstd;
-    if (a.ws) {
-        float var;
-        tn_merge_stats(s, a.ws + (size_t)c * s.S * 2, a.eps, mean, var, invstd);
-        if (blockIdx.y == 0 && tid == 0) tn_publish(a, c, s.N, mean, var, invstd);
-    } else {
-        mean = a.rm[c];
-        invstd = 1.0f / sqrtf(a.rv[c] + a.eps);
-    }
+    tn_apply_stats(s, a, c, mean, invstd);
     const float gamma = a.w ? a.w[c] : 1.0f, beta = a.b ? a.b[c] : 0.0f;
     const size_t chan = (size_t)c * s.HW;
     const int u0 = b0 * s.RU, u1 = b1 * s.RU;
@@ -699,14 +641,7 @@ __global__ __launch_bounds__(TN_BLOCK) void tt_fwd_apply_kernel(TnShape s, TtRow
     for (int u = u0 + tid; u < u1; u += TN_BLOCK, k.step(s)) {
         const size_t e = chan + k.at<V>(s);
         Vec<V> r = ldv<V>(a.x + e);
-        Vec<V> q = {};
-        if (a.res) q = ldv<V>(a.res + e);
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-            float y = tt_act(r.v[j], mean, invstd, gamma, beta);
-            if (a.res) y += q.v[j];
-            r.v[j] = a.relu ? fmaxf(y, 0.0f) : y;
-        }
+        tn_unit<V>(a, e, r, mean, invstd, gamma, beta);
         stv<V>(a.y + e, r);
         if (staged) {
             stv<V>(slab + (size_t)(u - u0) * V, r);
@@ -726,134 +661,31 @@ __global__ __launch_bounds__(TN_BLOCK) void tt_fwd_apply_kernel(TnShape s, TtRow
     }
 }
 
-// g and xhat of the V elements of unit k of channel c, at element e: tn_bwd_load with the upstream gradient dy + dm[b,c] / HW
-// (a.dy or dm may be NULL: the other one alone)
-template <int V>
-__device__ inline void tt_bwd_load(const TnShape& s, const TnBwd& a, const float* dm, int c, const TnWalk& k, size_t e, float mean,
-                                   float invstd, Vec<V>& g, Vec<V>& xh) {
-    g = Vec<V>{};
-    if (a.dy) g = ldv<V>(a.dy + e);
-    if (dm) {
-        const float q = dm[(size_t)k.b * s.C + c] / (float)s.HW;
+// the tail's gradient source: ActGrad on the upstream gradient dy + dm[b,c] / HW (a.dy or dm may be NULL: the other one
+// alone)
+struct TailGrad {
+    static constexpr bool dres = true, onepass = true;
+    const float* dm;
+    template <int V>
+    __device__ inline void load(const TnShape& s, const TnBwd& a, int c, const TnWalk& k, size_t e, float mean, float invstd,
+                                Vec<V>& g, Vec<V>& xh) const {
+        g = Vec<V>{};
+        if (a.dy) g = ldv<V>(a.dy + e);
+        if (dm) {
+            const float q = dm[(size_t)k.b * s.C + c] / (float)s.HW;
 #pragma unroll
-        for (int j = 0; j < V; ++j) g.v[j] = a.dy ? g.v[j] + q : q;
-    }
-    xh = ldv<V>(a.x + e);
-    if (a.y) {
-        const Vec<V> y = ldv<V>(a.y + e);
-#pragma unroll
-        for (int j = 0; j < V; ++j) g.v[j] = y.v[j] <= 0.0f ? 0.0f : g.v[j];
-    }
-#pragma unroll
-    for (int j = 0; j < V; ++j) xh.v[j] = (xh.v[j] - mean) * invstd;
-}
-
-// ---- backward, one-pass regime: tn_bwd_onepass_kernel on the upstream gradient of tt_bwd_load
-template <int BLOCK, int V>
-__global__ __launch_bounds__(BLOCK) void tt_bwd_onepass_kernel(TnShape s, TnBwd a, const float* dm) {
-    constexpr int SLAB = BLOCK == 64 ? TN_SMALL : TN_MAX;
-    __shared__ __attribute__((aligned(16))) float gs[SLAB];
-    __shared__ __attribute__((aligned(16))) float xs[SLAB];
-    __shared__ float red[2 * (TN_BLOCK / 64)];
-    const int c = blockIdx.x, tid = threadIdx.x;
-    if (s.N > SLAB) return;
-    float mean, invstd;
-    tn_bwd_stats(a, c, mean, invstd);
-    const size_t chan = (size_t)c * s.HW;
-    float sg = 0.0f, sgx = 0.0f;
-    {
-        TnWalk k(tid, s.RU);
-        for (int u = tid; u < s.NU; u += BLOCK, k.step(s)) {
-            const size_t e = chan + k.at<V>(s);
-            Vec<V> g, xh;
-            tt_bwd_load<V>(s, a, dm, c, k, e, mean, invstd, g, xh);
-            stv<V>(gs + (size_t)u * V, g);
-            stv<V>(xs + (size_t)u * V, xh);
-            if (a.dres) stv<V>(a.dres + e, g);
-#pragma unroll
-            for (int j = 0; j < V; ++j) { sg += g.v[j]; sgx += g.v[j] * xh.v[j]; }
+            for (int j = 0; j < V; ++j) g.v[j] = a.dy ? g.v[j] + q : q;
         }
-    }
-    block_sum2<BLOCK>(sg, sgx, red);
-    if (tid == 0) {
-        if (a.db) a.db[c] = sg;
-        if (a.dw) a.dw[c] = sgx;
-    }
-    if (!a.dx) return;
-    const float kk = (a.w ? a.w[c] : 1.0f) * invstd;
-    const float mg = a.eval ? 0.0f : sg / (float)s.N, mgx = a.eval ? 0.0f : sgx / (float)s.N;
-    TnWalk k(tid, s.RU);
-    for (int u = tid; u < s.NU; u += BLOCK, k.step(s)) {
-        Vec<V> g = ldv<V>(gs + (size_t)u * V);
-        const Vec<V> xh = ldv<V>(xs + (size_t)u * V);
+        xh = ldv<V>(a.x + e);
+        if (a.y) {
+            const Vec<V> y = ldv<V>(a.y + e);
 #pragma unroll
-        for (int j = 0; j < V; ++j) g.v[j] = kk * (g.v[j] - mg - xh.v[j] * mgx);
-        stv<V>(a.dx + chan + k.at<V>(s), g);
-    }
-}
-
-// ---- backward, split regime launch 1: tn_bwd_partial_kernel on the upstream gradient of tt_bwd_load
-template <int V>
-__global__ __launch_bounds__(TN_BLOCK) void tt_bwd_partial_kernel(TnShape s, TnBwd a, const float* dm) {
-    __shared__ float red[2 * (TN_BLOCK / 64)];
-    const int c = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
-    constexpr int SU = TN_SLICE / V, PER = TN_PER / V;
-    const int u0 = sl * SU, u1 = u0 + SU < s.NU ? u0 + SU : s.NU;
-    if (sl >= s.S || u0 >= s.NU) return;
-    float mean, invstd;
-    tn_bwd_stats(a, c, mean, invstd);
-    const size_t chan = (size_t)c * s.HW;
-    float sg = 0.0f, sgx = 0.0f;
-    TnWalk k(u0 + tid, s.RU);
-    for (int p = 0; p < PER; ++p, k.step(s)) {
-        if (u0 + tid + p * TN_BLOCK >= u1) break;
-        const size_t e = chan + k.at<V>(s);
-        Vec<V> g, xh;
-        tt_bwd_load<V>(s, a, dm, c, k, e, mean, invstd, g, xh);
-        if (a.dres) stv<V>(a.dres + e, g);
-#pragma unroll
-        for (int j = 0; j < V; ++j) { sg += g.v[j]; sgx += g.v[j] * xh.v[j]; }
-    }
-    block_sum2<TN_BLOCK>(sg, sgx, red);
-    if (tid == 0) {
-        a.ws[((size_t)c * s.S + sl) * 2] = sg;
-        a.ws[((size_t)c * s.S + sl) * 2 + 1] = sgx;
-    }
-}
-
-// ---- backward, split regime launch 2, and the eval backward without affine gradients (a.sums == 0): tn_bwd_apply_kernel
-// on the upstream gradient of tt_bwd_load
-template <int V>
-__global__ __launch_bounds__(TN_BLOCK) void tt_bwd_apply_kernel(TnShape s, TnBwd a, const float* dm) {
-    const int c = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
-    constexpr int SU = TN_SLICE / V, PER = TN_PER / V;
-    const int u0 = sl * SU, u1 = u0 + SU < s.NU ? u0 + SU : s.NU;
-    if (sl >= s.S || u0 >= s.NU) return;
-    float sg = 0.0f, sgx = 0.0f;
-    if (a.sums) {
-        tn_merge_sums(s, a.ws + (size_t)c * s.S * 2, sg, sgx);
-        if (sl == 0 && tid == 0) {
-            if (a.db) a.db[c] = sg;
-            if (a.dw) a.dw[c] = sgx;
+            for (int j = 0; j < V; ++j) g.v[j] = y.v[j] <= 0.0f ? 0.0f : g.v[j];
         }
-    }
-    if (!a.dx) return;
-    float mean, invstd;
-    tn_bwd_stats(a, c, mean, invstd);
-    const float kk = (a.w ? a.w[c] : 1.0f) * invstd;
-    const float mg = a.eval ? 0.0f : sg / (float)s.N, mgx = a.eval ? 0.0f : sgx / (float)s.N;
-    const size_t chan = (size_t)c * s.HW;
-    TnWalk k(u0 + tid, s.RU);
-    for (int p = 0; p < PER; ++p, k.step(s)) {
-        if (u0 + tid + p * TN_BLOCK >= u1) break;
-        const size_t e = chan + k.at<V>(s);
-        Vec<V> g, xh;
-        tt_bwd_load<V>(s, a, dm, c, k, e, mean, invstd, g, xh);
 #pragma unroll
-        for (int j = 0; j < V; ++j) g.v[j] = kk * (g.v[j] - mg - xh.v[j] * mgx);
-        stv<V>(a.dx + e, g);
+        for (int j = 0; j < V; ++j) xh.v[j] = (xh.v[j] - mean) * invstd;
     }
-}
+};
 
 static bool tn_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
@@ -871,107 +703,144 @@ static void tn_units(TnShape* s, int V, int block) {
     s->step_b = block / s->RU; s->step_i = block % s->RU;
 }
 
-}  // namespace vpn
+// the split regime's [C, S, 2] partials, forward and backward
+static size_t tn_workspace_bytes(const TnShape& s) { return (size_t)s.C * s.S * 2 * sizeof(float); }
 
-using namespace vpn;
-
-extern "C" size_t vpn_bn_act_workspace(int B, int C, int H, int W) {
-    TnShape s;
-    if (tn_shape(B, C, H, W, &s) != 0 || s.N <= TN_MAX) return 0;
-    return (size_t)C * s.S * 2 * sizeof(float);
+static bool tn_workspace_ok(const TnShape& s, const void* workspace, size_t bytes) {
+    return workspace && bytes >= tn_workspace_bytes(s) && !((uintptr_t)workspace & 3);
 }
 
-extern "C" int vpn_bn_act_fwd(const float* x, const float* residual, const float* weight, const float* bias, float* running_mean,
-                              float* running_var, long long* num_batches_tracked, int B, int C, int H, int W, int training,
-                              float momentum, float eps, int relu, float* y, float* save_mean, float* save_invstd, void* workspace,
-                              size_t workspace_bytes, void* stream) {
-    TnShape s;
-    const int rc = tn_shape(B, C, H, W, &s);
-    if (rc) return rc;
-    if (!x || !y || !(eps >= 0.0f)) return VPN_E_BADARG;
+// the kernels' template ladders: f(V) with V = 4 (vec) or 1, and f(BLOCK, V) with BLOCK = 64 or TN_BLOCK, as integral
+// constants, so that a launch is written once per kernel
+template <int I> using TnInt = std::integral_constant<int, I>;
+template <class F> static void tn_pick(bool vec, F f) {
+    if (vec) f(TnInt<4>{});
+    else f(TnInt<1>{});
+}
+template <class F> static void tn_pick(int block, bool vec, F f) {
+    if (block == 64) tn_pick(vec, [&](auto V) { f(TnInt<64>{}, V); });
+    else tn_pick(vec, [&](auto V) { f(TnInt<TN_BLOCK>{}, V); });
+}
+
+// what the three forwards check after their shape, and their TnFwd (`out`: y, or the pool's p).  a->ws says whether the
+// regime is the split one.
+static int tn_fwd_plan(const TnShape& s, const float* x, const float* residual, const float* weight, const float* bias,
+                       float* running_mean, float* running_var, long long* num_batches_tracked, int training, float momentum,
+                       float eps, int relu, float* out, float* save_mean, float* save_invstd, void* workspace,
+                       size_t workspace_bytes, TnFwd* a) {
+    if (!x || !out || !(eps >= 0.0f)) return VPN_E_BADARG;
     if (training ? (!save_mean || !save_invstd || s.N < 2 || !(momentum >= 0.0f && momentum <= 1.0f)) : (!running_mean || !running_var))
         return VPN_E_BADARG;
     const bool split = training && s.N > TN_MAX;
-    if (split && (!workspace || workspace_bytes < vpn_bn_act_workspace(B, C, H, W) || ((uintptr_t)workspace & 3))) return VPN_E_BADARG;
-    const bool vec = s.HW % 4 == 0 && tn_aligned16(x) && tn_aligned16(y) && tn_aligned16(residual);
-    hipStream_t st = (hipStream_t)stream;
-    TnFwd a{x, residual, weight, bias, running_mean, running_var, training ? num_batches_tracked : nullptr, y, save_mean,
-            save_invstd, split ? (float*)workspace : nullptr, momentum, eps, relu != 0};
-    if (training && !split) {
-        const int block = s.N <= TN_SMALL ? 64 : TN_BLOCK;
-        tn_units(&s, vec ? 4 : 1, block);
-        const dim3 grid((unsigned)C);
-        if (block == 64) {
-            if (vec) VPN_LAUNCH_AS("tn_fwd_onepass_kernel", (tn_fwd_onepass_kernel<64, 4>), grid, dim3(64), 0, st, s, a);
-            else VPN_LAUNCH_AS("tn_fwd_onepass_kernel", (tn_fwd_onepass_kernel<64, 1>), grid, dim3(64), 0, st, s, a);
-        } else {
-            if (vec) VPN_LAUNCH_AS("tn_fwd_onepass_kernel", (tn_fwd_onepass_kernel<TN_BLOCK, 4>), grid, dim3(TN_BLOCK), 0, st, s, a);
-            else VPN_LAUNCH_AS("tn_fwd_onepass_kernel", (tn_fwd_onepass_kernel<TN_BLOCK, 1>), grid, dim3(TN_BLOCK), 0, st, s, a);
-        }
-        VPN_LAUNCH_CHECK();
-        return 0;
-    }
-    tn_units(&s, vec ? 4 : 1, TN_BLOCK);
-    const dim3 grid((unsigned)C, (unsigned)s.S);
-    if (split) {
-        if (vec) VPN_LAUNCH_AS("tn_stats_kernel", (tn_stats_kernel<4>), grid, dim3(TN_BLOCK), 0, st, s, a);
-        else VPN_LAUNCH_AS("tn_stats_kernel", (tn_stats_kernel<1>), grid, dim3(TN_BLOCK), 0, st, s, a);
-        VPN_LAUNCH_CHECK();
-    }
-    if (vec) VPN_LAUNCH_AS("tn_fwd_apply_kernel", (tn_fwd_apply_kernel<4>), grid, dim3(TN_BLOCK), 0, st, s, a);
-    else VPN_LAUNCH_AS("tn_fwd_apply_kernel", (tn_fwd_apply_kernel<1>), grid, dim3(TN_BLOCK), 0, st, s, a);
+    if (split && !tn_workspace_ok(s, workspace, workspace_bytes)) return VPN_E_BADARG;
+    *a = TnFwd{x, residual, weight, bias, running_mean, running_var, training ? num_batches_tracked : nullptr, out, save_mean,
+               save_invstd, split ? (float*)workspace : nullptr, momentum, eps, relu != 0};
+    return 0;
+}
+
+// the split regime's launch 1 of the three forwards; s in units of vec ? 4 : 1 and workgroups of TN_BLOCK
+static int tn_launch_stats(const TnShape& s, const TnFwd& a, bool vec, hipStream_t st) {
+    const dim3 grid((unsigned)s.C, (unsigned)s.S);
+    tn_pick(vec, [&](auto V) { VPN_LAUNCH_AS("tn_stats_kernel", (tn_stats_kernel<V()>), grid, dim3(TN_BLOCK), 0, st, s, a); });
     VPN_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" int vpn_bn_act_bwd(const float* dy, const float* x, const float* y, const float* weight, const float* stat_mean,
-                              const float* stat_var, int B, int C, int H, int W, int training, float eps, int relu, float* dx,
-                              float* d_residual, float* d_weight, float* d_bias, void* workspace, size_t workspace_bytes,
-                              void* stream) {
-    TnShape s;
-    const int rc = tn_shape(B, C, H, W, &s);
+// vpn_bn_act_fwd (m == NULL) and vpn_bn_tail_fwd (m and its rows t) behind their shape checks
+static int tn_ring_fwd(TnShape s, const TtRows* t, float* m, const float* x, const float* residual, const float* weight,
+                       const float* bias, float* running_mean, float* running_var, long long* num_batches_tracked, int training,
+                       float momentum, float eps, int relu, float* y, float* save_mean, float* save_invstd, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    TnFwd a;
+    const int rc = tn_fwd_plan(s, x, residual, weight, bias, running_mean, running_var, num_batches_tracked, training, momentum, eps,
+                               relu, y, save_mean, save_invstd, workspace, workspace_bytes, &a);
     if (rc) return rc;
-    if (!dy || !x || !stat_mean || !stat_var || (relu && !y) || !(eps >= 0.0f) || (training && s.N < 2)) return VPN_E_BADARG;
-    const bool affine = d_weight || d_bias;
-    if (!dx && !d_residual && !affine) return 0;                     // nothing is wanted
-    const bool sums = training || affine;                            // eval: dx needs no sum
-    const bool split = s.N > TN_MAX;
-    const bool partial = sums || d_residual;                         // split regime: launch 1 forms the sums and writes d_residual
-    if (split && partial && (!workspace || workspace_bytes < vpn_bn_act_workspace(B, C, H, W) || ((uintptr_t)workspace & 3)))
-        return VPN_E_BADARG;
-    const bool vec = s.HW % 4 == 0 && tn_aligned16(dy) && tn_aligned16(x) && tn_aligned16(relu ? y : nullptr) && tn_aligned16(dx) &&
-                     tn_aligned16(d_residual);
+    const bool vec = s.HW % 4 == 0 && tn_aligned16(x) && tn_aligned16(y) && tn_aligned16(residual);
     hipStream_t st = (hipStream_t)stream;
-    TnBwd a{dy, x, relu ? y : nullptr, weight, stat_mean, stat_var, dx, d_residual, d_weight, d_bias,
-            split && partial ? (float*)workspace : nullptr, eps, training ? 0 : 1, split && sums ? 1 : 0};
-    if (!split) {
+    if (training && !a.ws) {
         const int block = s.N <= TN_SMALL ? 64 : TN_BLOCK;
         tn_units(&s, vec ? 4 : 1, block);
-        const dim3 grid((unsigned)C);
-        if (block == 64) {
-            if (vec) VPN_LAUNCH_AS("tn_bwd_onepass_kernel", (tn_bwd_onepass_kernel<64, 4>), grid, dim3(64), 0, st, s, a);
-            else VPN_LAUNCH_AS("tn_bwd_onepass_kernel", (tn_bwd_onepass_kernel<64, 1>), grid, dim3(64), 0, st, s, a);
-        } else {
-            if (vec) VPN_LAUNCH_AS("tn_bwd_onepass_kernel", (tn_bwd_onepass_kernel<TN_BLOCK, 4>), grid, dim3(TN_BLOCK), 0, st, s, a);
-            else VPN_LAUNCH_AS("tn_bwd_onepass_kernel", (tn_bwd_onepass_kernel<TN_BLOCK, 1>), grid, dim3(TN_BLOCK), 0, st, s, a);
-        }
+        const dim3 grid((unsigned)s.C);
+        tn_pick(block, vec, [&](auto BLOCK, auto V) {
+            if (m) VPN_LAUNCH_AS("tt_fwd_onepass_kernel", (tt_fwd_onepass_kernel<BLOCK(), V()>), grid, dim3(BLOCK()), 0, st, s, *t, a, m);
+            else VPN_LAUNCH_AS("tn_fwd_onepass_kernel", (tn_fwd_onepass_kernel<BLOCK(), V()>), grid, dim3(BLOCK()), 0, st, s, a);
+        });
         VPN_LAUNCH_CHECK();
         return 0;
     }
     tn_units(&s, vec ? 4 : 1, TN_BLOCK);
-    const dim3 grid((unsigned)C, (unsigned)s.S);
+    if (a.ws) {
+        const int rs = tn_launch_stats(s, a, vec, st);
+        if (rs) return rs;
+    }
+    tn_pick(vec, [&](auto V) {
+        if (m) {
+            const dim3 grid((unsigned)s.C, (unsigned)((t->B + t->RPB - 1) / t->RPB));
+            VPN_LAUNCH_AS("tt_fwd_apply_kernel", (tt_fwd_apply_kernel<V()>), grid, dim3(TN_BLOCK), 0, st, s, *t, a, m);
+        } else {
+            const dim3 grid((unsigned)s.C, (unsigned)s.S);
+            VPN_LAUNCH_AS("tn_fwd_apply_kernel", (tn_fwd_apply_kernel<V()>), grid, dim3(TN_BLOCK), 0, st, s, a);
+        }
+    });
+    VPN_LAUNCH_CHECK();
+    return 0;
+}
+
+struct TnLabels { const char *onepass, *partial, *apply; };        // the launch labels of a form's backward
+
+// the backward of all three forms behind the form's own pointer checks.  `a` comes with its pointers and eps; ws, eval and
+// sums are set here.  A form without a one-pass regime is in the split regime at any N.
+template <class SRC>
+static int tn_bwd(const TnLabels& L, const SRC& src, TnShape s, TnBwd a, int training, bool vec, void* workspace,
+                  size_t workspace_bytes, void* stream) {
+    if (!a.x || !a.stat_a || !a.stat_b || !(a.eps >= 0.0f) || (training && s.N < 2)) return VPN_E_BADARG;
+    const bool affine = a.dw || a.db;
+    if (!a.dx && !a.dres && !affine) return 0;                       // nothing is wanted
+    const bool sums = training || affine;                            // eval: dx needs no sum
+    const bool split = !SRC::onepass || s.N > TN_MAX;
+    const bool partial = sums || a.dres;                             // split regime: launch 1 forms the sums and writes d_residual
+    if (split && partial && !tn_workspace_ok(s, workspace, workspace_bytes)) return VPN_E_BADARG;
+    a.ws = split && partial ? (float*)workspace : nullptr;
+    a.eval = training ? 0 : 1;
+    a.sums = split && sums ? 1 : 0;
+    hipStream_t st = (hipStream_t)stream;
+    if constexpr (SRC::onepass) {
+        if (!split) {
+            const int block = s.N <= TN_SMALL ? 64 : TN_BLOCK;
+            tn_units(&s, vec ? 4 : 1, block);
+            const dim3 grid((unsigned)s.C);
+            tn_pick(block, vec, [&](auto BLOCK, auto V) {
+                VPN_LAUNCH_AS(L.onepass, (bwd_onepass_kernel<SRC, BLOCK(), V()>), grid, dim3(BLOCK()), 0, st, s, a, src);
+            });
+            VPN_LAUNCH_CHECK();
+            return 0;
+        }
+    }
+    tn_units(&s, vec ? 4 : 1, TN_BLOCK);
+    const dim3 grid((unsigned)s.C, (unsigned)s.S);
     if (partial) {
-        if (vec) VPN_LAUNCH_AS("tn_bwd_partial_kernel", (tn_bwd_partial_kernel<4>), grid, dim3(TN_BLOCK), 0, st, s, a);
-        else VPN_LAUNCH_AS("tn_bwd_partial_kernel", (tn_bwd_partial_kernel<1>), grid, dim3(TN_BLOCK), 0, st, s, a);
+        tn_pick(vec, [&](auto V) { VPN_LAUNCH_AS(L.partial, (bwd_partial_kernel<SRC, V()>), grid, dim3(TN_BLOCK), 0, st, s, a, src); });
         VPN_LAUNCH_CHECK();
     }
-    if (dx || affine) {
-        const dim3 g2 = dx ? grid : dim3((unsigned)C, 1u);
-        if (vec) VPN_LAUNCH_AS("tn_bwd_apply_kernel", (tn_bwd_apply_kernel<4>), g2, dim3(TN_BLOCK), 0, st, s, a);
-        else VPN_LAUNCH_AS("tn_bwd_apply_kernel", (tn_bwd_apply_kernel<1>), g2, dim3(TN_BLOCK), 0, st, s, a);
+    if (a.dx || affine) {
+        const dim3 g2 = a.dx ? grid : dim3((unsigned)s.C, 1u);
+        tn_pick(vec, [&](auto V) { VPN_LAUNCH_AS(L.apply, (bwd_apply_kernel<SRC, V()>), g2, dim3(TN_BLOCK), 0, st, s, a, src); });
         VPN_LAUNCH_CHECK();
     }
     return 0;
+}
+
+// vpn_bn_act_bwd and vpn_bn_tail_bwd behind their shape checks and the check of their upstream gradients
+template <class SRC>
+static int tn_ring_bwd(const TnLabels& L, const SRC& src, const TnShape& s, const float* dy, const float* x, const float* y,
+                       const float* weight, const float* stat_mean, const float* stat_var, int training, float eps, int relu,
+                       float* dx, float* d_residual, float* d_weight, float* d_bias, void* workspace, size_t workspace_bytes,
+                       void* stream) {
+    if (relu && !y) return VPN_E_BADARG;
+    const TnBwd a{dy, x, relu ? y : nullptr, weight, stat_mean, stat_var, dx, d_residual, d_weight, d_bias, nullptr, eps, 0, 0};
+    const bool vec = s.HW % 4 == 0 && tn_aligned16(dy) && tn_aligned16(x) && tn_aligned16(a.y) && tn_aligned16(dx) &&
+                     tn_aligned16(d_residual);
+    return tn_bwd(L, src, s, a, training, vec, workspace, workspace_bytes, stream);
 }
 
 // shape checks of the pool's entry points on top of tn_shape
@@ -982,91 +851,6 @@ static int tp_shape(int B, int C, int H, int W, TnShape* s, TpShape* g) {
     const long long NP = (long long)B * g->PH * g->PW, SP = (NP + TP_SLICE - 1) / TP_SLICE;
     if (SP > 65535) return VPN_E_TOOBIG;
     g->NP = (int)NP; g->SP = (int)SP;
-    return 0;
-}
-
-extern "C" size_t vpn_bn_pool_workspace(int B, int C, int H, int W) {
-    TnShape s;
-    TpShape g;
-    if (tp_shape(B, C, H, W, &s, &g) != 0) return 0;
-    return (size_t)C * s.S * 2 * sizeof(float);
-}
-
-static bool tp_workspace_ok(const void* workspace, size_t bytes, int B, int C, int H, int W) {
-    return workspace && bytes >= vpn_bn_pool_workspace(B, C, H, W) && !((uintptr_t)workspace & 3);
-}
-
-extern "C" int vpn_bn_pool_fwd(const float* x, const float* weight, const float* bias, float* running_mean, float* running_var,
-                               long long* num_batches_tracked, int B, int C, int H, int W, int training, float momentum, float eps,
-                               float* p, unsigned char* idx, float* save_mean, float* save_invstd, void* workspace,
-                               size_t workspace_bytes, void* stream) {
-    TnShape s;
-    TpShape g;
-    const int rc = tp_shape(B, C, H, W, &s, &g);
-    if (rc) return rc;
-    if (!x || !p || !idx || !(eps >= 0.0f)) return VPN_E_BADARG;
-    if (training ? (!save_mean || !save_invstd || s.N < 2 || !(momentum >= 0.0f && momentum <= 1.0f)) : (!running_mean || !running_var))
-        return VPN_E_BADARG;
-    const bool split = training && s.N > TN_MAX;
-    if (split && !tp_workspace_ok(workspace, workspace_bytes, B, C, H, W)) return VPN_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
-    TnFwd a{x, nullptr, weight, bias, running_mean, running_var, training ? num_batches_tracked : nullptr, p, save_mean,
-            save_invstd, split ? (float*)workspace : nullptr, momentum, eps, 1};
-    const bool vec = s.HW % 4 == 0 && tn_aligned16(x);              // how the statistics read x; the pool asks for W % 4 == 0
-    const int block = training && s.N <= TN_SMALL ? 64 : TN_BLOCK;
-    tn_units(&s, vec ? 4 : 1, block);
-    if (training && !split) {
-        const dim3 grid((unsigned)C);
-        if (block == 64) {
-            if (vec) VPN_LAUNCH_AS("tp_fwd_onepass_kernel", (tp_fwd_onepass_kernel<64, 4>), grid, dim3(64), 0, st, s, g, a, idx);
-            else VPN_LAUNCH_AS("tp_fwd_onepass_kernel", (tp_fwd_onepass_kernel<64, 1>), grid, dim3(64), 0, st, s, g, a, idx);
-        } else {
-            if (vec) VPN_LAUNCH_AS("tp_fwd_onepass_kernel", (tp_fwd_onepass_kernel<TN_BLOCK, 4>), grid, dim3(TN_BLOCK), 0, st, s, g, a, idx);
-            else VPN_LAUNCH_AS("tp_fwd_onepass_kernel", (tp_fwd_onepass_kernel<TN_BLOCK, 1>), grid, dim3(TN_BLOCK), 0, st, s, g, a, idx);
-        }
-        VPN_LAUNCH_CHECK();
-        return 0;
-    }
-    if (split) {                                   // the statistics launch of vpn_bn_act_fwd
-        const dim3 grid((unsigned)C, (unsigned)s.S);
-        if (vec) VPN_LAUNCH_AS("tn_stats_kernel", (tn_stats_kernel<4>), grid, dim3(TN_BLOCK), 0, st, s, a);
-        else VPN_LAUNCH_AS("tn_stats_kernel", (tn_stats_kernel<1>), grid, dim3(TN_BLOCK), 0, st, s, a);
-        VPN_LAUNCH_CHECK();
-    }
-    const dim3 grid((unsigned)C, (unsigned)g.SP);
-    if (vec && W % 4 == 0) VPN_LAUNCH_AS("tp_fwd_kernel", (tp_fwd_kernel<4>), grid, dim3(TN_BLOCK), 0, st, s, g, a, idx);
-    else VPN_LAUNCH_AS("tp_fwd_kernel", (tp_fwd_kernel<1>), grid, dim3(TN_BLOCK), 0, st, s, g, a, idx);
-    VPN_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int vpn_bn_pool_bwd(const float* dp, const float* x, const float* p, const unsigned char* idx, const float* weight,
-                               const float* stat_mean, const float* stat_var, int B, int C, int H, int W, int training, float eps,
-                               float* dx, float* d_weight, float* d_bias, void* workspace, size_t workspace_bytes, void* stream) {
-    TnShape s;
-    TpShape g;
-    const int rc = tp_shape(B, C, H, W, &s, &g);
-    if (rc) return rc;
-    if (!dp || !x || !p || !idx || !stat_mean || !stat_var || !(eps >= 0.0f) || (training && s.N < 2)) return VPN_E_BADARG;
-    const bool affine = d_weight || d_bias;
-    if (!dx && !affine) return 0;                                    // nothing is wanted
-    const bool sums = training || affine;                            // eval: dx needs no sum
-    if (sums && !tp_workspace_ok(workspace, workspace_bytes, B, C, H, W)) return VPN_E_BADARG;
-    const bool vec = W % 4 == 0 && tn_aligned16(x) && tn_aligned16(dx);
-    hipStream_t st = (hipStream_t)stream;
-    TnBwd a{dp, x, p, weight, stat_mean, stat_var, dx, nullptr, d_weight, d_bias, sums ? (float*)workspace : nullptr, eps,
-            training ? 0 : 1, sums ? 1 : 0};
-    tn_units(&s, vec ? 4 : 1, TN_BLOCK);
-    const dim3 grid((unsigned)C, (unsigned)s.S);
-    if (sums) {
-        if (vec) VPN_LAUNCH_AS("tp_bwd_partial_kernel", (tp_bwd_partial_kernel<4>), grid, dim3(TN_BLOCK), 0, st, s, g, a, idx);
-        else VPN_LAUNCH_AS("tp_bwd_partial_kernel", (tp_bwd_partial_kernel<1>), grid, dim3(TN_BLOCK), 0, st, s, g, a, idx);
-        VPN_LAUNCH_CHECK();
-    }
-    const dim3 g2 = dx ? grid : dim3((unsigned)C, 1u);
-    if (vec) VPN_LAUNCH_AS("tp_bwd_apply_kernel", (tp_bwd_apply_kernel<4>), g2, dim3(TN_BLOCK), 0, st, s, g, a, idx);
-    else VPN_LAUNCH_AS("tp_bwd_apply_kernel", (tp_bwd_apply_kernel<1>), g2, dim3(TN_BLOCK), 0, st, s, g, a, idx);
-    VPN_LAUNCH_CHECK();
     return 0;
 }
 
@@ -1082,11 +866,103 @@ static int tt_shape(int B, int C, int H, int W, TnShape* s, TtRows* t) {
     return 0;
 }
 
+}  // namespace vpn
+
+using namespace vpn;
+
+extern "C" size_t vpn_bn_act_workspace(int B, int C, int H, int W) {
+    TnShape s;
+    if (tn_shape(B, C, H, W, &s) != 0 || s.N <= TN_MAX) return 0;
+    return tn_workspace_bytes(s);
+}
+
+extern "C" int vpn_bn_act_fwd(const float* x, const float* residual, const float* weight, const float* bias, float* running_mean,
+                              float* running_var, long long* num_batches_tracked, int B, int C, int H, int W, int training,
+                              float momentum, float eps, int relu, float* y, float* save_mean, float* save_invstd, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    TnShape s;
+    const int rc = tn_shape(B, C, H, W, &s);
+    if (rc) return rc;
+    return tn_ring_fwd(s, nullptr, nullptr, x, residual, weight, bias, running_mean, running_var, num_batches_tracked, training,
+                       momentum, eps, relu, y, save_mean, save_invstd, workspace, workspace_bytes, stream);
+}
+
+extern "C" int vpn_bn_act_bwd(const float* dy, const float* x, const float* y, const float* weight, const float* stat_mean,
+                              const float* stat_var, int B, int C, int H, int W, int training, float eps, int relu, float* dx,
+                              float* d_residual, float* d_weight, float* d_bias, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+    static const TnLabels L{"tn_bwd_onepass_kernel", "tn_bwd_partial_kernel", "tn_bwd_apply_kernel"};
+    TnShape s;
+    const int rc = tn_shape(B, C, H, W, &s);
+    if (rc) return rc;
+    if (!dy) return VPN_E_BADARG;
+    return tn_ring_bwd(L, ActGrad{}, s, dy, x, y, weight, stat_mean, stat_var, training, eps, relu, dx, d_residual, d_weight, d_bias,
+                       workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t vpn_bn_pool_workspace(int B, int C, int H, int W) {
+    TnShape s;
+    TpShape g;
+    if (tp_shape(B, C, H, W, &s, &g) != 0) return 0;
+    return tn_workspace_bytes(s);
+}
+
+extern "C" int vpn_bn_pool_fwd(const float* x, const float* weight, const float* bias, float* running_mean, float* running_var,
+                               long long* num_batches_tracked, int B, int C, int H, int W, int training, float momentum, float eps,
+                               float* p, unsigned char* idx, float* save_mean, float* save_invstd, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    TnShape s;
+    TpShape g;
+    int rc = tp_shape(B, C, H, W, &s, &g);
+    if (rc) return rc;
+    if (!idx) return VPN_E_BADARG;
+    TnFwd a;
+    rc = tn_fwd_plan(s, x, nullptr, weight, bias, running_mean, running_var, num_batches_tracked, training, momentum, eps, 1, p,
+                     save_mean, save_invstd, workspace, workspace_bytes, &a);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const bool vec = s.HW % 4 == 0 && tn_aligned16(x);              // how the statistics read x; the pool asks for W % 4 == 0
+    const int block = training && s.N <= TN_SMALL ? 64 : TN_BLOCK;
+    tn_units(&s, vec ? 4 : 1, block);
+    if (training && !a.ws) {
+        const dim3 grid((unsigned)C);
+        tn_pick(block, vec, [&](auto BLOCK, auto V) {
+            VPN_LAUNCH_AS("tp_fwd_onepass_kernel", (tp_fwd_onepass_kernel<BLOCK(), V()>), grid, dim3(BLOCK()), 0, st, s, g, a, idx);
+        });
+        VPN_LAUNCH_CHECK();
+        return 0;
+    }
+    if (a.ws) {
+        rc = tn_launch_stats(s, a, vec, st);
+        if (rc) return rc;
+    }
+    const dim3 grid((unsigned)C, (unsigned)g.SP);
+    tn_pick(vec && W % 4 == 0, [&](auto V) {
+        VPN_LAUNCH_AS("tp_fwd_kernel", (tp_fwd_kernel<V()>), grid, dim3(TN_BLOCK), 0, st, s, g, a, idx);
+    });
+    VPN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vpn_bn_pool_bwd(const float* dp, const float* x, const float* p, const unsigned char* idx, const float* weight,
+                               const float* stat_mean, const float* stat_var, int B, int C, int H, int W, int training, float eps,
+                               float* dx, float* d_weight, float* d_bias, void* workspace, size_t workspace_bytes, void* stream) {
+    static const TnLabels L{nullptr, "tp_bwd_partial_kernel", "tp_bwd_apply_kernel"};
+    TnShape s;
+    TpShape g;
+    const int rc = tp_shape(B, C, H, W, &s, &g);
+    if (rc) return rc;
+    if (!dp || !p || !idx) return VPN_E_BADARG;
+    const TnBwd a{dp, x, p, weight, stat_mean, stat_var, dx, nullptr, d_weight, d_bias, nullptr, eps, 0, 0};
+    const bool vec = W % 4 == 0 && tn_aligned16(x) && tn_aligned16(dx);
+    return tn_bwd(L, PoolGrad{g, idx}, s, a, training, vec, workspace, workspace_bytes, stream);
+}
+
 extern "C" size_t vpn_bn_tail_workspace(int B, int C, int H, int W) {
     TnShape s;
     TtRows t;
     if (tt_shape(B, C, H, W, &s, &t) != 0 || s.N <= TN_MAX) return 0;
-    return (size_t)C * s.S * 2 * sizeof(float);
+    return tn_workspace_bytes(s);
 }
 
 extern "C" int vpn_bn_tail_fwd(const float* x, const float* residual, const float* weight, const float* bias, float* running_mean,
@@ -1097,90 +973,21 @@ extern "C" int vpn_bn_tail_fwd(const float* x, const float* residual, const floa
     TtRows t;
     const int rc = tt_shape(B, C, H, W, &s, &t);
     if (rc) return rc;
-    if (!x || !y || !m || !(eps >= 0.0f)) return VPN_E_BADARG;
-    if (training ? (!save_mean || !save_invstd || s.N < 2 || !(momentum >= 0.0f && momentum <= 1.0f)) : (!running_mean || !running_var))
-        return VPN_E_BADARG;
-    const bool split = training && s.N > TN_MAX;
-    if (split && (!workspace || workspace_bytes < vpn_bn_tail_workspace(B, C, H, W) || ((uintptr_t)workspace & 3))) return VPN_E_BADARG;
-    const bool vec = s.HW % 4 == 0 && tn_aligned16(x) && tn_aligned16(y) && tn_aligned16(residual);
-    hipStream_t st = (hipStream_t)stream;
-    TnFwd a{x, residual, weight, bias, running_mean, running_var, training ? num_batches_tracked : nullptr, y, save_mean,
-            save_invstd, split ? (float*)workspace : nullptr, momentum, eps, relu != 0};
-    if (training && !split) {
-        const int block = s.N <= TN_SMALL ? 64 : TN_BLOCK;
-        tn_units(&s, vec ? 4 : 1, block);
-        const dim3 grid((unsigned)C);
-        if (block == 64) {
-            if (vec) VPN_LAUNCH_AS("tt_fwd_onepass_kernel", (tt_fwd_onepass_kernel<64, 4>), grid, dim3(64), 0, st, s, t, a, m);
-            else VPN_LAUNCH_AS("tt_fwd_onepass_kernel", (tt_fwd_onepass_kernel<64, 1>), grid, dim3(64), 0, st, s, t, a, m);
-        } else {
-            if (vec) VPN_LAUNCH_AS("tt_fwd_onepass_kernel", (tt_fwd_onepass_kernel<TN_BLOCK, 4>), grid, dim3(TN_BLOCK), 0, st, s, t, a, m);
-            else VPN_LAUNCH_AS("tt_fwd_onepass_kernel", (tt_fwd_onepass_kernel<TN_BLOCK, 1>), grid, dim3(TN_BLOCK), 0, st, s, t, a, m);
-        }
-        VPN_LAUNCH_CHECK();
-        return 0;
-    }
-    tn_units(&s, vec ? 4 : 1, TN_BLOCK);
-    if (split) {                                   // the statistics launch of vpn_bn_act_fwd
-        const dim3 grid((unsigned)C, (unsigned)s.S);
-        if (vec) VPN_LAUNCH_AS("tn_stats_kernel", (tn_stats_kernel<4>), grid, dim3(TN_BLOCK), 0, st, s, a);
-        else VPN_LAUNCH_AS("tn_stats_kernel", (tn_stats_kernel<1>), grid, dim3(TN_BLOCK), 0, st, s, a);
-        VPN_LAUNCH_CHECK();
-    }
-    const dim3 grid((unsigned)C, (unsigned)((B + t.RPB - 1) / t.RPB));
-    if (vec) VPN_LAUNCH_AS("tt_fwd_apply_kernel", (tt_fwd_apply_kernel<4>), grid, dim3(TN_BLOCK), 0, st, s, t, a, m);
-    else VPN_LAUNCH_AS("tt_fwd_apply_kernel", (tt_fwd_apply_kernel<1>), grid, dim3(TN_BLOCK), 0, st, s, t, a, m);
-    VPN_LAUNCH_CHECK();
-    return 0;
+    if (!m) return VPN_E_BADARG;
+    return tn_ring_fwd(s, &t, m, x, residual, weight, bias, running_mean, running_var, num_batches_tracked, training, momentum, eps,
+                       relu, y, save_mean, save_invstd, workspace, workspace_bytes, stream);
 }
 
 extern "C" int vpn_bn_tail_bwd(const float* dy, const float* dm, const float* x, const float* y, const float* weight,
                                const float* stat_mean, const float* stat_var, int B, int C, int H, int W, int training, float eps,
                                int relu, float* dx, float* d_residual, float* d_weight, float* d_bias, void* workspace,
                                size_t workspace_bytes, void* stream) {
+    static const TnLabels L{"tt_bwd_onepass_kernel", "tt_bwd_partial_kernel", "tt_bwd_apply_kernel"};
     TnShape s;
     TtRows t;
     const int rc = tt_shape(B, C, H, W, &s, &t);
     if (rc) return rc;
-    if ((!dy && !dm) || !x || !stat_mean || !stat_var || (relu && !y) || !(eps >= 0.0f) || (training && s.N < 2)) return VPN_E_BADARG;
-    const bool affine = d_weight || d_bias;
-    if (!dx && !d_residual && !affine) return 0;                     // nothing is wanted
-    const bool sums = training || affine;                            // eval: dx needs no sum
-    const bool split = s.N > TN_MAX;
-    const bool partial = sums || d_residual;                         // split regime: launch 1 forms the sums and writes d_residual
-    if (split && partial && (!workspace || workspace_bytes < vpn_bn_tail_workspace(B, C, H, W) || ((uintptr_t)workspace & 3)))
-        return VPN_E_BADARG;
-    const bool vec = s.HW % 4 == 0 && tn_aligned16(dy) && tn_aligned16(x) && tn_aligned16(relu ? y : nullptr) && tn_aligned16(dx) &&
-                     tn_aligned16(d_residual);
-    hipStream_t st = (hipStream_t)stream;
-    TnBwd a{dy, x, relu ? y : nullptr, weight, stat_mean, stat_var, dx, d_residual, d_weight, d_bias,
-            split && partial ? (float*)workspace : nullptr, eps, training ? 0 : 1, split && sums ? 1 : 0};
-    if (!split) {
-        const int block = s.N <= TN_SMALL ? 64 : TN_BLOCK;
-        tn_units(&s, vec ? 4 : 1, block);
-        const dim3 grid((unsigned)C);
-        if (block == 64) {
-            if (vec) VPN_LAUNCH_AS("tt_bwd_onepass_kernel", (tt_bwd_onepass_kernel<64, 4>), grid, dim3(64), 0, st, s, a, dm);
-            else VPN_LAUNCH_AS("tt_bwd_onepass_kernel", (tt_bwd_onepass_kernel<64, 1>), grid, dim3(64), 0, st, s, a, dm);
-        } else {
-            if (vec) VPN_LAUNCH_AS("tt_bwd_onepass_kernel", (tt_bwd_onepass_kernel<TN_BLOCK, 4>), grid, dim3(TN_BLOCK), 0, st, s, a, dm);
-            else VPN_LAUNCH_AS("tt_bwd_onepass_kernel", (tt_bwd_onepass_kernel<TN_BLOCK, 1>), grid, dim3(TN_BLOCK), 0, st, s, a, dm);
-        }
-        VPN_LAUNCH_CHECK();
-        return 0;
-    }
-    tn_units(&s, vec ? 4 : 1, TN_BLOCK);
-    const dim3 grid((unsigned)C, (unsigned)s.S);
-    if (partial) {
-        if (vec) VPN_LAUNCH_AS("tt_bwd_partial_kernel", (tt_bwd_partial_kernel<4>), grid, dim3(TN_BLOCK), 0, st, s, a, dm);
-        else VPN_LAUNCH_AS("tt_bwd_partial_kernel", (tt_bwd_partial_kernel<1>), grid, dim3(TN_BLOCK), 0, st, s, a, dm);
-        VPN_LAUNCH_CHECK();
-    }
-    if (dx || affine) {
-        const dim3 g2 = dx ? grid : dim3((unsigned)C, 1u);
-        if (vec) VPN_LAUNCH_AS("tt_bwd_apply_kernel", (tt_bwd_apply_kernel<4>), g2, dim3(TN_BLOCK), 0, st, s, a, dm);
-        else VPN_LAUNCH_AS("tt_bwd_apply_kernel", (tt_bwd_apply_kernel<1>), g2, dim3(TN_BLOCK), 0, st, s, a, dm);
-        VPN_LAUNCH_CHECK();
-    }
-    return 0;
+    if (!dy && !dm) return VPN_E_BADARG;
+    return tn_ring_bwd(L, TailGrad{dm}, s, dy, x, y, weight, stat_mean, stat_var, training, eps, relu, dx, d_residual, d_weight,
+                       d_bias, workspace, workspace_bytes, stream);
 }

@@ -2342,6 +2342,37 @@ def _bn_act_check(x, weight, bias, running_mean, running_var, num_batches_tracke
             raise ValueError('batch_norm_act runs on the GPU only (%s is a %s tensor); there is no CPU path' % (name, t.device.type))
 
 
+def _bn_fwd_inputs(x, weight, bias, running_mean, running_var, num_batches_tracked, residual, training, momentum):
+    """The prologue of the three forwards: _bn_act_check, then (x, residual, weight, bias) contiguous (channels_last and
+    other strided inputs: NCHW first)."""
+    _bn_act_check(x, weight, bias, running_mean, running_var, num_batches_tracked, residual, training, momentum)
+    return tuple(None if t is None else t.contiguous() for t in (x, residual, weight, bias))
+
+
+def _bn_fwd_stats(x, training, running_mean, running_var, workspace):
+    """(save_mean, save_invstd, stats, ws, ws_bytes) of a forward over x.  Training: the two buffers the launch fills, which
+    are also the `stats` the backward reads, and `ws`, the buffer of the library's `workspace` query (None: the caller knows
+    that none is needed), None where that is empty.  Eval: no buffers, and the running statistics are the `stats`."""
+    if not training:
+        return None, None, (running_mean, running_var), None, 0
+    B, C, H, W = x.shape
+    save_mean = torch.empty((C,), dtype=torch.float32, device=x.device)
+    save_invstd = torch.empty((C,), dtype=torch.float32, device=x.device)
+    ws = None if workspace is None else _workspace(workspace, B, C, H, W, dev=x.device)
+    if ws is not None and not ws.numel():
+        ws = None
+    return save_mean, save_invstd, (save_mean, save_invstd), ws, 0 if ws is None else ws.numel() * 4
+
+
+def _bn_bwd_outputs(x, need_x, need_w, need_b):
+    """(dx, dw, db) of the three backwards: an uninitialised buffer for each gradient that is needed, None for the others."""
+    C = x.shape[1]
+    dx = torch.empty_like(x) if need_x else None
+    dw = torch.empty((C,), dtype=torch.float32, device=x.device) if need_w else None
+    db = torch.empty((C,), dtype=torch.float32, device=x.device) if need_b else None
+    return dx, dw, db
+
+
 class BatchNormActFunction(Function):
     """y = relu?(batch_norm(x) + residual?) on csrc/trunknorm.hip.  apply(x, weight, bias, running_mean, running_var,
     num_batches_tracked, residual | None, training, momentum, eps, relu).  Training: batch statistics, the running statistics
@@ -2351,23 +2382,13 @@ class BatchNormActFunction(Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, num_batches_tracked, residual, training, momentum, eps, relu):
         training, relu = bool(training), bool(relu)
-        _bn_act_check(x, weight, bias, running_mean, running_var, num_batches_tracked, residual, training, momentum)
-        x = x.contiguous()                    # channels_last and other strided inputs: NCHW first
-        res = None if residual is None else residual.contiguous()
-        weight = None if weight is None else weight.contiguous()
-        bias = None if bias is None else bias.contiguous()
+        x, res, weight, bias = _bn_fwd_inputs(x, weight, bias, running_mean, running_var, num_batches_tracked, residual,
+                                              training, momentum)
         B, C, H, W = x.shape
-        dev = x.device
-        y = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
-        save_mean = save_invstd = ws = None
-        if training:
-            save_mean = torch.empty((C,), dtype=torch.float32, device=dev)
-            save_invstd = torch.empty((C,), dtype=torch.float32, device=dev)
-            ws = _workspace('vpn_bn_act_workspace', B, C, H, W, dev=dev)
+        y = torch.empty((B, C, H, W), dtype=torch.float32, device=x.device)
+        save_mean, save_invstd, stats, ws, ws_bytes = _bn_fwd_stats(x, training, running_mean, running_var, 'vpn_bn_act_workspace')
         _lib.call('vpn_bn_act_fwd', x, res, weight, bias, running_mean, running_var, num_batches_tracked, B, C, H, W,
-                  int(training), float(momentum), float(eps), int(relu), y, save_mean, save_invstd,
-                  ws if ws is not None and ws.numel() else None, 0 if ws is None else ws.numel() * 4, _lib.stream())
-        stats = (save_mean, save_invstd) if training else (running_mean, running_var)
+                  int(training), float(momentum), float(eps), int(relu), y, save_mean, save_invstd, ws, ws_bytes, _lib.stream())
         ctx.save_for_backward(x, y if relu else None, weight, *stats)
         ctx.cfg = (training, float(eps), relu, residual is not None)
         return y
@@ -2375,25 +2396,30 @@ class BatchNormActFunction(Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_y):
-        x, y, weight, stat_a, stat_b = ctx.saved_tensors
-        training, eps, relu, has_res = ctx.cfg
-        need_x, need_w, need_b, need_r = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2],
-                                          has_res and ctx.needs_input_grad[6])
-        B, C, H, W = x.shape
-        dev = x.device
-        dy = grad_y.contiguous()
-        dx = torch.empty_like(x) if need_x else None
-        dw = torch.empty((C,), dtype=torch.float32, device=dev) if need_w else None
-        db = torch.empty((C,), dtype=torch.float32, device=dev) if need_b else None
-        # without a ReLU the residual's gradient IS dy: returned as it is, nothing written
-        dres = torch.empty_like(x) if need_r and relu else None
-        if dx is not None or dw is not None or db is not None or dres is not None:
-            ws = _workspace('vpn_bn_act_workspace', B, C, H, W, dev=dev)
-            _lib.call('vpn_bn_act_bwd', dy, x, y, weight, stat_a, stat_b, B, C, H, W, int(training), eps, int(relu), dx, dres,
-                      dw, db, ws if ws.numel() else None, ws.numel() * 4, _lib.stream())
-        if need_r and not relu:
-            dres = dy
-        return dx, dw, db, None, None, None, dres, None, None, None, None
+        return _bn_ring_backward(ctx, 'act', grad_y, None)
+
+
+def _bn_ring_backward(ctx, form, grad_y, grad_m):
+    """The backward of BatchNormActFunction (form 'act', grad_m None) and BatchNormMeanFunction (form 'tail': grad_y or
+    grad_m may be None, not both)."""
+    x, y, weight, stat_a, stat_b = ctx.saved_tensors
+    training, eps, relu, has_res = ctx.cfg
+    need_x, need_w, need_b = ctx.needs_input_grad[:3]
+    need_r = has_res and ctx.needs_input_grad[6]
+    B, C, H, W = x.shape
+    dy = None if grad_y is None else grad_y.contiguous()
+    dm = None if grad_m is None else grad_m.contiguous()
+    dx, dw, db = _bn_bwd_outputs(x, need_x, need_w, need_b)
+    # without a ReLU and without a gradient of m the residual's gradient IS dy: returned as it is, nothing written
+    dres = torch.empty_like(x) if need_r and (relu or dm is not None) else None
+    if dx is not None or dw is not None or db is not None or dres is not None:
+        ws = _workspace('vpn_bn_%s_workspace' % form, B, C, H, W, dev=x.device)
+        upstream = (dy,) if form == 'act' else (dy, dm)
+        _lib.call('vpn_bn_%s_bwd' % form, *upstream, x, y, weight, stat_a, stat_b, B, C, H, W, int(training), eps, int(relu), dx,
+                  dres, dw, db, ws if ws.numel() else None, ws.numel() * 4, _lib.stream())
+    if need_r and dres is None:
+        dres = dy
+    return dx, dw, db, None, None, None, dres, None, None, None, None
 
 
 class BatchNormMeanFunction(Function):
@@ -2407,24 +2433,15 @@ class BatchNormMeanFunction(Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, num_batches_tracked, residual, training, momentum, eps, relu):
         training, relu = bool(training), bool(relu)
-        _bn_act_check(x, weight, bias, running_mean, running_var, num_batches_tracked, residual, training, momentum)
-        x = x.contiguous()
-        res = None if residual is None else residual.contiguous()
-        weight = None if weight is None else weight.contiguous()
-        bias = None if bias is None else bias.contiguous()
+        x, res, weight, bias = _bn_fwd_inputs(x, weight, bias, running_mean, running_var, num_batches_tracked, residual,
+                                              training, momentum)
         B, C, H, W = x.shape
-        dev = x.device
-        y = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
-        m = torch.empty((B, C), dtype=torch.float32, device=dev)
-        save_mean = save_invstd = ws = None
-        if training:
-            save_mean = torch.empty((C,), dtype=torch.float32, device=dev)
-            save_invstd = torch.empty((C,), dtype=torch.float32, device=dev)
-            ws = _workspace('vpn_bn_tail_workspace', B, C, H, W, dev=dev)
+        y = torch.empty((B, C, H, W), dtype=torch.float32, device=x.device)
+        m = torch.empty((B, C), dtype=torch.float32, device=x.device)
+        save_mean, save_invstd, stats, ws, ws_bytes = _bn_fwd_stats(x, training, running_mean, running_var, 'vpn_bn_tail_workspace')
         _lib.call('vpn_bn_tail_fwd', x, res, weight, bias, running_mean, running_var, num_batches_tracked, B, C, H, W,
-                  int(training), float(momentum), float(eps), int(relu), y, m, save_mean, save_invstd,
-                  ws if ws is not None and ws.numel() else None, 0 if ws is None else ws.numel() * 4, _lib.stream())
-        stats = (save_mean, save_invstd) if training else (running_mean, running_var)
+                  int(training), float(momentum), float(eps), int(relu), y, m, save_mean, save_invstd, ws, ws_bytes,
+                  _lib.stream())
         ctx.save_for_backward(x, y if relu else None, weight, *stats)
         ctx.cfg = (training, float(eps), relu, residual is not None)
         ctx.set_materialize_grads(False)      # a gradient that does not exist arrives as None and travels as NULL
@@ -2433,29 +2450,9 @@ class BatchNormMeanFunction(Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_y, grad_m):
-        x, y, weight, stat_a, stat_b = ctx.saved_tensors
-        training, eps, relu, has_res = ctx.cfg
-        none = (None,) * 11
         if grad_y is None and grad_m is None:
-            return none
-        need_x, need_w, need_b, need_r = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2],
-                                          has_res and ctx.needs_input_grad[6])
-        B, C, H, W = x.shape
-        dev = x.device
-        dy = None if grad_y is None else grad_y.contiguous()
-        dm = None if grad_m is None else grad_m.contiguous()
-        dx = torch.empty_like(x) if need_x else None
-        dw = torch.empty((C,), dtype=torch.float32, device=dev) if need_w else None
-        db = torch.empty((C,), dtype=torch.float32, device=dev) if need_b else None
-        # without a ReLU and without a gradient of m the residual's gradient IS dy: returned as it is, nothing written
-        dres = torch.empty_like(x) if need_r and (relu or dm is not None) else None
-        if dx is not None or dw is not None or db is not None or dres is not None:
-            ws = _workspace('vpn_bn_tail_workspace', B, C, H, W, dev=dev)
-            _lib.call('vpn_bn_tail_bwd', dy, dm, x, y, weight, stat_a, stat_b, B, C, H, W, int(training), eps, int(relu), dx,
-                      dres, dw, db, ws if ws.numel() else None, ws.numel() * 4, _lib.stream())
-        if need_r and dres is None:
-            dres = dy
-        return dx, dw, db, None, None, None, dres, None, None, None, None
+            return (None,) * 11
+        return _bn_ring_backward(ctx, 'tail', grad_y, grad_m)
 
 
 def pool_out_size(H, W):
@@ -2473,25 +2470,17 @@ class BatchNormPoolFunction(Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, num_batches_tracked, training, momentum, eps):
         training = bool(training)
-        _bn_act_check(x, weight, bias, running_mean, running_var, num_batches_tracked, None, training, momentum)
-        x = x.contiguous()
-        weight = None if weight is None else weight.contiguous()
-        bias = None if bias is None else bias.contiguous()
+        x, _, weight, bias = _bn_fwd_inputs(x, weight, bias, running_mean, running_var, num_batches_tracked, None, training,
+                                            momentum)
         B, C, H, W = x.shape
         PH, PW = pool_out_size(H, W)
-        dev = x.device
-        p = torch.empty((B, C, PH, PW), dtype=torch.float32, device=dev)
-        idx = torch.empty((B, C, PH, PW), dtype=torch.uint8, device=dev)
-        save_mean = save_invstd = ws = None
-        if training:
-            save_mean = torch.empty((C,), dtype=torch.float32, device=dev)
-            save_invstd = torch.empty((C,), dtype=torch.float32, device=dev)
-            if B * H * W > TRUNKNORM_ONE_PASS_MAX:
-                ws = _workspace('vpn_bn_pool_workspace', B, C, H, W, dev=dev)
+        p = torch.empty((B, C, PH, PW), dtype=torch.float32, device=x.device)
+        idx = torch.empty((B, C, PH, PW), dtype=torch.uint8, device=x.device)
+        # the pool's query sizes the backward's workspace, needed at any N; forward only the split regime has one
+        save_mean, save_invstd, stats, ws, ws_bytes = _bn_fwd_stats(
+            x, training, running_mean, running_var, 'vpn_bn_pool_workspace' if B * H * W > TRUNKNORM_ONE_PASS_MAX else None)
         _lib.call('vpn_bn_pool_fwd', x, weight, bias, running_mean, running_var, num_batches_tracked, B, C, H, W, int(training),
-                  float(momentum), float(eps), p, idx, save_mean, save_invstd, ws, 0 if ws is None else ws.numel() * 4,
-                  _lib.stream())
-        stats = (save_mean, save_invstd) if training else (running_mean, running_var)
+                  float(momentum), float(eps), p, idx, save_mean, save_invstd, ws, ws_bytes, _lib.stream())
         ctx.save_for_backward(x, p, idx, weight, *stats)
         ctx.cfg = (training, float(eps))
         return p
@@ -2501,15 +2490,11 @@ class BatchNormPoolFunction(Function):
     def backward(ctx, grad_p):
         x, p, idx, weight, stat_a, stat_b = ctx.saved_tensors
         training, eps = ctx.cfg
-        need_x, need_w, need_b = ctx.needs_input_grad[:3]
         B, C, H, W = x.shape
-        dev = x.device
         dp = grad_p.contiguous()
-        dx = torch.empty_like(x) if need_x else None
-        dw = torch.empty((C,), dtype=torch.float32, device=dev) if need_w else None
-        db = torch.empty((C,), dtype=torch.float32, device=dev) if need_b else None
+        dx, dw, db = _bn_bwd_outputs(x, *ctx.needs_input_grad[:3])
         if dx is not None or dw is not None or db is not None:
-            ws = _workspace('vpn_bn_pool_workspace', B, C, H, W, dev=dev)
+            ws = _workspace('vpn_bn_pool_workspace', B, C, H, W, dev=x.device)
             _lib.call('vpn_bn_pool_bwd', dp, x, p, idx, weight, stat_a, stat_b, B, C, H, W, int(training), eps, dx, dw, db, ws,
                       ws.numel() * 4, _lib.stream())
         return dx, dw, db, None, None, None, None, None, None
