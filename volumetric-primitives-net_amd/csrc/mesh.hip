@@ -5,7 +5,7 @@
 // (modules/loss/silhouette.py:13-23) and train_sphere.py:128 use it, and kaolin's TriangleMesh.sample
 // (train_sphere.py:76: area-weighted surface samples of the deformed 386-vertex sphere).  Both live in kaolin, which is
 // absent: the arithmetic here follows the repo's own specification oracle.vpn_oracle.mesh_raster / mesh_sample
-// (parity unpinned), the camera is the one of the primitive raster (vpn_raster_common.h make_camera).
+// (parity unpinned), the camera is the one of the primitive raster (vpn_raster_common.h make_camera), evaluated in fp64.
 //
 // Raster: one wavefront per 16x16 pixel tile (the layout of raster.hip: lane = one pixel in each 8x8 quadrant).  The
 // wave walks the face list 64 faces at a time -- lane = face: gather its three projected corners, test the face's
@@ -26,49 +26,78 @@ constexpr float MR_X_CUT = 16.0f;         // outside a face's box inflated by sq
 constexpr int MR_LDS_F4 = 64 * 2;         // staged faces per pass: (ax, ay, bx, by), (cx, cy, face, -)
 constexpr float MR_MIN_AREA2 = 1e-12f;    // twice the NDC area below which a face has no inside (oracle MESH_MIN_AREA2): 1e-8 of a 256^2 pixel
 
-// ---- projection: (x, y) in NDC (y in [-1,1] over the image height, +x right, +y up), z = depth along the optical axis
+// ---- projection: (x, y) in NDC (y in [-1,1] over the image height, +x right, +y up), z = depth along the optical axis.
+// Camera basis and projection are evaluated in fp64 and rounded once: at sigma = 1e-4 the logit d2 / sigma turns an
+// error of 1e-7 NDC in a corner into 1e-4 of a pixel's gradient, and the fp32 camera (angle in radians, sin / cos, the
+// fp32 tan(fov / 2)) with the fp32 dot products left several times that -- per vertex, the float64 projection brings the
+// gradient's element-wise distance from float64 down about 4x (domain tests).  P vertices, not a hot path.
+constexpr double MR_TAN_HALF_FOV_D = 0.4571428511950223;   // tan(49.13434207744484 deg / 2) (oracle FOVY_DEG)
+
+struct CameraD { double eye[3], right[3], up[3], fwd[3]; };
+
+// make_camera (vpn_raster_common.h) in fp64
+__device__ inline CameraD make_camera_d(const float* cam) {
+    CameraD C;
+    const double d = (double)cam[0];
+    const double el = (double)cam[1] * (3.141592653589793 / 180.0), az = (double)cam[2] * (3.141592653589793 / 180.0);
+    const double ce = cos(el), se = sin(el), ca = cos(az), sa = sin(az);
+    C.eye[0] = d * ce * ca; C.eye[1] = d * se; C.eye[2] = d * ce * sa;
+    const double inv = 1.0 / sqrt(C.eye[0] * C.eye[0] + C.eye[1] * C.eye[1] + C.eye[2] * C.eye[2]);
+    const double zx = C.eye[0] * inv, zy = C.eye[1] * inv, zz = C.eye[2] * inv;
+    double rx = zz, rz = -zx;                              // right = normalize((0,1,0) x zax) ; up = zax x right
+    const double rinv = 1.0 / sqrt(rx * rx + rz * rz);
+    rx *= rinv; rz *= rinv;
+    C.right[0] = rx; C.right[1] = 0.0; C.right[2] = rz;
+    C.up[0] = zy * rz; C.up[1] = zz * rx - zx * rz; C.up[2] = -zy * rx;
+    C.fwd[0] = -zx; C.fwd[1] = -zy; C.fwd[2] = -zz;
+    return C;
+}
+
+// camera-space coordinates of vertex v; the fp32 depth decides "in front of the near plane" everywhere (it is what
+// stage_faces reads back from proj.z)
+__device__ inline void mesh_camera_space(const CameraD& C, const F3 v, double& xc, double& yc, double& zc) {
+    const double rx = (double)v.x - C.eye[0], ry = (double)v.y - C.eye[1], rz = (double)v.z - C.eye[2];
+    xc = rx * C.right[0] + ry * C.right[1] + rz * C.right[2];
+    yc = rx * C.up[0] + ry * C.up[1] + rz * C.up[2];
+    zc = rx * C.fwd[0] + ry * C.fwd[1] + rz * C.fwd[2];
+}
+
 __global__ __launch_bounds__(256) void mesh_project_kernel(const float* __restrict__ verts, const float* __restrict__ cam,
                                                            int P, float4* __restrict__ proj) {
-    __shared__ Camera C;
+    __shared__ CameraD C;
     const int b = blockIdx.y;
-    if (threadIdx.x == 0) C = make_camera(cam + b * 3);
+    if (threadIdx.x == 0) C = make_camera_d(cam + b * 3);
     __syncthreads();
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= P) return;
-    const F3 v = ld3(verts + ((size_t)b * P + p) * 3);
-    const float rx = v.x - C.eye[0], ry = v.y - C.eye[1], rz = v.z - C.eye[2];
-    const float xc = rx * C.right[0] + ry * C.right[1] + rz * C.right[2];
-    const float yc = rx * C.up[0] + ry * C.up[1] + rz * C.up[2];
-    const float zc = rx * C.fwd[0] + ry * C.fwd[1] + rz * C.fwd[2];
-    const float zs = zc > MR_NEAR ? zc : 1.0f;
-    const float inv = 1.0f / (zs * R_TAN_HALF_FOV);
-    proj[(size_t)b * P + p] = make_float4(xc * inv, yc * inv, zc, 0.0f);
+    double xc, yc, zc;
+    mesh_camera_space(C, ld3(verts + ((size_t)b * P + p) * 3), xc, yc, zc);
+    const double zs = (float)zc > MR_NEAR ? zc : 1.0;
+    const double inv = 1.0 / (zs * MR_TAN_HALF_FOV_D);
+    proj[(size_t)b * P + p] = make_float4((float)(xc * inv), (float)(yc * inv), (float)zc, 0.0f);
 }
 
 // d total / d verts from d total / d (x_ndc, y_ndc) of the projected vertices
 __global__ __launch_bounds__(256) void mesh_project_bwd_kernel(const float* __restrict__ verts, const float* __restrict__ cam,
                                                                int P, const float* __restrict__ gproj,
                                                                float* __restrict__ gverts) {
-    __shared__ Camera C;
+    __shared__ CameraD C;
     const int b = blockIdx.y;
-    if (threadIdx.x == 0) C = make_camera(cam + b * 3);
+    if (threadIdx.x == 0) C = make_camera_d(cam + b * 3);
     __syncthreads();
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= P) return;
-    const F3 v = ld3(verts + ((size_t)b * P + p) * 3);
-    const float rx = v.x - C.eye[0], ry = v.y - C.eye[1], rz = v.z - C.eye[2];
-    const float xc = rx * C.right[0] + ry * C.right[1] + rz * C.right[2];
-    const float yc = rx * C.up[0] + ry * C.up[1] + rz * C.up[2];
-    const float zc = rx * C.fwd[0] + ry * C.fwd[1] + rz * C.fwd[2];
-    float gx = gproj[((size_t)b * P + p) * 2], gy = gproj[((size_t)b * P + p) * 2 + 1];
-    float gxc = 0.f, gyc = 0.f, gzc = 0.f;
-    if (zc > MR_NEAR) {                                  // x = xc / (zc th), y = yc / (zc th)
-        const float inv = 1.0f / (zc * R_TAN_HALF_FOV);
+    double xc, yc, zc;
+    mesh_camera_space(C, ld3(verts + ((size_t)b * P + p) * 3), xc, yc, zc);
+    const double gx = (double)gproj[((size_t)b * P + p) * 2], gy = (double)gproj[((size_t)b * P + p) * 2 + 1];
+    double gxc = 0.0, gyc = 0.0, gzc = 0.0;
+    if ((float)zc > MR_NEAR) {                           // x = xc / (zc th), y = yc / (zc th)
+        const double inv = 1.0 / (zc * MR_TAN_HALF_FOV_D);
         gxc = gx * inv; gyc = gy * inv;
         gzc = -(gx * xc + gy * yc) * inv / zc;
     }
-    st3(gverts + ((size_t)b * P + p) * 3, gxc * C.right[0] + gyc * C.up[0] + gzc * C.fwd[0],
-        gxc * C.right[1] + gyc * C.up[1] + gzc * C.fwd[1], gxc * C.right[2] + gyc * C.up[2] + gzc * C.fwd[2]);
+    st3(gverts + ((size_t)b * P + p) * 3, (float)(gxc * C.right[0] + gyc * C.up[0] + gzc * C.fwd[0]),
+        (float)(gxc * C.right[1] + gyc * C.up[1] + gzc * C.fwd[1]), (float)(gxc * C.right[2] + gyc * C.up[2] + gzc * C.fwd[2]));
 }
 
 struct MTile {
