@@ -1,6 +1,6 @@
 """The refinement step of the reference's train_gcn.py (:119-138) on the drop-in surface, with synthetic inputs.
 
-    python examples/train_gcn_step.py [--steps 5] [--batch 8] [--net standin|vpnet_oneres] [--vpn CKPT] [--gcn-input plain|factored] [--gcn-collapse] [--vpn-fold]
+    python examples/train_gcn_step.py [--steps 5] [--batch 8] [--net standin|vpnet_oneres] [--vpn CKPT] [--gcn-input plain|factored] [--gcn-collapse] [--vpn-fold] [--mesh-reg WE,WL,WN]
 
 --net vpnet_oneres runs the reference's frozen VPNetOneRes (modules/network.py; --vpn CKPT loads a reference checkpoint
 into it as train_gcn.py:100-102 does, otherwise it is randomly initialised).  By default a stand-in
@@ -12,6 +12,10 @@ reference's step:
     gcn(predict_meshes, rgbs, ...)     train_gcn.py:129-130 GCNModel                                        (vpn_gcn_*)
     cd_loss + emd_loss                 train_gcn.py:132-135 ChamferDistanceLoss + sqrt(EMD dist).mean()
     Adam(lr, betas=(0.9, 0.99), weight_decay)               train_gcn.py:100-101
+
+--mesh-reg WE,WL,WN (off by default; not in the reference) adds vpn_amd.MeshRegularizationLoss(WE, WL, WN) of predict_vertices
+over the composed mesh's faces to the two point-set losses: edge length, uniform Laplacian, normal consistency
+(csrc/meshreg.hip).  Chamfer and EMD never look at the triangles; these three keep them from folding.
 """
 import argparse
 import os
@@ -90,7 +94,19 @@ def main(argv=None):
                     help='the frozen VPNetOneRes runs its trunk in the inference form: every batch norm folded into the convolution '
                          'before it, bias, residual add and ReLU in the convolution\'s epilogue (ResNet18.fold(), csrc/trunkfold.hip); '
                          'needs --net vpnet_oneres; the --trunk-* choices select nothing then')
+    ap.add_argument('--mesh-reg', default=None, metavar='WE,WL,WN',
+                    help='add the mesh regularisers on predict_vertices with these weights: edge length, uniform Laplacian, normal '
+                         'consistency (vpn_amd.MeshRegularizationLoss, csrc/meshreg.hip); a weight of 0 drops its term')
     args = ap.parse_args(argv)
+    mesh_reg = None
+    if args.mesh_reg is not None:
+        try:
+            weights = [float(w) for w in args.mesh_reg.split(',')]
+        except ValueError:
+            weights = []
+        if len(weights) != 3:
+            ap.error('--mesh-reg takes three numbers WE,WL,WN')
+        mesh_reg = vpn_amd.MeshRegularizationLoss(*weights)
     if args.vpn_fold and not (args.vpn or args.net == 'vpnet_oneres'):
         ap.error('--vpn-fold needs --net vpnet_oneres (or --vpn CKPT): the stand-in has no trunk to fold')
     dev = torch.device('cuda')
@@ -121,11 +137,16 @@ def main(argv=None):
         cd_loss = cd_loss_func(predict_vertices, points)
         emd_loss = calculate_emd_loss(predict_vertices, points)
         total_loss = cd_loss + emd_loss
+        if mesh_reg is not None:
+            reg_loss = mesh_reg(predict_vertices, predict_meshes[0].faces)
+            total_loss = total_loss + reg_loss
         optimizer.zero_grad()
         total_loss.backward()
         optimizer.step()
         losses.append((float(cd_loss), float(emd_loss)))
-        print('step %d  CD Loss = %.6f, EMD Loss = %.6f' % (step, losses[-1][0], losses[-1][1]), flush=True)
+        print('step %d  CD Loss = %.6f, EMD Loss = %.6f' % (step, losses[-1][0], losses[-1][1])
+              + ('' if mesh_reg is None else ', Mesh Reg = %.6f (edge %.6f, lap %.6f, normal %.6f)' % ((float(reg_loss),) + tuple(mesh_reg.last.tolist()))),
+              flush=True)
     return losses
 
 

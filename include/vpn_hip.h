@@ -1124,6 +1124,43 @@ int vpn_conv2d_bias_act_fwd(const float* x, const float* w, const float* bias, c
                             int C_out, int H, int W, int R, int stride, int pad, int relu, void* workspace, size_t workspace_bytes,
                             void* stream);
 
+/* ---- mesh regularisers (csrc/meshreg.hip): the edge-length, uniform-Laplacian (squared) and
+ * normal-consistency terms of Pixel2Mesh (Wang et al., ECCV 2018) on verts DEVICE fp32 [B,V,3] over ONE face topology shared
+ * by the batch.  out DEVICE fp32 [3] = (edge, lap, normal):
+ *   edge    mean over (b, e) of (|v_a - v_b| - edge_target)^2, as |v_a - v_b|^2 without a root when edge_target == 0; with
+ *           edge_target > 0 an edge of length exactly 0 has gradient 0.
+ *   lap     mean over (b, i), all V vertices, of |delta_i|^2, delta_i = (1 / deg_i) sum_{j in N(i)} v_j - v_i, 0 when deg_i = 0.
+ *   normal  mean over (b, pair) of 1 - s n_f.n_g / (max(|n_f|, 1e-8) max(|n_g|, 1e-8)), n_f = (v1 - v0) x (v2 - v0); a
+ *           clamped norm is a constant in the gradient.  0 when P = 0; edge and lap are 0 when E = 0.
+ * The tables are DEVICE int32, built on the host (ops.mesh_topology): faces [F,3]; edges [E,2], unique, a < b; nbr_ptr [V+1]
+ * / nbr [2E], the neighbours of a vertex in CSR form; adj [F,3], for edge j = (corner j, corner j + 1) of a face the adjacent
+ * face g of the pair across it as 2 g + (s < 0), or -1 (every edge with exactly two incident faces is one pair; a face
+ * with a repeated index is incident to nothing); vf_ptr [V+1] / vf, per vertex the (face, corner) it is of faces with a pair,
+ * as 4 f + corner.  P: the number of pairs.  Index values are NOT checked on the device.
+ * terms: bits VPN_MESHREG_EDGE | _LAP | _NORMAL; a term whose bit is absent is not computed, its value is 0 and it adds
+ *   nothing to the gradient, whatever its upstream gradient.
+ * vpn_meshreg_fwd: two launches (per-workgroup sums over 256-item chunks, then their sum in a fixed order); workspace:
+ *   vpn_meshreg_workspace(B, V, E, F) bytes (0: rejected shapes).  delta [B,V,3] and normals [B,F,3] (either may be NULL: not
+ *   written) are what the backward reads: delta under the LAP bit, normals under the NORMAL bit.
+ * vpn_meshreg_bwd: one launch, a gather per vertex: dverts [B,V,3] = sum_k grad[k] d out[k] / d verts with grad DEVICE fp32
+ *   [3]; delta (LAP) and normals (NORMAL, when P > 0) as the forward wrote them with the same terms and edge_target.
+ * No host synchronisation, nothing allocated, no atomics: bit-equal from run to run, capturable.  Any vertex degree.
+ * B <= 65535, V, E, F <= VPN_MESHREG_MAX_ITEMS: VPN_E_TOOBIG beyond.  Null pointers (edges and nbr may be NULL when E = 0, vf
+ * when P = 0), B, V or F < 1, E or P < 0, terms outside 0..7, an edge_target that is negative or not finite: VPN_E_BADARG.
+ * All before any HIP call.  Added without a change of VPN_ABI_VERSION. */
+#define VPN_MESHREG_EDGE 1
+#define VPN_MESHREG_LAP 2
+#define VPN_MESHREG_NORMAL 4
+#define VPN_MESHREG_CHUNK 256          /* items (edges, vertices, faces) per workgroup and per partial sum of the forward */
+#define VPN_MESHREG_MAX_ITEMS 16777216
+size_t vpn_meshreg_workspace(int B, int V, int E, int F);
+int vpn_meshreg_fwd(const float* verts, const int32_t* faces, const int32_t* edges, const int32_t* nbr_ptr, const int32_t* nbr,
+                    const int32_t* adj, int B, int V, int E, int F, int P, float edge_target, int terms, void* workspace,
+                    float* delta, float* normals, float* out, void* stream);
+int vpn_meshreg_bwd(const float* grad, const float* verts, const float* delta, const float* normals, const int32_t* faces,
+                    const int32_t* nbr_ptr, const int32_t* nbr, const int32_t* vf_ptr, const int32_t* vf, const int32_t* adj,
+                    int B, int V, int E, int F, int P, float edge_target, int terms, float* dverts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

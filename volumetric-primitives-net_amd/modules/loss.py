@@ -4,7 +4,7 @@ import torch
 import torch.nn as nn
 
 from .. import config
-from ..ops import ChamferFunction, EmdFunction, RasterTotalFunction
+from ..ops import ChamferFunction, EmdFunction, RasterTotalFunction, const_tensor, mesh_regularizers
 from ..primitives import PrimitivePack
 from .render import VertexRenderer
 
@@ -86,3 +86,25 @@ class SilhouetteLoss(nn.Module):
                                            VertexRenderer.sigma, VertexRenderer.gamma, VertexRenderer.z_far, self.is_mse,
                                            1.0, 0.0)
         return losses[2]
+
+
+class MeshRegularizationLoss(nn.Module):
+    """The surface priors a mesh-deformation stage trains with next to its point-set losses (Pixel2Mesh, Wang et al., ECCV
+    2018, section 3.4; not part of the reference, whose train_gcn.py:131-134 has Chamfer and EMD alone):
+    w_edge * edge + w_lap * lap + w_normal * normal of ops.mesh_regularizers over one face topology for the batch.  A
+    weight of exactly 0 drops its term from the launch.  `.last` keeps the three parts of the latest call, detached and on
+    the device (reading them is the caller's synchronisation, not this module's).  To regularise towards the primitives'
+    shape rather than towards flatness pass the offsets, forward(predict_vertices - vertices, faces): the Laplacian is
+    linear."""
+
+    def __init__(self, w_edge=1.0, w_lap=1.0, w_normal=1.0, edge_target=0.0):
+        super().__init__()
+        self.weights = (float(w_edge), float(w_lap), float(w_normal))
+        self.edge_target = float(edge_target)
+        self.terms = tuple(t for t, w in zip(('edge', 'lap', 'normal'), self.weights) if w != 0.0)
+        self.last = None
+
+    def forward(self, vertices: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+        parts = mesh_regularizers(vertices, faces, self.edge_target, self.terms)
+        self.last = parts.detach()
+        return (parts * const_tensor(self.weights, torch.float32, parts.device)).sum()

@@ -1575,6 +1575,193 @@ def gcn_project(x, theta):
     return GcnProjectFunction.apply(x, theta)
 
 
+# ---- mesh regularisers (csrc/meshreg.hip): edge length, uniform Laplacian, normal consistency
+
+MESHREG_TERMS = {'edge': _H['VPN_MESHREG_EDGE'], 'lap': _H['VPN_MESHREG_LAP'], 'normal': _H['VPN_MESHREG_NORMAL']}
+MESHREG_MAX_ITEMS = _H['VPN_MESHREG_MAX_ITEMS']
+_MESH_TOPOLOGIES = {}
+
+
+class MeshTopology:
+    """What the regularisers need of one face topology over n vertices, int32 tables on one device:
+
+        faces [F,3]; edges [E,2] (ops.gcn_edges: unique, a < b, sorted); nbr_ptr [n+1] / nbr [2E]: the neighbours of a vertex,
+        ascending; adj [F,3]: across edge j = (corner j, corner (j + 1) % 3) of face f the other face g of the pair as
+        2 g + (s < 0), or -1; vf_ptr [n+1] / vf: per vertex 4 f + corner for every face with a pair it is a corner of,
+        ascending.
+
+    An edge with exactly two incident faces is one pair (f, g, s), f < g, s = +1 when the two traverse it in opposite
+    directions (consistent winding), else -1; a face with a repeated index gives its edges and is incident to nothing.
+    `pairs` [P,3] int64 (host, sorted), E, F, n_pairs, n_boundary (edges of one face), n_nonmanifold (of three or more) and
+    n_flipped (pairs with s = -1) are host values."""
+
+    def __init__(self, n, device, tables, pairs, n_boundary, n_nonmanifold):
+        self.n, self.device, self.pairs = n, device, pairs
+        self.host = tables
+        for k, v in tables.items():
+            setattr(self, k, v.to(device))
+        self.E, self.F, self.n_pairs = int(tables['edges'].shape[0]), int(tables['faces'].shape[0]), int(pairs.shape[0])
+        self.n_boundary, self.n_nonmanifold = n_boundary, n_nonmanifold
+        self.n_flipped = int((pairs[:, 2] < 0).sum())
+
+
+def _csr(rows, values, n):
+    """(ptr [n+1] int32, values int32 ordered by (row, value)) of host int64 rows / values."""
+    order = torch.argsort(rows * (int(values.max()) + 1 if values.numel() else 1) + values)
+    ptr = torch.zeros(n + 1, dtype=torch.long)
+    ptr[1:] = torch.cumsum(torch.bincount(rows, minlength=n), 0)
+    return ptr.int(), values[order].int()
+
+
+def _unique_runs(sorted_keys):
+    """(values, first index, length) of the runs of equal values of a sorted host vector."""
+    if sorted_keys.numel() == 0:
+        z = torch.zeros(0, dtype=torch.long)
+        return z, z, z
+    values, count = torch.unique_consecutive(sorted_keys, return_counts=True)
+    return values, torch.cumsum(count, 0) - count, count
+
+
+def mesh_topology(faces, n, device):
+    """The MeshTopology of a face tensor [F,3] over n vertices on `device`, built on the host once per (face content, n,
+    device) (keyed by ops.faces_fingerprint, like ops.gcn_graph): a repeated step does no host work and no synchronisation.
+    An index outside [0, n) raises ValueError."""
+    key = (faces_fingerprint(faces), int(n), str(torch.device(device)))
+    hit = _MESH_TOPOLOGIES.get(key)
+    if hit is not None:
+        return hit
+    n = int(n)
+    f = faces.detach().cpu().long().reshape(-1, 3)
+    F = int(f.shape[0])
+    if F and (int(f.max()) >= n or int(f.min()) < 0):
+        raise ValueError('faces index vertex %d of a %d-vertex mesh' % (int(f.max()) if int(f.max()) >= n else int(f.min()), n))
+    edges = gcn_edges(f)
+    E = int(edges.shape[0])
+    nbr_ptr, nbr = _csr(torch.cat([edges[:, 0], edges[:, 1]]), torch.cat([edges[:, 1], edges[:, 0]]), n)
+    # the directed edges (face, slot) of the faces that count, grouped by their undirected edge
+    live = torch.nonzero((f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 2] != f[:, 0])).flatten()
+    fid = live.repeat_interleave(3)
+    slot = torch.arange(3).repeat(live.numel())
+    a, b = f[fid, slot], f[fid, (slot + 1) % 3]
+    ekey = torch.minimum(a, b) * n + torch.maximum(a, b)
+    order = torch.argsort(ekey, stable=True)                       # fid ascends already: within an edge the faces stay in order
+    ekey, fid, slot, fwd = ekey[order], fid[order], slot[order], (a < b)[order]
+    _, start, count = _unique_runs(ekey)
+    n_boundary, n_nonmanifold = int((count == 1).sum()), int((count >= 3).sum())
+    first = start[count == 2]
+    pf, pg = fid[first], fid[first + 1]
+    ps = torch.where(fwd[first] != fwd[first + 1], 1, -1)
+    adj = torch.full((F, 3), -1, dtype=torch.long)
+    adj[pf, slot[first]] = 2 * pg + (ps < 0).long()
+    adj[pg, slot[first + 1]] = 2 * pf + (ps < 0).long()
+    pairs = torch.stack([pf, pg, ps], 1) if first.numel() else torch.zeros((0, 3), dtype=torch.long)
+    if pairs.shape[0]:
+        pairs = pairs[torch.argsort(pf * F + pg)]
+    paired = torch.nonzero((adj >= 0).any(1)).flatten()
+    pid = paired.repeat_interleave(3)
+    corner = torch.arange(3).repeat(paired.numel())
+    vf_ptr, vf = _csr(f[pid, corner], 4 * pid + corner, n)
+    tables = dict(faces=f.int().contiguous(), edges=edges.int().contiguous(), nbr_ptr=nbr_ptr, nbr=nbr, adj=adj.int(),
+                  vf_ptr=vf_ptr, vf=vf)
+    if len(_MESH_TOPOLOGIES) > 64:
+        _MESH_TOPOLOGIES.clear()
+    hit = _MESH_TOPOLOGIES[key] = MeshTopology(n, torch.device(device), tables, pairs, n_boundary, n_nonmanifold)
+    return hit
+
+
+def meshreg_terms_mask(terms):
+    """The `terms` bit mask of vpn_meshreg_* of an iterable of names out of 'edge', 'lap', 'normal'."""
+    if isinstance(terms, str):
+        terms = (terms,)
+    mask = 0
+    for t in terms:
+        if t not in MESHREG_TERMS:
+            raise ValueError('mesh_regularizers: unknown term %r (terms are %s)' % (t, ', '.join(MESHREG_TERMS)))
+        mask |= MESHREG_TERMS[t]
+    return mask
+
+
+def _meshreg_check(verts, faces, edge_target):
+    """The contract of mesh_regularizers, from shapes and dtypes alone: ValueError before any launch."""
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 3 or verts.shape[2] != 3 or min(verts.shape) < 1:
+        raise ValueError('mesh_regularizers: verts must be [B,V,3], got %r' % (tuple(getattr(verts, 'shape', ())),))
+    if verts.dtype != torch.float32:
+        raise ValueError('mesh_regularizers: verts must be float32, got %s' % verts.dtype)
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise ValueError('mesh_regularizers: faces must be [F,3], one topology for the batch, got %r'
+                         % (tuple(getattr(faces, 'shape', ())),))
+    if faces.dtype not in (torch.int32, torch.int64):
+        raise ValueError('mesh_regularizers: faces must be int32 or int64, got %s' % faces.dtype)
+    if not (isinstance(edge_target, (int, float)) and 0.0 <= float(edge_target) < math.inf):
+        raise ValueError('mesh_regularizers: edge_target must be a finite number >= 0, got %r' % (edge_target,))
+    B, V = int(verts.shape[0]), int(verts.shape[1])
+    if B > 65535 or max(V, int(faces.shape[0])) > MESHREG_MAX_ITEMS:
+        raise ValueError('mesh_regularizers: at most 65535 samples and %d vertices or faces, got B = %d, V = %d, F = %d'
+                         % (MESHREG_MAX_ITEMS, B, V, int(faces.shape[0])))
+    return B, V
+
+
+class MeshRegFunction(Function):
+    """out [3] = (edge, lap, normal) of verts [B,V,3] over a MeshTopology (see vpn_meshreg_fwd in include/vpn_hip.h for the
+    definitions): two launches forward, one gather launch backward, no atomics, bit-equal from run to run.  The gradient goes
+    to verts only and is first order (once_differentiable); the upstream gradient [3] stays on the device, so weights
+    applied in torch never cross to the host.  When verts needs no gradient nothing is saved and nothing runs backward."""
+
+    @staticmethod
+    def forward(ctx, verts, topo, edge_target, terms):
+        if verts.dim() != 3 or tuple(verts.shape[1:]) != (topo.n, 3) or verts.shape[0] < 1 or verts.dtype != torch.float32:
+            raise ValueError('MeshRegFunction: verts must be float32 [B,%d,3] for this topology, got %s %r'
+                             % (topo.n, verts.dtype, tuple(verts.shape)))
+        if not 0 <= int(terms) <= 7 or not 0.0 <= float(edge_target) < math.inf:
+            raise ValueError('MeshRegFunction: terms is a mask of 0..7 and edge_target a finite number >= 0, got %r, %r'
+                             % (terms, edge_target))
+        verts = _f32c(verts)
+        B, V = int(verts.shape[0]), int(verts.shape[1])
+        dev = verts.device
+        need = ctx.needs_input_grad[0]
+        delta = torch.empty_like(verts) if need and terms & MESHREG_TERMS['lap'] else None
+        normals = torch.empty((B, topo.F, 3), dtype=torch.float32, device=dev) if need and terms & MESHREG_TERMS['normal'] else None
+        ws = _workspace('vpn_meshreg_workspace', B, V, topo.E, topo.F, dev=dev)
+        out = torch.empty(3, dtype=torch.float32, device=dev)
+        _lib.call('vpn_meshreg_fwd', verts, topo.faces, topo.edges, topo.nbr_ptr, topo.nbr, topo.adj, B, V, topo.E, topo.F,
+                  topo.n_pairs, float(edge_target), terms, ws, delta, normals, out, _lib.stream())
+        if need:
+            ctx.save_for_backward(verts, delta, normals)
+            ctx.meta = (topo, float(edge_target), terms)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        verts, delta, normals = ctx.saved_tensors
+        topo, edge_target, terms = ctx.meta
+        B, V = int(verts.shape[0]), int(verts.shape[1])
+        dverts = torch.empty_like(verts)
+        _lib.call('vpn_meshreg_bwd', _f32c(g), verts, delta, normals, topo.faces, topo.nbr_ptr, topo.nbr, topo.vf_ptr, topo.vf,
+                  topo.adj, B, V, topo.E, topo.F, topo.n_pairs, edge_target, terms, dverts, _lib.stream())
+        return dverts, None, None, None
+
+
+def mesh_regularizers(verts, faces, edge_target=0.0, terms=('edge', 'lap', 'normal')):
+    """[3] = (edge, lap, normal) of verts [B,V,3] fp32 over faces [F,3], one topology for the batch (MeshRegFunction):
+
+        edge    mean over (b, e) of (|v_a - v_b| - edge_target)^2 over the unique edges
+        lap     mean over (b, i) of |mean of i's neighbours - v_i|^2 (uniform weights, squared: smooth at 0)
+        normal  mean over (b, pair) of 1 - cos of the normals of two faces that share an edge
+
+    A term absent from `terms` is not computed: its value is 0 and it has no gradient.  Weight the three in torch.  To hold
+    a deformation to the SHAPE it started from rather than to flatness, pass the offsets: the Laplacian is linear, so
+    mesh_regularizers(pred - verts, faces, terms=('lap',))[1] is the mean of |delta(pred) - delta(verts)|^2.  The topology
+    tables are built once per face content (ops.mesh_topology).  Anything outside the contract raises ValueError before
+    any launch; CPU tensors have no path."""
+    mask = meshreg_terms_mask(terms)
+    _, V = _meshreg_check(verts, faces, edge_target)
+    topo = mesh_topology(faces, V, verts.device)
+    return MeshRegFunction.apply(verts, topo, float(edge_target), mask)
+
+
 # ---- the batch augmentation stage (csrc/augment.hip).  Plain functions: the augmented tensors are data, nothing here is
 # differentiable and no output requires grad.
 
