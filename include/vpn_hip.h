@@ -7,8 +7,9 @@
  *    included); the library allocates no device memory and keeps no state that a
  *    RESULT depends on (contrast: the reference's module-global renderer,
  *    vertex_renderer.py:7,18).  What it does keep per process: the optional launch
- *    profiler's event list (vpn_profile_enable/read), two "dynamic LDS limit
- *    already raised" marks and the cached VPN_CHAMFER_MODE / VPN_CHAMFER_R
+ *    profiler's event list (vpn_profile_enable/read), the "dynamic LDS limit
+ *    already raised" marks of a few kernels (vpn_chamfer_bwd's is kept per
+ *    device) and the cached VPN_CHAMFER_MODE / VPN_CHAMFER_R
  *    environment overrides -- one process per GPU is the intended deployment,
  *    several host threads driving one library instance are not supported;
  *  - all tensors are contiguous fp32 unless stated, indices are int32;
@@ -174,7 +175,9 @@ int vpn_chamfer_loss(const float* dist1, const float* dist2, int B, int N, int M
                      float w1, float w2, float* loss_b, void* stream);
 /* Backward of loss_b w.r.t. the points given grad_loss_b [B].  grad_p1 [B,N,3] /
  * grad_p2 [B,M,3] are written; either may be NULL.  A coincident pair gives NaN
- * like the reference's autograd (0/0). */
+ * like the reference's autograd (0/0).  An index outside the other cloud (the
+ * filtered scans return 0x7fffffff for a point with a NaN or infinite coordinate)
+ * is not read through: that point's row is NaN and the pair adds to no other row. */
 int vpn_chamfer_bwd(const float* p1, const float* p2,
                     const float* dist1, const int32_t* idx1,
                     const float* dist2, const int32_t* idx2,

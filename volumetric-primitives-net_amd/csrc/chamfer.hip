@@ -214,6 +214,14 @@ __global__ __launch_bounds__(256) void chamfer_loss_kernel(const float* __restri
 
 // direct terms: every point's own nearest neighbour.  grad_p1[i] = g1 (a_i - b_j*)/d ;
 // grad_p2[j] = -g2 (a_i* - b_j)/d.  Written, not accumulated.
+// An index outside the other cloud (the filtered scans report 0x7fffffff for a query with a NaN or infinite coordinate:
+// it has no nearest neighbour) is never read through, as in emd_bwd_kernel: the point's own row says NaN, and the
+// scatter kernels skip the pair.
+__device__ inline bool cb_in_range(int j, int n) { return (unsigned)j < (unsigned)n; }
+__device__ inline void cb_store_nan(float* o) {
+    const float nan = __builtin_nanf("");
+    o[0] = nan; o[1] = nan; o[2] = nan;
+}
 __global__ __launch_bounds__(256) void chamfer_bwd_direct_kernel(
     const float* __restrict__ p1, const float* __restrict__ p2, const float* __restrict__ d1,
     const int32_t* __restrict__ i1, const float* __restrict__ d2, const int32_t* __restrict__ i2,
@@ -223,18 +231,28 @@ __global__ __launch_bounds__(256) void chamfer_bwd_direct_kernel(
     const int e = blockIdx.x * 256 + threadIdx.x;
     const float g = gl[b];
     if (g1 && e < N) {
-        const float* a = p1 + ((size_t)b * N + e) * 3;
-        const float* c = p2 + ((size_t)b * M + i1[(size_t)b * N + e]) * 3;
-        float coef = (g * w1 / (float)N) / d1[(size_t)b * N + e];
+        const int j = i1[(size_t)b * N + e];
         float* o = g1 + ((size_t)b * N + e) * 3;
-        o[0] = coef * (a[0] - c[0]); o[1] = coef * (a[1] - c[1]); o[2] = coef * (a[2] - c[2]);
+        if (cb_in_range(j, M)) {
+            const float* a = p1 + ((size_t)b * N + e) * 3;
+            const float* c = p2 + ((size_t)b * M + j) * 3;
+            float coef = (g * w1 / (float)N) / d1[(size_t)b * N + e];
+            o[0] = coef * (a[0] - c[0]); o[1] = coef * (a[1] - c[1]); o[2] = coef * (a[2] - c[2]);
+        } else {
+            cb_store_nan(o);
+        }
     }
     if (g2 && e < M) {
-        const float* c = p2 + ((size_t)b * M + e) * 3;
-        const float* a = p1 + ((size_t)b * N + i2[(size_t)b * M + e]) * 3;
-        float coef = (g * w2 / (float)M) / d2[(size_t)b * M + e];
+        const int i = i2[(size_t)b * M + e];
         float* o = g2 + ((size_t)b * M + e) * 3;
-        o[0] = coef * (c[0] - a[0]); o[1] = coef * (c[1] - a[1]); o[2] = coef * (c[2] - a[2]);
+        if (cb_in_range(i, N)) {
+            const float* c = p2 + ((size_t)b * M + e) * 3;
+            const float* a = p1 + ((size_t)b * N + i) * 3;
+            float coef = (g * w2 / (float)M) / d2[(size_t)b * M + e];
+            o[0] = coef * (c[0] - a[0]); o[1] = coef * (c[1] - a[1]); o[2] = coef * (c[2] - a[2]);
+        } else {
+            cb_store_nan(o);
+        }
     }
 }
 
@@ -247,7 +265,7 @@ __global__ __launch_bounds__(256) void chamfer_bwd_scatter_kernel(
     const int b = blockIdx.y;
     const int e = blockIdx.x * 256 + threadIdx.x;
     const float g = gl[b];
-    if (g2 && e < N) {   // direction 1 pair (e, i1[e]) pushes on p2[i1[e]]
+    if (g2 && e < N && cb_in_range(i1[(size_t)b * N + e], M)) {   // direction 1 pair (e, i1[e]) pushes on p2[i1[e]]
         const int j = i1[(size_t)b * N + e];
         const float* a = p1 + ((size_t)b * N + e) * 3;
         const float* c = p2 + ((size_t)b * M + j) * 3;
@@ -257,7 +275,7 @@ __global__ __launch_bounds__(256) void chamfer_bwd_scatter_kernel(
         atomicAdd(o + 1, coef * (c[1] - a[1]));
         atomicAdd(o + 2, coef * (c[2] - a[2]));
     }
-    if (g1 && e < M) {   // direction 2 pair (i2[e], e) pushes on p1[i2[e]]
+    if (g1 && e < M && cb_in_range(i2[(size_t)b * M + e], N)) {   // direction 2 pair (i2[e], e) pushes on p1[i2[e]]
         const int i = i2[(size_t)b * M + e];
         const float* c = p2 + ((size_t)b * M + e) * 3;
         const float* a = p1 + ((size_t)b * N + i) * 3;
@@ -275,6 +293,7 @@ __global__ __launch_bounds__(256) void chamfer_bwd_scatter_kernel(
 // Replaces chamfer_bwd_direct + chamfer_bwd_scatter (global float atomics to random rows: 26 us at C3).
 constexpr int CB_THREADS = 1024;
 constexpr int CB_MAX_POINTS = 12288;
+constexpr size_t CB_LDS_DEFAULT = 65536;   // dynamic LDS a kernel may ask for without a raised limit
 
 // grad of cloud A [Na] (queries of direction dA: dA/iA over Na, scattered into by direction dB/iB over Nb)
 __global__ __launch_bounds__(CB_THREADS) void chamfer_bwd_lds_kernel(
@@ -289,6 +308,7 @@ __global__ __launch_bounds__(CB_THREADS) void chamfer_bwd_lds_kernel(
     const float ca = g * wA / (float)Na, cb = g * wB / (float)Nb;
     for (int e = threadIdx.x; e < Na; e += CB_THREADS) {          // own nearest neighbour
         const int j = iA[(size_t)b * Na + e];
+        if (!cb_in_range(j, Nb)) { cb_store_nan(acc + e * 3); continue; }
         const float coef = ca / dA[(size_t)b * Na + e];
         acc[e * 3 + 0] = coef * (A[e * 3 + 0] - Bp[j * 3 + 0]);
         acc[e * 3 + 1] = coef * (A[e * 3 + 1] - Bp[j * 3 + 1]);
@@ -297,6 +317,7 @@ __global__ __launch_bounds__(CB_THREADS) void chamfer_bwd_lds_kernel(
     __syncthreads();
     for (int e = threadIdx.x; e < Nb; e += CB_THREADS) {          // being somebody else's nearest neighbour
         const int i = iB[(size_t)b * Nb + e];
+        if (!cb_in_range(i, Na)) continue;
         const float coef = cb / dB[(size_t)b * Nb + e];
         atomicAdd(&acc[i * 3 + 0], coef * (A[i * 3 + 0] - Bp[e * 3 + 0]));
         atomicAdd(&acc[i * 3 + 1], coef * (A[i * 3 + 1] - Bp[e * 3 + 1]));
@@ -310,13 +331,22 @@ __global__ __launch_bounds__(CB_THREADS) void chamfer_bwd_lds_kernel(
 static int launch_bwd_lds(const float* pa, const float* pb, const float* dA, const int32_t* iA, const float* dB,
                           const int32_t* iB, const float* gl, int B, int Na, int Nb, float wA, float wB, float* ga,
                           hipStream_t s) {
-    static int raised = 0;
+    // the raised limit is an attribute of the kernel on ONE device: one mark per device, and a device beyond the marks
+    // sets the attribute on every such call
+    constexpr int CB_MARKS = 64;
+    static unsigned char raised[CB_MARKS];
     const size_t lds = (size_t)Na * 3 * sizeof(float);
-    if (lds > 65536 && !raised) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(chamfer_bwd_lds_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, CB_MAX_POINTS * 12);
+    if (lds > CB_LDS_DEFAULT) {
+        int dev = -1;
+        hipError_t e = hipGetDevice(&dev);
         if (e != hipSuccess) return (int)e;
-        raised = 1;
+        const bool marked = dev >= 0 && dev < CB_MARKS;
+        if (!marked || !raised[dev]) {
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(chamfer_bwd_lds_kernel),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, CB_MAX_POINTS * 12);
+            if (e != hipSuccess) return (int)e;
+            if (marked) raised[dev] = 1;
+        }
     }
     VPN_LAUNCH(chamfer_bwd_lds_kernel, dim3(B), dim3(CB_THREADS), lds, s, pa, pb, dA, iA, dB, iB, gl, Na, Nb, wA,
                        wB, ga);

@@ -416,7 +416,10 @@ __global__ __launch_bounds__(SCB_BLOCK) void sample_chamfer_bwd_kernel(
         add(pl, S0 * gx + S3 * gy + S6 * gz, S1 * gx + S4 * gy + S7 * gz, S2 * gx + S5 * gy + S8 * gz);
     };
     for (int pl = threadIdx.x; pl < n; pl += SCB_BLOCK) {              // own nearest neighbour
-        const int i = k * n + pl, j = idx1[(size_t)b * N + i];
+        // a point with a NaN coordinate has no nearest neighbour: the filtered scans give it index 0x7fffffff (and dist = inf).
+        // The index is clamped into the cloud, so nothing is read through it (one instruction in the chain idx1 -> gt); the
+        // primitive's gradient is NaN all the same, through the point's own NaN coordinate in a - g
+        const int i = k * n + pl, j = (int)min((unsigned)idx1[(size_t)b * N + i], (unsigned)(M - 1));
         const float coef = ca / dist1[(size_t)b * N + i];
         const F3 a = ld3(A + i * 3), g = ld3(G2 + j * 3);
         float gx = coef * (a.x - g.x), gy = coef * (a.y - g.y), gz = coef * (a.z - g.z);
@@ -434,7 +437,7 @@ __global__ __launch_bounds__(SCB_BLOCK) void sample_chamfer_bwd_kernel(
         }
         add(pl, gx, gy, gz);
         if (EXTRAS && ex.cn_points) {
-            const int jc = ex.cn_idx1[(size_t)b * N + i];
+            const int jc = (int)min((unsigned)ex.cn_idx1[(size_t)b * N + i], (unsigned)(ex.cn_M - 1));   // clamped as j above
             const float cc = (gl * ex.cn_c1) / ex.cn_dist1[(size_t)b * N + i];
             const F3 ac = ld3(ex.cn_points + ((size_t)b * N + i) * 3), gc = ld3(ex.cn_gt + ((size_t)b * ex.cn_M + jc) * 3);
             add_canon(pl, cc * (ac.x - gc.x), cc * (ac.y - gc.y), cc * (ac.z - gc.z));
