@@ -1,6 +1,6 @@
 """The refinement step of the reference's train_gcn.py (:119-138) on the drop-in surface, with synthetic inputs.
 
-    python examples/train_gcn_step.py [--steps 5] [--batch 8] [--net standin|vpnet_oneres] [--vpn CKPT] [--gcn-input plain|factored] [--gcn-collapse] [--vpn-fold] [--mesh-reg WE,WL,WN]
+    python examples/train_gcn_step.py [--steps 5] [--batch 8] [--net standin|vpnet_oneres] [--vpn CKPT] [--gcn-input plain|factored] [--gcn-collapse] [--vpn-fold] [--mesh-reg WE,WL,WN] [--surface-loss WP,WF]
 
 --net vpnet_oneres runs the reference's frozen VPNetOneRes (modules/network.py; --vpn CKPT loads a reference checkpoint
 into it as train_gcn.py:100-102 does, otherwise it is randomly initialised).  By default a stand-in
@@ -16,6 +16,10 @@ reference's step:
 --mesh-reg WE,WL,WN (off by default; not in the reference) adds vpn_amd.MeshRegularizationLoss(WE, WL, WN) of predict_vertices
 over the composed mesh's faces to the two point-set losses: edge length, uniform Laplacian, normal consistency
 (csrc/meshreg.hip).  Chamfer and EMD never look at the triangles; these three keep them from folding.
+
+--surface-loss WP,WF (off by default; not in the reference) adds vpn_amd.PointMeshDistanceLoss(WP, WF) of `points` against
+the surface of predict_vertices over the composed mesh's faces: the squared distance from every point to its nearest
+triangle and from every triangle to its nearest point (csrc/pointmesh.hip), the data term that sees the triangles.
 """
 import argparse
 import os
@@ -97,7 +101,19 @@ def main(argv=None):
     ap.add_argument('--mesh-reg', default=None, metavar='WE,WL,WN',
                     help='add the mesh regularisers on predict_vertices with these weights: edge length, uniform Laplacian, normal '
                          'consistency (vpn_amd.MeshRegularizationLoss, csrc/meshreg.hip); a weight of 0 drops its term')
+    ap.add_argument('--surface-loss', default=None, metavar='WP,WF',
+                    help='add the point-to-surface distance between the ground-truth points and the triangles of predict_vertices '
+                         'with these weights: points to faces, faces to points (vpn_amd.PointMeshDistanceLoss, csrc/pointmesh.hip)')
     args = ap.parse_args(argv)
+    surface_loss = None
+    if args.surface_loss is not None:
+        try:
+            weights = [float(w) for w in args.surface_loss.split(',')]
+        except ValueError:
+            weights = []
+        if len(weights) != 2:
+            ap.error('--surface-loss takes two numbers WP,WF')
+        surface_loss = vpn_amd.PointMeshDistanceLoss(*weights)
     mesh_reg = None
     if args.mesh_reg is not None:
         try:
@@ -140,12 +156,16 @@ def main(argv=None):
         if mesh_reg is not None:
             reg_loss = mesh_reg(predict_vertices, predict_meshes[0].faces)
             total_loss = total_loss + reg_loss
+        if surface_loss is not None:
+            surf_loss = surface_loss(points, predict_vertices, predict_meshes[0].faces)
+            total_loss = total_loss + surf_loss
         optimizer.zero_grad()
         total_loss.backward()
         optimizer.step()
         losses.append((float(cd_loss), float(emd_loss)))
         print('step %d  CD Loss = %.6f, EMD Loss = %.6f' % (step, losses[-1][0], losses[-1][1])
-              + ('' if mesh_reg is None else ', Mesh Reg = %.6f (edge %.6f, lap %.6f, normal %.6f)' % ((float(reg_loss),) + tuple(mesh_reg.last.tolist()))),
+              + ('' if mesh_reg is None else ', Mesh Reg = %.6f (edge %.6f, lap %.6f, normal %.6f)' % ((float(reg_loss),) + tuple(mesh_reg.last.tolist())))
+              + ('' if surface_loss is None else ', Surface Loss = %.6f (point %.6f, face %.6f)' % ((float(surf_loss),) + tuple(surface_loss.last.tolist()))),
               flush=True)
     return losses
 

@@ -1164,6 +1164,39 @@ int vpn_meshreg_bwd(const float* grad, const float* verts, const float* delta, c
                     const int32_t* nbr_ptr, const int32_t* nbr, const int32_t* vf_ptr, const int32_t* vf, const int32_t* adj,
                     int B, int V, int E, int F, int P, float edge_target, int terms, float* dverts, void* stream);
 
+/* ---- point-to-surface distance (csrc/pointmesh.hip): the squared Euclidean distance between points DEVICE
+ * fp32 [B,P,3] and the closed triangles of verts DEVICE fp32 [B,V,3] over ONE face list faces DEVICE int32 [F,3] for the
+ * batch, both ways (the point_mesh_face_distance of PyTorch3D):
+ *   d(p, T)   min over the simplex w of |p - (w0 v0 + w1 v1 + w2 v2)|^2, formed from p - c, c the closest point.  A
+ *             triangle without area is the segment or the point it degenerates to and is still a face.
+ *   dist_p [B,P], face_of_point [B,P] int32   min over the faces and the lowest face that gives it;
+ *   dist_f [B,F], point_of_face [B,F] int32   min over the points and the lowest point that gives it;
+ *   out [2] = (mean of dist_p over (b, i), mean of dist_f over (b, f)).
+ * "Lowest" is by strict < from (inf, index 0) among the values computed: every index written lies in [0, F) / [0, P)
+ * whatever the coordinates hold, NaN and inf included.  Index values of faces are NOT checked on the device.
+ * vpn_pointmesh_fwd: at most four launches (face records, the pair scan over (256-point tile, face slice, sample), the merge
+ *   of the partial minima with the chunk sums, the two means).  dist_p, face_of_point, dist_f, point_of_face and out may
+ *   each be NULL: not written.  workspace: at least vpn_pointmesh_workspace(B, P, V, F) bytes (0: rejected shapes).
+ * vpn_pointmesh_bwd: at most three launches, no scatter: per face the points that chose it (a scan of face_of_point), per
+ *   point the faces that chose it (a scan of point_of_face), a gather per vertex over vf_ptr [V+1] / vf [3F], DEVICE int32,
+ *   per vertex 4 f + corner of EVERY face it is a corner of, ascending.  grad DEVICE fp32 [2]; with c and w of the saved
+ *   index, d d / d p = 2 (p - c), d d / d v_k = -2 w_k (p - c).  dpoints [B,P,3] and dverts [B,V,3] may each be NULL: not
+ *   computed (vf_ptr, vf and workspace are needed for dverts only).  The same workspace size serves.
+ * No host synchronisation, nothing allocated, no atomics: bit-equal from run to run, capturable.
+ * Null pointers, B, P, V or F < 1, a workspace shorter than needed: VPN_E_BADARG.  B > 65535 or P, V or F >
+ * VPN_POINTMESH_MAX_ITEMS: VPN_E_TOOBIG.  All before any HIP call.  Added without a change of VPN_ABI_VERSION. */
+#define VPN_POINTMESH_TILE 256           /* points per workgroup of the pair scan */
+#define VPN_POINTMESH_MIN_SLICE 128      /* a face slice of the pair scan has at least this many faces (but for the last) */
+#define VPN_POINTMESH_MAX_SLICES 64
+#define VPN_POINTMESH_MAX_ITEMS 1048576
+size_t vpn_pointmesh_workspace(int B, int P, int V, int F);
+int vpn_pointmesh_fwd(const float* points, const float* verts, const int32_t* faces, int B, int P, int V, int F, void* workspace,
+                      size_t workspace_bytes, float* dist_p, int32_t* face_of_point, float* dist_f, int32_t* point_of_face,
+                      float* out, void* stream);
+int vpn_pointmesh_bwd(const float* grad, const float* points, const float* verts, const int32_t* faces,
+                      const int32_t* face_of_point, const int32_t* point_of_face, const int32_t* vf_ptr, const int32_t* vf, int B,
+                      int P, int V, int F, void* workspace, size_t workspace_bytes, float* dpoints, float* dverts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

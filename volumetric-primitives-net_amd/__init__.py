@@ -11,9 +11,10 @@ from .ops import (SPHERE, CUBOID, SampleFunction, TransformFunction, ChamferFunc
                   cluster_points, support_hulls, hull_meshes, hull_augment, union_surface, acd_mix_points,
                   GcnFactoredInputFunction, gcn_factored_input,
                   GcnAggregate2Function, gcn_aggregate2, GcnProjectFunction, gcn_project, gcn_blocks,
-                  MeshRegFunction, mesh_regularizers, mesh_topology)
+                  MeshRegFunction, mesh_regularizers, mesh_topology,
+                  PointMeshFunction, point_mesh_distance, point_mesh_nearest, mesh_incidence)
 from .primitives import PrimitivePack, pack_primitives, kinds_from_counts
-from .modules import (Sampling, ChamferDistanceLoss, EarthMoverDistanceLoss, SilhouetteLoss, VPDiverseLoss, MeshRegularizationLoss, VertexRenderer, PhongRenderer,
+from .modules import (Sampling, ChamferDistanceLoss, EarthMoverDistanceLoss, SilhouetteLoss, VPDiverseLoss, MeshRegularizationLoss, PointMeshDistanceLoss, VertexRenderer, PhongRenderer,
                       transform_points, rotate_points, translate_points, view_to_obj_points,
                       obj_to_view_points, rotate_points_forward_x_axis, pack_head_outputs, split_primitives, Meshing, TriangleMesh, load_obj, merge_meshes,
                       cut_mix_data, cut_mix_batch_points, adjust_point_num, mixup_points, point_mixup_data,

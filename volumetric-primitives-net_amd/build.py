@@ -13,7 +13,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libvpn_hip.so')
-SOURCES = ['vpn_api.hip', 'sampler.hip', 'chamfer.hip', 'raster.hip', 'emd.hip', 'head.hip', 'mesh.hip', 'trainstep.hip', 'gcn.hip', 'augment.hip', 'evaluate.hip', 'visualize.hip', 'phong.hip', 'reconstruct.hip', 'acdmix.hip', 'input.hip', 'gtpoints.hip', 'fcstack.hip', 'optim.hip', 'trunknorm.hip', 'trunkconv.hip', 'trunkstride.hip', 'gcnpair.hip', 'trunkfold.hip', 'meshreg.hip']
+SOURCES = ['vpn_api.hip', 'sampler.hip', 'chamfer.hip', 'raster.hip', 'emd.hip', 'head.hip', 'mesh.hip', 'trainstep.hip', 'gcn.hip', 'augment.hip', 'evaluate.hip', 'visualize.hip', 'phong.hip', 'reconstruct.hip', 'acdmix.hip', 'input.hip', 'gtpoints.hip', 'fcstack.hip', 'optim.hip', 'trunknorm.hip', 'trunkconv.hip', 'trunkstride.hip', 'gcnpair.hip', 'trunkfold.hip', 'meshreg.hip', 'pointmesh.hip']
 COMMON = ['-O3', '--offload-arch=gfx950', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function']
 COMMON += os.environ.get('VPN_EXTRA_FLAGS', '').split()      # experiments only (e.g. -DVPN_CHAMFER_DEBUG)
 RASTER_EXTRA = os.environ.get('VPN_RASTER_FLAGS', '').split()  # experiments only: extra flags for raster.hip alone

@@ -4,7 +4,7 @@ import torch
 import torch.nn as nn
 
 from .. import config
-from ..ops import ChamferFunction, EmdFunction, RasterTotalFunction, const_tensor, mesh_regularizers
+from ..ops import ChamferFunction, EmdFunction, RasterTotalFunction, const_tensor, mesh_regularizers, point_mesh_distance
 from ..primitives import PrimitivePack
 from .render import VertexRenderer
 
@@ -106,5 +106,24 @@ class MeshRegularizationLoss(nn.Module):
 
     def forward(self, vertices: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
         parts = mesh_regularizers(vertices, faces, self.edge_target, self.terms)
+        self.last = parts.detach()
+        return (parts * const_tensor(self.weights, torch.float32, parts.device)).sum()
+
+
+class PointMeshDistanceLoss(nn.Module):
+    """The data term that sees the triangles (the point_mesh_face_distance of PyTorch3D; not part of the reference, whose
+    train_gcn.py:131-134 compares the predicted VERTICES with the ground-truth points): w_point * (mean squared distance
+    from every point to its nearest triangle) + w_face * (mean squared distance from every triangle to its nearest point)
+    of ops.point_mesh_distance over one face topology for the batch.  Both parts come out of one scan, so a weight of 0
+    only drops its part from the sum and from the gradient.  `.last` keeps the two parts of the latest call, detached and
+    on the device (reading them is the caller's synchronisation, not this module's)."""
+
+    def __init__(self, w_point=1.0, w_face=1.0):
+        super().__init__()
+        self.weights = (float(w_point), float(w_face))
+        self.last = None
+
+    def forward(self, points: torch.Tensor, vertices: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+        parts = point_mesh_distance(points, vertices, faces)
         self.last = parts.detach()
         return (parts * const_tensor(self.weights, torch.float32, parts.device)).sum()

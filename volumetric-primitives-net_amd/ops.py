@@ -1762,6 +1762,151 @@ def mesh_regularizers(verts, faces, edge_target=0.0, terms=('edge', 'lap', 'norm
     return MeshRegFunction.apply(verts, topo, float(edge_target), mask)
 
 
+# ---- point-to-surface distance (csrc/pointmesh.hip): points to triangles, both ways
+
+POINTMESH_MAX_ITEMS = _H['VPN_POINTMESH_MAX_ITEMS']
+_MESH_INCIDENCES = {}
+
+
+class MeshIncidence:
+    """Which (face, corner) every vertex of one face list over n vertices is, int32 tables on one device: faces [F,3];
+    vf_ptr [n+1] / vf [3F]: per vertex 4 f + corner of EVERY face it is a corner of (a face with a repeated index counts
+    once per corner; MeshTopology.vf lists only faces with a pair), ascending.  `host` keeps the host copies."""
+
+    def __init__(self, n, device, tables):
+        self.n, self.device, self.host = n, device, tables
+        for k, v in tables.items():
+            setattr(self, k, v.to(device))
+        self.F = int(tables['faces'].shape[0])
+
+
+def mesh_incidence(faces, n, device):
+    """The MeshIncidence of a face tensor [F,3] over n vertices on `device`, built on the host once per (face content, n,
+    device) (keyed by ops.faces_fingerprint, like ops.mesh_topology): a repeated step does no host work and no
+    synchronisation.  An index outside [0, n) raises ValueError."""
+    key = (faces_fingerprint(faces), int(n), str(torch.device(device)))
+    hit = _MESH_INCIDENCES.get(key)
+    if hit is not None:
+        return hit
+    n = int(n)
+    f = faces.detach().cpu().long().reshape(-1, 3)
+    F = int(f.shape[0])
+    if F and (int(f.max()) >= n or int(f.min()) < 0):
+        raise ValueError('faces index vertex %d of a %d-vertex mesh' % (int(f.max()) if int(f.max()) >= n else int(f.min()), n))
+    fid = torch.arange(F).repeat_interleave(3)
+    corner = torch.arange(3).repeat(F)
+    vf_ptr, vf = _csr(f.reshape(-1), 4 * fid + corner, n)
+    tables = dict(faces=f.int().contiguous(), vf_ptr=vf_ptr, vf=vf)
+    if len(_MESH_INCIDENCES) > 64:
+        _MESH_INCIDENCES.clear()
+    hit = _MESH_INCIDENCES[key] = MeshIncidence(n, torch.device(device), tables)
+    return hit
+
+
+def _pointmesh_check(name, points, verts, faces):
+    """The contract of point_mesh_distance / point_mesh_nearest, from shapes and dtypes alone: ValueError before any launch."""
+    for what, t, dim in (('points', points, 'P'), ('verts', verts, 'V')):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[2] != 3 or min(t.shape) < 1:
+            raise ValueError('%s: %s must be [B,%s,3], got %r' % (name, what, dim, tuple(getattr(t, 'shape', ()))))
+        if t.dtype != torch.float32:
+            raise ValueError('%s: %s must be float32, got %s' % (name, what, t.dtype))
+    if points.shape[0] != verts.shape[0]:
+        raise ValueError('%s: points and verts must have one batch size, got %d and %d' % (name, points.shape[0], verts.shape[0]))
+    if points.device != verts.device:
+        raise ValueError('%s: points and verts must be on one device, got %s and %s' % (name, points.device, verts.device))
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise ValueError('%s: faces must be [F,3], one topology for the batch, got %r' % (name, tuple(getattr(faces, 'shape', ()))))
+    if faces.dtype not in (torch.int32, torch.int64):
+        raise ValueError('%s: faces must be int32 or int64, got %s' % (name, faces.dtype))
+    B, P, V, F = int(points.shape[0]), int(points.shape[1]), int(verts.shape[1]), int(faces.shape[0])
+    if B > 65535 or max(P, V, F) > POINTMESH_MAX_ITEMS:
+        raise ValueError('%s: at most 65535 samples and %d points, vertices or faces, got B = %d, P = %d, V = %d, F = %d'
+                         % (name, POINTMESH_MAX_ITEMS, B, P, V, F))
+    return B, P, V, F
+
+
+def _pointmesh_fwd(points, verts, inc, per_query, want_out):
+    """One vpn_pointmesh_fwd: (dist_p, face_of_point, dist_f, point_of_face) or Nones, and out [2] or None."""
+    B, P, V, dev = int(points.shape[0]), int(points.shape[1]), int(verts.shape[1]), points.device
+    ws = _workspace('vpn_pointmesh_workspace', B, P, V, inc.F, dev=dev)
+    dist_p = dist_f = fop = pof = None
+    if per_query & 1:
+        fop = torch.empty((B, P), dtype=torch.int32, device=dev)
+        pof = torch.empty((B, inc.F), dtype=torch.int32, device=dev)
+    if per_query & 2:
+        dist_p = torch.empty((B, P), dtype=torch.float32, device=dev)
+        dist_f = torch.empty((B, inc.F), dtype=torch.float32, device=dev)
+    out = torch.empty(2, dtype=torch.float32, device=dev) if want_out else None
+    _lib.call('vpn_pointmesh_fwd', points, verts, inc.faces, B, P, V, inc.F, ws, ws.numel() * 4, dist_p, fop, dist_f, pof, out,
+              _lib.stream())
+    return (dist_p, fop, dist_f, pof), out
+
+
+class PointMeshFunction(Function):
+    """out [2] = (mean over (b, i) of dist_p, mean over (b, f) of dist_f) of points [B,P,3] against the triangles of verts
+    [B,V,3] over a MeshIncidence (see vpn_pointmesh_fwd in include/vpn_hip.h for the definitions): four launches forward,
+    at most three backward, no atomics, bit-equal from run to run.  The gradient goes to points and to verts, each only when
+    needed, and is first order (once_differentiable); the upstream gradient [2] stays on the device.  Only the two index
+    tensors are saved; when neither input needs a gradient nothing is saved and the indices are not written."""
+
+    @staticmethod
+    def forward(ctx, points, verts, inc):
+        if (points.dim() != 3 or verts.dim() != 3 or points.shape[2] != 3 or tuple(verts.shape[1:]) != (inc.n, 3)
+                or points.shape[0] != verts.shape[0] or min(points.shape) < 1 or points.dtype != torch.float32
+                or verts.dtype != torch.float32):
+            raise ValueError('PointMeshFunction: points must be float32 [B,P,3] and verts float32 [B,%d,3] for this incidence, '
+                             'got %s %r and %s %r' % (inc.n, points.dtype, tuple(points.shape), verts.dtype, tuple(verts.shape)))
+        points, verts = _f32c(points), _f32c(verts)
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        (_, fop, _, pof), out = _pointmesh_fwd(points, verts, inc, 1 if need else 0, True)
+        if need:
+            ctx.save_for_backward(points, verts, fop, pof)
+            ctx.inc = inc
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        need_p, need_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_p or need_v):
+            return None, None, None
+        points, verts, fop, pof = ctx.saved_tensors
+        inc = ctx.inc
+        B, P, V = int(points.shape[0]), int(points.shape[1]), int(verts.shape[1])
+        dpoints = torch.empty_like(points) if need_p else None
+        dverts = torch.empty_like(verts) if need_v else None
+        ws = _workspace('vpn_pointmesh_workspace', B, P, V, inc.F, dev=points.device) if need_v else None
+        _lib.call('vpn_pointmesh_bwd', _f32c(g), points, verts, inc.faces, fop, pof, inc.vf_ptr, inc.vf, B, P, V, inc.F, ws,
+                  ws.numel() * 4 if need_v else 0, dpoints, dverts, _lib.stream())
+        return dpoints, dverts, None
+
+
+def point_mesh_distance(points, verts, faces):
+    """[2] = (point term, face term) of points [B,P,3] fp32 against the surface of verts [B,V,3] fp32 over faces [F,3], one
+    topology for the batch (PointMeshFunction; the point_mesh_face_distance of PyTorch3D, squared distances):
+
+        point term  mean over (b, i) of the squared distance from point i to its nearest triangle
+        face term   mean over (b, f) of the squared distance from triangle f to its nearest point
+
+    A triangle without area is the segment or point it degenerates to.  Weight the two in torch.  Differentiable to points
+    and to verts.  The incidence table is built once per face content (ops.mesh_incidence).  Anything outside the
+    contract raises ValueError before any launch; CPU tensors have no path."""
+    _, _, V, _ = _pointmesh_check('point_mesh_distance', points, verts, faces)
+    inc = mesh_incidence(faces, V, verts.device)
+    return PointMeshFunction.apply(points, verts, inc)
+
+
+def point_mesh_nearest(points, verts, faces):
+    """(dist_p [B,P], face_of_point [B,P] int32, dist_f [B,F], point_of_face [B,F] int32): per point the squared distance to
+    and the index of its nearest triangle, per triangle of its nearest point, the lowest index on ties (the forward of
+    point_mesh_distance).  No autograd node: for tests, evaluation scripts and visual debugging."""
+    _, _, V, _ = _pointmesh_check('point_mesh_nearest', points, verts, faces)
+    inc = mesh_incidence(faces, V, verts.device)
+    with torch.no_grad():
+        per_query, _ = _pointmesh_fwd(_f32c(points.detach()), _f32c(verts.detach()), inc, 3, False)
+    return per_query
+
+
 # ---- the batch augmentation stage (csrc/augment.hip).  Plain functions: the augmented tensors are data, nothing here is
 # differentiable and no output requires grad.
 
