@@ -4,6 +4,7 @@
     python examples/eval_step.py --gcn [--gcn-input factored] [--gcn-collapse]     # test_gcn.py:115-178: Chamfer + EMD on refined vertices
 
     python examples/eval_step.py --dump DIR [--three-elev] [--gcn]  # also write the visual dump of sample 0 every third batch
+    python examples/eval_step.py --surface [--thresholds 0.01,0.02] [--gcn]        # also the surface metrics
 
 The trained networks and the dataset are out of scope; what the loops do with a batch is
 the reference's, under torch.no_grad():
@@ -12,6 +13,9 @@ the reference's, under torch.no_grad():
     test_gcn.py   VPN -> sphere meshes -> GCNModel (2048 vertices) -> Chamfer + sqrt(EMD dist).mean(1)     test_gcn.py:136-143
     bookkeeping   batch means, per-class sums and counts, the table at the end                             EvaluationMeter
     dumps         Visualizer.render_vp_meshes (test.py:110-124) / render_refine_vp_meshes (test_gcn.py:154-161)
+    --surface     SurfaceEvaluationMeter beside the meter above: F-score at the thresholds, Chamfer-L1 and -L2; with --gcn on
+                  points sampled from the refined SURFACE with normal consistency (the stand-in ground-truth normals point away
+                  from the origin), without it on the sampled primitive points, which carry no normals
 
 The class indices cycle over the reference's 13 ShapeNet classes; the last batch is short."""
 import argparse
@@ -46,18 +50,24 @@ def test(args, dev):
     model = Heads(64, VP_NUM).to(dev).eval()
     kinds = [vpn_amd.SPHERE] * VP_NUM
     meter = vpn_amd.EvaluationMeter(CLASS_NAMES, dev, emd=False, cd_scale=L_VIEW_CD)
+    surface = vpn_amd.SurfaceEvaluationMeter(CLASS_NAMES, dev, thresholds=args.thresholds) if args.surface else None
     for it, (b, class_indices) in enumerate(batches(args.batches, args.batch)):
         feats = torch.randn(b, 64, device=dev)
         view_points = (torch.rand(b, VP_NUM * SAMPLE_NUM, 3, device=dev) - 0.5) * 0.8
         params = vpn_amd.pack_head_outputs(*model(feats))
         predict_points = vpn_amd.Sampling.sample_primitives(params, kinds, SAMPLE_NUM, seed=100 + it)
         meter.update(predict_points, view_points, class_indices)
+        if surface is not None:
+            surface.update(predict_points, view_points, class_indices)
         if args.dump and it % 3 == 0:                                    # test.py:110-124: the K meshes of sample 0
             volumes, rotates, translates = vpn_amd.split_primitives(params)
             vp_meshes = [vpn_amd.Meshing.sphere_meshing(volumes[k][:1], rotates[k][:1], translates[k][:1])[0] for k in range(VP_NUM)]
             vpn_amd.Visualizer.render_vp_meshes(torch.rand(3, 128, 128, device=dev), vp_meshes,
                                                 os.path.join(args.dump, 'vp_%03d.gif' % it), is_three_elev=args.three_elev)
-    return meter.report(args.epoch)
+    res = meter.report(args.epoch)
+    if surface is not None:
+        surface.report()
+    return res
 
 
 @torch.no_grad()
@@ -65,6 +75,7 @@ def test_gcn(args, dev):
     vpn = StandInVPN().to(dev).eval()
     gcn = GCNModel(factored_input=args.gcn_input == 'factored', collapse_pairs=args.gcn_collapse).to(dev).eval()
     meter = vpn_amd.EvaluationMeter(CLASS_NAMES, dev, emd=True)
+    surface = vpn_amd.SurfaceEvaluationMeter(CLASS_NAMES, dev, thresholds=args.thresholds) if args.surface else None
     for it, (b, class_indices) in enumerate(batches(args.batches, args.batch)):
         rgbs = torch.zeros(b, 3, 128, 128, device=dev)
         rgbs[:, :, 24:104, 16:112] = torch.rand(b, 3, 80, 96, device=dev)
@@ -74,10 +85,17 @@ def test_gcn(args, dev):
         predict_meshes = compose_vp_meshes(vp_meshes)
         predict_vertices = gcn(predict_meshes, rgbs, perceptual_features, global_features)
         meter.update(predict_vertices, gt_points, class_indices)
+        if surface is not None:                                          # one face list for the batch: the composed topology
+            gt_normals = torch.nn.functional.normalize(gt_points, dim=-1)
+            surface.update_mesh(predict_vertices, predict_meshes[0].faces, gt_points, class_indices, n=gt_points.size(1),
+                                seed=200 + it, gt_normals=gt_normals)
         if args.dump and it % 3 == 0:                                    # test_gcn.py:154-161
             vpn_amd.Visualizer.render_refine_vp_meshes(rgbs[0], vp_meshes[0], predict_vertices[0],
                                                        os.path.join(args.dump, 'refine_%03d.gif' % it))
-    return meter.report(args.epoch)
+    res = meter.report(args.epoch)
+    if surface is not None:
+        surface.report()
+    return res
 
 
 def main(argv=None):
@@ -92,6 +110,10 @@ def main(argv=None):
     ap.add_argument('--epoch', type=int, default=0)
     ap.add_argument('--dump', default='', metavar='DIR', help='write the visual dump of sample 0 every third batch into DIR')
     ap.add_argument('--three-elev', action='store_true', help='three elevations per frame (is_three_elev of render_vp_meshes)')
+    ap.add_argument('--surface', action='store_true',
+                    help='also run SurfaceEvaluationMeter: F-score, Chamfer-L1 / -L2 and (with --gcn) normal consistency')
+    ap.add_argument('--thresholds', default=(0.01, 0.02), type=lambda s: tuple(float(t) for t in s.split(',')),
+                    help='with --surface: the distance thresholds of the F-score, comma separated (default 0.01,0.02)')
     args = ap.parse_args(argv)
     if args.dump:
         os.makedirs(args.dump, exist_ok=True)

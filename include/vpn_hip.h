@@ -1197,6 +1197,58 @@ int vpn_pointmesh_bwd(const float* grad, const float* points, const float* verts
                       const int32_t* face_of_point, const int32_t* point_of_face, const int32_t* vf_ptr, const int32_t* vf, int B,
                       int P, int V, int F, void* workspace, size_t workspace_bytes, float* dpoints, float* dverts, void* stream);
 
+/* ---- surface evaluation (csrc/surfeval.hip): the metrics of single-view reconstruction on points sampled
+ * from the predicted SURFACE, per sample, and the per-class bookkeeping of an evaluation epoch on the device.
+ * vpn_face_normals_at: the unit normal of the face every sampled point lies on, one launch, DEVICE pointers.
+ *   batched layout (vert_offset and face_offset NULL): verts fp32 [B,P,3], ONE faces int32 [F,3] for the batch, fidx int32
+ *     [B,n] in [0,F) (what vpn_mesh_sample_fwd returns); sets is not used (pass 1).
+ *   ragged layout (both offsets given; the ground truth of a packed mesh batch): verts [P,3] with P = sumP, faces [F,3] with
+ *     F = sumF and MESH-LOCAL vertex indices, vert_offset / face_offset int32 [S+1], fidx [B,n] mesh-local with B = S sets
+ *     (what vpn_ragged_sample returns); sample b belongs to mesh b / sets.
+ *   xforms fp32 [B,3,4] or NULL: affine rows (R | t); the three corners are mapped first (x' = m0 x + m1 y + m2 z + m3, summed
+ *     left to right) and the normal is taken from the mapped corners, which is right for any affine map without an
+ *     inverse-transpose; a map of negative determinant flips the sign.
+ *   normals fp32 [B,n,3]: e1 = v1 - v0, e2 = v2 - v0, c = e1 x e2, n = c / sqrtf(c.c), every operation rounded by itself;
+ *     (0,0,0) where c.c is 0 or not finite, where the face index lies outside its range or a vertex index outside its mesh
+ *     (nothing is read out of range).
+ * vpn_surfeval_accumulate: two launches on `stream` (one workgroup per sample, then ONE workgroup for the bookkeeping; no
+ *   ticket, no atomics).  dist1 [B,N] / idx1 [B,N] (prediction -> ground truth) and dist2 [B,M] / idx2 [B,M]: the distances
+ *   and int32 indices as vpn_chamfer_fwd_ws writes them, that is EUCLIDEAN, NOT squared, distances d (the reference's Chamfer
+ *   takes the root); below, d^2 is the product formed in fp64, where it is exact; n_pred [B,N,3] and n_gt [B,M,3]: unit normals, both or
+ *   neither; thr2 [T]: SQUARED distance thresholds, fp32 on the device; class_index [B] int32.  Writes per_sample [B,W] fp32,
+ *   W = 6 + 3 T:
+ *     [0] acc2 = mean_i dist1^2    [1] comp2 = mean_j dist2^2
+ *     [2] acc1 = mean_i dist1      [3] comp1 = mean_j dist2
+ *     [4] nc1 = mean_i |n_pred[i] . n_gt[idx1[i]]|    [5] nc2 = mean_j |n_gt[j] . n_pred[idx2[j]]|   (0 without normals; the
+ *         dot product is the fp64 sum of fp64 products; a neighbour index outside its range is clamped into it)
+ *     [6, 6+T) precision_t = #{i : dist1[i]^2 < thr2[t]} / N    [6+T, 6+2T) recall_t = #{j : dist2[j]^2 < thr2[t]} / M
+ *         (the exact fp64 square against the fp32 threshold: no rounding decides a count)
+ *     [6+2T, 6+3T) fscore_t = 2 P R / (P + R), 0 when P + R = 0
+ *   Counts are integers (a NaN distance is a miss); P, R and F are formed in fp64 from them and rounded once.  Every
+ *   floating sum is taken in fp64 in ONE order (lane t of 256 owns elements t, t + 256, ...; xor tree over the wave; the
+ *   four waves (0 + 1) + (2 + 3)), divided and rounded to fp32 once: bit-equal from run to run.
+ *   state: vpn_surfeval_state_size(C, T) bytes (0: rejected sizes), 8-byte aligned, ZEROED BY THE CALLER before the first
+ *   batch of an epoch: (1 + C) W doubles -- total[W], then class_sum[C][W] -- followed by 3 + C int64 -- n_samples,
+ *   n_batches, n_invalid, class_n[C].  In sample order b = 0 .. B-1 and in fp64 (Python's `+= float(x)`): total[k] +=
+ *   per_sample[b,k]; class_sum[c][k] += per_sample[b,k] and class_n[c] += 1 for c = class_index[b]; a class index outside
+ *   [0, C) enters the totals, no class, and n_invalid.  Totals are SAMPLE-weighted: divide by n_samples (vpn_eval_accumulate
+ *   adds batch means instead, which is the reference's rule for its own two metrics).  Two states are merged by adding them
+ *   field by field.  Launches on one state must be ordered (one stream).
+ * Nothing is allocated, no host synchronisation, capturable.  A null pointer (xforms, n_pred and n_gt may be NULL), a
+ * non-positive size, one offset table or one normal tensor without the other, B no multiple of sets in the ragged layout, a
+ * misaligned state: VPN_E_BADARG.  T > VPN_SURFEVAL_MAX_THRESHOLDS, B > 65535, N, M, n, P, F or C above
+ * VPN_SURFEVAL_MAX_ITEMS: VPN_E_TOOBIG.  All before any HIP call.  Added without a change of VPN_ABI_VERSION (DESIGN.md
+ * 4.10). */
+#define VPN_SURFEVAL_MAX_THRESHOLDS 8
+#define VPN_SURFEVAL_MAX_ITEMS 16777216
+size_t vpn_surfeval_state_size(int num_classes, int T);
+int vpn_face_normals_at(const float* verts, const int32_t* faces, const int32_t* vert_offset, const int32_t* face_offset,
+                        const int32_t* fidx, const float* xforms, int B, int n, int P, int F, int sets, float* normals,
+                        void* stream);
+int vpn_surfeval_accumulate(const float* dist1, const int32_t* idx1, const float* dist2, const int32_t* idx2, const float* n_pred,
+                            const float* n_gt, const float* thr2, const int32_t* class_index, int B, int N, int M, int T,
+                            int num_classes, void* state, float* per_sample, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,13 +9,13 @@ from .network import (pack_head_outputs, split_primitives, batch_norm_act, batch
                       SDNet)
 from .meshing import Meshing, TriangleMesh, load_obj, merge_meshes
 from .dataset import (parse_split_csv, parse_rendering_metadata, split_rgba, prepare_images, resized_size, MeshBatch,
-                      sample_gt_points, gt_points, view_center_xforms, genre_xforms)
+                      sample_gt_points, gt_points, gt_normals, view_center_xforms, genre_xforms)
 from . import augmentation
 from .augmentation import (cut_mix_data, cut_mix_batch_points, adjust_point_num, mixup_points, point_mixup_data,
                            points_to_meshes_and_colors, points_to_mesh_batch, meshes_to_imgs, generate_point_mixup_data,
                            acd, augment, acd_mix_meshes, acd_mix_data)
 from . import evaluation
-from .evaluation import EvaluationMeter
+from .evaluation import EvaluationMeter, SurfaceEvaluationMeter
 from . import visualize
 from .visualize import Visualizer
 from . import optim

@@ -273,3 +273,17 @@ def gt_points(batch, dists, elevs, azims, *, n=GT_POINT_NUM, dist_invariant=Fals
     xf = torch.stack([torch.zeros_like(view), view], 1)            # set 0 is masked out: its rows are never read
     pts = sample_gt_points(batch, n, sets=2, xforms=xf, xform_mask=2, seed=seed, mesh_base=mesh_base, seed_dev=seed_dev)
     return pts[:, 0], pts[:, 1]
+
+
+def gt_normals(batch, face, *, sets=1, xforms=None):
+    """The unit normals of the ground-truth points of sample_gt_points(batch, ..., return_faces=True): face [S,sets,n] int32
+    (mesh-local) -> [S,sets,n,3].  xforms [S,sets,3,4]: the maps the points were sampled under, for EVERY set (a set that
+    xform_mask left unmapped takes the identity rows); the normal is taken from the mapped corners, so it is the normal of
+    the mapped surface for any affine map.  A face without area gives (0,0,0).  One launch, no host synchronisation."""
+    if not isinstance(batch, MeshBatch):
+        raise TypeError('batch must be a MeshBatch (MeshBatch.pack / MeshBatch.from_objs)')
+    if batch.verts is None:
+        raise RuntimeError('vpn_amd operators run on the GPU only: pack the MeshBatch with a device; there is no CPU path')
+    if xforms is not None and not isinstance(xforms, torch.Tensor):
+        xforms = torch.as_tensor(xforms, dtype=torch.float32)
+    return ops.ragged_face_normals(batch.verts, batch.faces, batch.vert_offset, batch.face_offset, face, sets=sets, xforms=xforms)

@@ -18,7 +18,13 @@ The one deliberate deviation: a class index outside [0, len(class_names)) makes 
 negative, silently count the sample for a class from the end).  Raising needs a synchronisation; here the sample is left out
 of every class sum, still enters the batch mean like in the reference, and `result()['n_invalid']` counts it.
 
-The visual dumps of the evaluation scripts (Visualizer.render_*, test.py:110-124) are modules/visualize.py."""
+The visual dumps of the evaluation scripts (Visualizer.render_*, test.py:110-124) are modules/visualize.py.
+
+SurfaceEvaluationMeter (csrc/surfeval.hip) is the same kind of meter for the metrics the reference does not
+report: Chamfer-L2 / -L1, precision / recall / F-score at distance thresholds and normal consistency on points sampled from
+the predicted SURFACE, which, unlike the vertices, see a triangle that cuts through empty space."""
+import math
+
 import torch
 
 from .. import dist as vdist
@@ -124,6 +130,169 @@ class EvaluationMeter:
                     continue
                 print(name, 'avg cd loss = %.6f' % res['class_cd'][i])
             print('============================\ntotal avg cd loss = %.6f' % fmt(res['cd']))
+        if res['n_invalid']:
+            print('n_invalid = %d (class index outside [0, %d): in the total, in no class)' % (res['n_invalid'], self.C))
+        return res
+
+
+class SurfaceEvaluationMeter:
+    """Per-class surface metrics of an evaluation epoch, kept on the device (csrc/surfeval.hip):
+
+        meter = SurfaceEvaluationMeter(class_names, device, thresholds=(0.01, 0.02))
+        for data in dataloader:
+            ...
+            meter.update_mesh(predict_vertices, faces, gt_points, data['class_index'], seed=step)
+        meter.report(epoch)
+
+    Like EvaluationMeter, `update` makes no host synchronisation, can be captured into a HIP graph and is bit-equal from run
+    to run; `result` is the ONE device-to-host copy of an epoch.  Unlike it, the totals are SAMPLE-weighted: the sum over
+    all samples divided by n_samples.  EvaluationMeter's mean over batch means is the reference's rule for the reference's
+    two metrics; these metrics have no reference to imitate, so they take the standard definition, under which a short last
+    batch weighs by its samples.  A class index outside [0, C) enters the totals, no class, and n_invalid.
+
+    Per sample, with nearest-neighbour distances d1 (prediction -> ground truth) and d2 (the other way) as chamfer_nn gives
+    them (Euclidean, not squared; squares are formed in fp64, where they are exact):
+        accuracy = mean d1^2, completeness = mean d2^2, cd = accuracy + completeness               (Chamfer-L2)
+        cd_l1 = (mean d1 + mean d2) / 2                                                             (Chamfer-L1)
+        precision_t = #{d1^2 < tau_t^2} / N, recall_t = #{d2^2 < tau_t^2} / M, fscore_t = 2 P R / (P + R), 0 when P + R = 0
+        normal_consistency = (mean |n_pred . n_gt[nearest]| + mean |n_gt . n_pred[nearest]|) / 2
+    and an epoch figure is the mean of the per-sample figure (cd and cd_l1 of the means of their two halves)."""
+
+    def __init__(self, class_names, device, thresholds=(0.01, 0.02)):
+        """thresholds: DISTANCES (not squared); the default is 1 % and 2 % of the unit box the data lives in.  The kernel
+        compares squared distances with float32(tau * tau), the product formed in float64, uploaded once here."""
+        self.class_names = [str(c) for c in class_names]
+        if not self.class_names:
+            raise ValueError('SurfaceEvaluationMeter needs at least one class name')
+        self.C = len(self.class_names)
+        self.device = torch.device(device)
+        self.thresholds = [float(t) for t in thresholds]
+        self.T = len(self.thresholds)
+        ops.surfeval_width(self.T)
+        if not all(math.isfinite(t) and t > 0.0 for t in self.thresholds):
+            raise ValueError('thresholds must be positive finite distances, got %r' % (self.thresholds,))
+        self.W = 6 + 3 * self.T
+        thr2 = torch.tensor([t * t for t in self.thresholds], dtype=torch.float64).to(torch.float32)
+        self.thr2 = thr2.pin_memory().to(self.device, non_blocking=True) if self.device.type == 'cuda' else thr2
+        self.state = ops.surfeval_state(self.C, self.T, self.device)
+        self.has_normals = False            # a host flag: whether any batch of the epoch carried normals (no read-back)
+
+    _class_index = EvaluationMeter._class_index
+
+    @torch.no_grad()
+    def update(self, predict_points, gt_points, class_indices, predict_normals=None, gt_normals=None):
+        """One batch: predict_points [B,N,3], gt_points [B,M,3] on the device (N and M may differ), class_indices [B] (a
+        device tensor, a CPU tensor or a list), unit normals [B,N,3] / [B,M,3] for both or for neither.  Returns the
+        per-sample rows [B, 6 + 3 T] (include/vpn_hip.h lists the columns) as a device tensor."""
+        if not (isinstance(predict_points, torch.Tensor) and isinstance(gt_points, torch.Tensor)
+                and predict_points.dim() == 3 and gt_points.dim() == 3):
+            raise ValueError('predict_points [B,N,3] and gt_points [B,M,3] expected')
+        if (predict_normals is None) != (gt_normals is None):
+            raise ValueError('normals of the prediction and of the ground truth come together or not at all')
+        if not (predict_points.is_cuda and gt_points.is_cuda):
+            raise RuntimeError('vpn_amd operators run on the GPU only (got a %s tensor); there is no CPU path'
+                               % predict_points.device.type)
+        rows = ops.surfeval_step(predict_points, gt_points, self._class_index(class_indices, predict_points.size(0)), self.state,
+                                 self.C, self.thr2, predict_normals, gt_normals)
+        self.has_normals = self.has_normals or predict_normals is not None
+        return rows
+
+    @torch.no_grad()
+    def update_mesh(self, verts, faces, gt_points, class_indices, *, n=2048, seed, mesh_base=0, gt_normals=None):
+        """One batch of predicted MESHES: verts [B,P,3], one faces [F,3] for the batch (int32 or int64, host or device).
+        ops.sample_meshes draws n area-weighted surface points per mesh (Philox(seed; mesh_base + b, point)); with
+        gt_normals [B,M,3] the normals of their faces are taken (ops.face_normals_at) and normal consistency is measured,
+        without them that step is skipped; then `update`.  Returns the per-sample rows."""
+        if not (isinstance(verts, torch.Tensor) and verts.dim() == 3 and verts.size(-1) == 3):
+            raise ValueError('verts [B,P,3] expected')
+        if not verts.is_cuda:
+            raise RuntimeError('vpn_amd operators run on the GPU only (got a %s tensor); there is no CPU path' % verts.device.type)
+        verts = verts.detach()
+        f32 = ops.faces_i32(faces, verts.device)
+        points, fidx, _ = ops.sample_meshes(verts, f32, n, seed, mesh_base)
+        normals = None if gt_normals is None else ops.face_normals_at(verts.float().contiguous(), f32, fidx)
+        return self.update(points, gt_points, class_indices, normals, gt_normals)
+
+    def reset(self):
+        self.state.zero_()
+        self.has_normals = False
+
+    def load_state(self, state, has_normals=True):
+        """Replace the meter's state by a copy of `state` (a state tensor of the same classes and thresholds, any device).
+        has_normals: whether the loaded epoch measured normal consistency (a state does not say)."""
+        ops.surfeval_state_fields(state, self.C, self.T)
+        self.state.copy_(state)
+        self.has_normals = bool(has_normals)
+
+    @staticmethod
+    def merge(state_a, state_b, T=2):
+        """The state of two evaluations taken together: the field-wise sum of two state tensors of the same classes and
+        thresholds (sums as float64, counts as int64).  What result(group=...) does across ranks, without a process group;
+        works on CPU tensors.  T: the number of thresholds of both (the default meter has 2); the number of classes follows
+        from the size."""
+        W = ops.surfeval_width(T)
+        if state_a.shape != state_b.shape or state_a.dim() != 1 or state_a.numel() < 2 * W + 4 or (state_a.numel() - 3 - W) % (W + 1):
+            raise ValueError('merge needs two surface evaluation states of the same number of classes and of %d thresholds' % T)
+        C = (state_a.numel() - 3 - W) // (W + 1)
+        out = torch.empty_like(state_a)
+        (sa, na), (sb, nb), (so, no) = (ops.surfeval_state_fields(t, C, T) for t in (state_a, state_b.to(state_a.device), out))
+        torch.add(sa, sb, out=so)
+        torch.add(na, nb, out=no)
+        return out
+
+    def result(self, group=None):
+        """The epoch so far as plain Python.  Epoch figures: 'cd' (accuracy + completeness), 'cd_l1', 'accuracy',
+        'completeness', 'normal_consistency' (None when no batch of the epoch carried normals), 'precision', 'recall',
+        'fscore' (lists of T); per class the same keys as 'class_*' lists, None for a class that never occurred; 'class_n',
+        'n_samples', 'n_batches', 'n_invalid', 'thresholds'.  group: a torch.distributed process group whose ranks each
+        evaluated a shard: their states are summed by one all-reduce first.  One device-to-host copy."""
+        state = self.state if group is None else vdist.all_reduce_surfeval_state(self.state, self.C, self.T, group)
+        sums, counts = ops.surfeval_state_fields(state.cpu(), self.C, self.T)
+        sums, counts = sums.tolist(), counts.tolist()
+        C, T, W = self.C, self.T, self.W
+        n_samples, n_batches, n_invalid, class_n = counts[0], counts[1], counts[2], counts[3:]
+
+        def figures(row, n):
+            if not n:
+                return None
+            m = [v / n for v in row]
+            return {'cd': m[0] + m[1], 'cd_l1': 0.5 * (m[2] + m[3]), 'accuracy': m[0], 'completeness': m[1],
+                    'normal_consistency': 0.5 * (m[4] + m[5]) if self.has_normals else None,
+                    'precision': m[6:6 + T], 'recall': m[6 + T:6 + 2 * T], 'fscore': m[6 + 2 * T:6 + 3 * T]}
+
+        keys = ('cd', 'cd_l1', 'accuracy', 'completeness', 'normal_consistency', 'precision', 'recall', 'fscore')
+        total = figures(sums[:W], n_samples)
+        per_class = [figures(sums[(1 + c) * W:(2 + c) * W], class_n[c]) for c in range(C)]
+        res = {k: None if total is None else total[k] for k in keys}
+        for k in keys:
+            res['class_' + k] = [None if f is None else f[k] for f in per_class]
+        res.update(class_n=class_n, n_samples=n_samples, n_batches=n_batches, n_invalid=n_invalid,
+                   thresholds=list(self.thresholds))
+        return res
+
+    def report(self, epoch=None, group=None):
+        """Prints one line per class that occurred, then the total; a line for n_invalid when it is not zero.  Returns
+        result()."""
+        res = self.result(group)
+        head = '\nEpoch %d\n' % epoch if epoch is not None else ''
+        print(head + '=' * 30)
+
+        def line(name, get):
+            nc = get('normal_consistency')
+            text = '%s \t\tsurface cd = %.6f, cd_l1 = %.6f, nc = %s' % (name, get('cd'), get('cd_l1'),
+                                                                     'n/a' if nc is None else '%.4f' % nc)
+            for t, tau in enumerate(self.thresholds):
+                text += ', F@%g = %.4f (P %.4f, R %.4f)' % (tau, get('fscore')[t], get('precision')[t], get('recall')[t])
+            print(text)
+
+        for i, name in enumerate(self.class_names):
+            if res['class_n'][i]:
+                line(name, lambda k, i=i: res['class_' + k][i])
+        print('=' * 30)
+        if res['n_samples']:
+            line('total', lambda k: res[k])
+        else:
+            print('total \t\tno samples')
         if res['n_invalid']:
             print('n_invalid = %d (class index outside [0, %d): in the total, in no class)' % (res['n_invalid'], self.C))
         return res

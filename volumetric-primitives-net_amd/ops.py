@@ -2248,6 +2248,166 @@ def eval_step(predict_points, gt_points, class_index, state, C, *, emd=True, eps
     return cd_b, emd_b
 
 
+# ---- surface evaluation (csrc/surfeval.hip): Chamfer-L2 / -L1, precision / recall / F-score at distance
+# thresholds and normal consistency on points sampled from the predicted surface.  Plain functions: reported values.
+
+SURFEVAL_MAX_THRESHOLDS = _H['VPN_SURFEVAL_MAX_THRESHOLDS']
+SURFEVAL_MAX_ITEMS = _H['VPN_SURFEVAL_MAX_ITEMS']
+
+
+def surfeval_width(T):
+    """Columns of a per-sample row: acc2 comp2 acc1 comp1 nc1 nc2, then precision, recall and F-score at each threshold."""
+    T = int(T)
+    if not 1 <= T <= SURFEVAL_MAX_THRESHOLDS:
+        raise ValueError('surface evaluation takes 1 .. %d thresholds, got %d' % (SURFEVAL_MAX_THRESHOLDS, T))
+    return 6 + 3 * T
+
+
+def surfeval_state(C, T, device):
+    """A zeroed state of the surface evaluation for C classes and T thresholds (include/vpn_hip.h, vpn_surfeval_accumulate):
+    one float64 tensor of (1 + C) W + 3 + C elements, W = 6 + 3 T, the last 3 + C of which hold int64 bit patterns
+    (surfeval_state_fields splits it)."""
+    surfeval_width(T)
+    nbytes = _lib.lib().vpn_surfeval_state_size(int(C), int(T))
+    if nbytes == 0:
+        raise ValueError('the surface evaluation state needs 1 .. %d classes, got %d' % (SURFEVAL_MAX_ITEMS, int(C)))
+    return torch.zeros((nbytes // 8,), dtype=torch.float64, device=device)
+
+
+def surfeval_state_fields(state, C, T):
+    """Views of a state tensor (any device): (sums float64 [(1 + C) W]: total[W] then class_sum[C][W]; counts int64 [3 + C]:
+    n_samples, n_batches, n_invalid, class_n[C])."""
+    nd = (1 + int(C)) * surfeval_width(T)
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.float64 or state.dim() != 1 or state.numel() != nd + 3 + C:
+        raise ValueError('not a surface evaluation state of %d classes and %d thresholds' % (C, T))
+    return state[:nd], state[nd:].view(torch.int64)
+
+
+def _normals_check(name, verts, faces, fidx, vdim):
+    """Shapes and dtypes of the three tensors of a normals call: ValueError before any launch."""
+    want = '[B,P,3]' if vdim == 3 else '[sumP,3]'
+    if not isinstance(verts, torch.Tensor) or verts.dim() != vdim or verts.shape[-1] != 3 or min(verts.shape) < 1:
+        raise ValueError('%s: verts must be %s, got %r' % (name, want, tuple(getattr(verts, 'shape', ()))))
+    if verts.dtype != torch.float32:
+        raise ValueError('%s: verts must be float32, got %s' % (name, verts.dtype))
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise ValueError('%s: faces must be [F,3], got %r' % (name, tuple(getattr(faces, 'shape', ()))))
+    if faces.dtype not in (torch.int32, torch.int64):
+        raise ValueError('%s: faces must be int32 or int64, got %s' % (name, faces.dtype))
+    if not isinstance(fidx, torch.Tensor) or fidx.dim() < 2 or min(fidx.shape) < 1:
+        raise ValueError('%s: fidx must be [B,n], got %r' % (name, tuple(getattr(fidx, 'shape', ()))))
+    if fidx.dtype != torch.int32:
+        raise ValueError('%s: fidx must be int32 (what the samplers return), got %s' % (name, fidx.dtype))
+    if max(verts.shape[-2], faces.shape[0], fidx.shape[-1]) > SURFEVAL_MAX_ITEMS:
+        raise ValueError('%s: at most %d vertices, faces or points' % (name, SURFEVAL_MAX_ITEMS))
+
+
+def _normals_launch(name, verts, faces, vert_offset, face_offset, fidx2, xforms, sets):
+    if not verts.is_cuda:
+        raise RuntimeError('vpn_amd operators run on the GPU only (got a %s tensor); there is no CPU path' % verts.device.type)
+    dev = verts.device
+    B, n = fidx2.shape
+    if not fidx2.is_cuda:
+        raise ValueError('%s: fidx must be on the device' % name)
+    if xforms is not None:
+        xforms = _draw_tensor('xforms', xforms, (B, 3, 4), torch.float32, dev)
+    out = torch.empty((B, n, 3), dtype=torch.float32, device=dev)
+    _lib.call('vpn_face_normals_at', verts.detach().contiguous(), faces_i32(faces, dev), vert_offset, face_offset,
+              fidx2.contiguous(), xforms, B, n, verts.shape[-2], faces.shape[0], int(sets), out, _lib.stream())
+    return out
+
+
+@torch.no_grad()
+def face_normals_at(verts, faces, fidx, xforms=None):
+    """The unit normal of the face every sampled point lies on (vpn_face_normals_at, the batched layout): verts [B,P,3]
+    fp32, ONE faces [F,3] for the batch (int32 or int64, host or device), fidx [B,n] int32 as sample_meshes returns it ->
+    normals [B,n,3].  xforms [B,3,4]: affine rows applied to the corners first; the normal of the mapped triangle needs no
+    inverse-transpose.  A map of negative determinant (a reflection) flips the sign, which the normal-consistency metric,
+    taking |dot|, does not see.  A face without area, a face index outside [0,F) or a vertex index outside [0,P) gives
+    (0,0,0).  One launch, no host synchronisation; everything is validated before it."""
+    _normals_check('face_normals_at', verts, faces, fidx, 3)
+    if fidx.dim() != 2 or fidx.shape[0] != verts.shape[0]:
+        raise ValueError('face_normals_at: fidx must be [B,n] with B = %d, got %r' % (verts.shape[0], tuple(fidx.shape)))
+    if verts.shape[0] > 65535:
+        raise ValueError('face_normals_at: at most 65535 samples, got %d' % verts.shape[0])
+    return _normals_launch('face_normals_at', verts, faces, None, None, fidx, xforms, 1)
+
+
+@torch.no_grad()
+def ragged_face_normals(verts, faces, vert_offset, face_offset, fidx, sets=1, xforms=None):
+    """face_normals_at for the packed meshes of a MeshBatch (the ragged layout): verts [sumP,3] fp32, faces [sumF,3] with
+    MESH-LOCAL vertex indices, vert_offset / face_offset [S+1] int32 on the device, fidx [S,sets,n] (or [S sets,n]) int32
+    mesh-local as ragged_sample(..., return_faces=True) returns it -> normals of the same leading shape + [3].  xforms
+    [S,sets,3,4] (or [S sets,3,4]): the map of every (mesh, set), as ragged_sample takes it."""
+    _normals_check('ragged_face_normals', verts, faces, fidx, 2)
+    sets = int(sets)
+    for what, t in (('vert_offset', vert_offset), ('face_offset', face_offset)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.numel() < 2:
+            raise ValueError('ragged_face_normals: %s must be an int32 tensor of S + 1 entries' % what)
+    S = vert_offset.numel() - 1
+    if face_offset.numel() != S + 1:
+        raise ValueError('ragged_face_normals: the two offset tables must have S + 1 entries each')
+    if sets < 1:
+        raise ValueError('ragged_face_normals: sets must be positive, got %d' % sets)
+    lead = tuple(fidx.shape[:-1])
+    if lead not in ((S, sets), (S * sets,)):
+        raise ValueError('ragged_face_normals: fidx must be [S,sets,n] = [%d,%d,n], got %r' % (S, sets, tuple(fidx.shape)))
+    if S * sets > 65535:
+        raise ValueError('ragged_face_normals: at most 65535 samples, got %d' % (S * sets))
+    if isinstance(xforms, torch.Tensor) and xforms.dim() == 4:
+        if tuple(xforms.shape) != (S, sets, 3, 4):
+            raise ValueError('xforms must be %r, got %r' % ((S, sets, 3, 4), tuple(xforms.shape)))
+        xforms = xforms.reshape(S * sets, 3, 4)
+    if verts.is_cuda and not (vert_offset.is_cuda and face_offset.is_cuda):
+        raise ValueError('ragged_face_normals: the offset tables must be on the device')
+    out = _normals_launch('ragged_face_normals', verts, faces, vert_offset.contiguous(), face_offset.contiguous(),
+                          fidx.reshape(S * sets, fidx.shape[-1]), xforms, sets)
+    return out.reshape(lead + (fidx.shape[-1], 3))
+
+
+@torch.no_grad()
+def surfeval_step(predict_points, gt_points, class_index, state, C, thr2, predict_normals=None, gt_normals=None):
+    """One batch of the surface evaluation: the nearest-neighbour scan both ways (chamfer_nn, mode 'auto'), then
+    vpn_surfeval_accumulate (two launches), which writes the per-sample rows and adds the batch to `state`
+    (surfeval_state).  predict_points [B,N,3], gt_points [B,M,3] (N and M may differ); class_index [B] int32 on the device;
+    thr2 [T] fp32 on the device: SQUARED distance thresholds; predict_normals [B,N,3] and gt_normals [B,M,3]: unit normals,
+    both or neither.  No host synchronisation; everything is validated before a launch.  -> per_sample [B, 6 + 3 T]."""
+    for what, t in (('predict_points', predict_points), ('gt_points', gt_points)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[2] != 3 or min(t.shape) < 1:
+            raise ValueError('surfeval_step: %s must be [B,n,3], got %r' % (what, tuple(getattr(t, 'shape', ()))))
+    B, N, M = predict_points.shape[0], predict_points.shape[1], gt_points.shape[1]
+    if gt_points.shape[0] != B or not isinstance(class_index, torch.Tensor) or class_index.numel() != B:
+        raise ValueError('predicted points, ground-truth points and class indices must agree on the batch size')
+    if B > 65535 or max(N, M) > SURFEVAL_MAX_ITEMS:
+        raise ValueError('surfeval_step: at most 65535 samples of %d points, got B = %d, N = %d, M = %d'
+                         % (SURFEVAL_MAX_ITEMS, B, N, M))
+    if not isinstance(thr2, torch.Tensor) or thr2.dtype != torch.float32 or thr2.dim() != 1:
+        raise ValueError('thr2 must be a float32 tensor [T] of squared thresholds')
+    T = thr2.numel()
+    surfeval_state_fields(state, C, T)
+    if (predict_normals is None) != (gt_normals is None):
+        raise ValueError('surfeval_step: normals of the prediction and of the ground truth come together or not at all')
+    for what, t, pts in (('predict_normals', predict_normals, predict_points), ('gt_normals', gt_normals, gt_points)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.shape == pts.shape and t.dtype == torch.float32):
+            raise ValueError('surfeval_step: %s must be float32 %r' % (what, tuple(pts.shape)))
+    if class_index.dtype != torch.int32:
+        raise ValueError('class_index must be an int32 tensor on the device')
+    p, g = _f32c(predict_points.detach()), _f32c(gt_points.detach())
+    dev = p.device
+    for what, t in (('class_index', class_index), ('thr2', thr2), ('state', state), ('predict_normals', predict_normals),
+                    ('gt_normals', gt_normals)):
+        if t is not None and t.device != dev:
+            raise ValueError('surfeval_step: %s must be on %s, got %s' % (what, dev, t.device))
+    if not state.is_contiguous():
+        raise ValueError('surfeval_step: the state must be contiguous')
+    d1, i1, d2, i2 = chamfer_nn(p, g)
+    per_sample = torch.empty((B, 6 + 3 * T), dtype=torch.float32, device=dev)
+    _lib.call('vpn_surfeval_accumulate', d1, i1, d2, i2, None if predict_normals is None else predict_normals.detach().contiguous(),
+              None if gt_normals is None else gt_normals.detach().contiguous(), thr2.contiguous(), class_index.reshape(-1).contiguous(),
+              B, N, M, T, int(C), state, per_sample, _lib.stream())
+    return per_sample
+
+
 # ---- the visualisation stage (csrc/visualize.hip; modules/visualize/render.py:13-24).  Plain functions: a picture has no
 # gradient.
 
