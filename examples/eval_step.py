@@ -5,6 +5,7 @@
 
     python examples/eval_step.py --dump DIR [--three-elev] [--gcn]  # also write the visual dump of sample 0 every third batch
     python examples/eval_step.py --surface [--thresholds 0.01,0.02] [--gcn]        # also the surface metrics
+    python examples/eval_step.py --volume [--resolution 32] [--gcn]                # also volumetric IoU
 
 The trained networks and the dataset are out of scope; what the loops do with a batch is
 the reference's, under torch.no_grad():
@@ -16,6 +17,9 @@ the reference's, under torch.no_grad():
     --surface     SurfaceEvaluationMeter beside the meter above: F-score at the thresholds, Chamfer-L1 and -L2; with --gcn on
                   points sampled from the refined SURFACE with normal consistency (the stand-in ground-truth normals point away
                   from the origin), without it on the sampled primitive points, which carry no normals
+    --volume      VolumeEvaluationMeter beside them: IoU, precision and recall of the occupied volume on a resolution^3 grid; the
+                  prediction is the primitive assembly's closed-form occupancy (with --gcn the refined mesh's winding number), the
+                  stand-in ground truth a packed batch of ellipsoid meshes
 
 The class indices cycle over the reference's 13 ShapeNet classes; the last batch is short."""
 import argparse
@@ -45,12 +49,23 @@ def batches(n, B):
         seen += b
 
 
+def gt_meshes(b, it, dev):
+    """The stand-in ground truth of --volume: b ellipsoid meshes (semi-axes 0.15 .. 0.35) as one MeshBatch; its own generator,
+    so the other draws of the loop are what they are without the flag."""
+    from vpn_amd.modules.meshing import uv_sphere
+    g = torch.Generator().manual_seed(300 + it)
+    sv, sf = uv_sphere()
+    sv, sf = sv.cpu(), sf.cpu().flip(1)          # the template is wound clockwise seen from outside: flipped, w = +1 inside
+    return vpn_amd.MeshBatch.pack([(sv * (0.15 + 0.2 * torch.rand(3, generator=g)), sf) for _ in range(b)], dev)
+
+
 @torch.no_grad()
 def test(args, dev):
     model = Heads(64, VP_NUM).to(dev).eval()
     kinds = [vpn_amd.SPHERE] * VP_NUM
     meter = vpn_amd.EvaluationMeter(CLASS_NAMES, dev, emd=False, cd_scale=L_VIEW_CD)
     surface = vpn_amd.SurfaceEvaluationMeter(CLASS_NAMES, dev, thresholds=args.thresholds) if args.surface else None
+    volume = vpn_amd.VolumeEvaluationMeter(CLASS_NAMES, dev, resolution=args.resolution) if args.volume else None
     for it, (b, class_indices) in enumerate(batches(args.batches, args.batch)):
         feats = torch.randn(b, 64, device=dev)
         view_points = (torch.rand(b, VP_NUM * SAMPLE_NUM, 3, device=dev) - 0.5) * 0.8
@@ -59,6 +74,8 @@ def test(args, dev):
         meter.update(predict_points, view_points, class_indices)
         if surface is not None:
             surface.update(predict_points, view_points, class_indices)
+        if volume is not None:
+            volume.update_primitives(params, kinds, gt_meshes(b, it, dev), class_indices)
         if args.dump and it % 3 == 0:                                    # test.py:110-124: the K meshes of sample 0
             volumes, rotates, translates = vpn_amd.split_primitives(params)
             vp_meshes = [vpn_amd.Meshing.sphere_meshing(volumes[k][:1], rotates[k][:1], translates[k][:1])[0] for k in range(VP_NUM)]
@@ -67,6 +84,8 @@ def test(args, dev):
     res = meter.report(args.epoch)
     if surface is not None:
         surface.report()
+    if volume is not None:
+        volume.report()
     return res
 
 
@@ -76,6 +95,7 @@ def test_gcn(args, dev):
     gcn = GCNModel(factored_input=args.gcn_input == 'factored', collapse_pairs=args.gcn_collapse).to(dev).eval()
     meter = vpn_amd.EvaluationMeter(CLASS_NAMES, dev, emd=True)
     surface = vpn_amd.SurfaceEvaluationMeter(CLASS_NAMES, dev, thresholds=args.thresholds) if args.surface else None
+    volume = vpn_amd.VolumeEvaluationMeter(CLASS_NAMES, dev, resolution=args.resolution) if args.volume else None
     for it, (b, class_indices) in enumerate(batches(args.batches, args.batch)):
         rgbs = torch.zeros(b, 3, 128, 128, device=dev)
         rgbs[:, :, 24:104, 16:112] = torch.rand(b, 3, 80, 96, device=dev)
@@ -89,12 +109,17 @@ def test_gcn(args, dev):
             gt_normals = torch.nn.functional.normalize(gt_points, dim=-1)
             surface.update_mesh(predict_vertices, predict_meshes[0].faces, gt_points, class_indices, n=gt_points.size(1),
                                 seed=200 + it, gt_normals=gt_normals)
+        if volume is not None:
+            # the composed sphere template is wound clockwise seen from outside; occupancy wants w = +1 inside
+            volume.update_mesh(predict_vertices, predict_meshes[0].faces.flip(1), gt_meshes(b, it, dev), class_indices)
         if args.dump and it % 3 == 0:                                    # test_gcn.py:154-161
             vpn_amd.Visualizer.render_refine_vp_meshes(rgbs[0], vp_meshes[0], predict_vertices[0],
                                                        os.path.join(args.dump, 'refine_%03d.gif' % it))
     res = meter.report(args.epoch)
     if surface is not None:
         surface.report()
+    if volume is not None:
+        volume.report()
     return res
 
 
@@ -114,6 +139,9 @@ def main(argv=None):
                     help='also run SurfaceEvaluationMeter: F-score, Chamfer-L1 / -L2 and (with --gcn) normal consistency')
     ap.add_argument('--thresholds', default=(0.01, 0.02), type=lambda s: tuple(float(t) for t in s.split(',')),
                     help='with --surface: the distance thresholds of the F-score, comma separated (default 0.01,0.02)')
+    ap.add_argument('--volume', action='store_true',
+                    help='also run VolumeEvaluationMeter: volumetric IoU, precision and recall against stand-in ground-truth meshes')
+    ap.add_argument('--resolution', type=int, default=32, help='with --volume: the query grid has resolution^3 cell centres')
     args = ap.parse_args(argv)
     if args.dump:
         os.makedirs(args.dump, exist_ok=True)

@@ -1249,6 +1249,61 @@ int vpn_surfeval_accumulate(const float* dist1, const int32_t* idx1, const float
                             const float* n_gt, const float* thr2, const int32_t* class_index, int B, int N, int M, int T,
                             int num_classes, void* state, float* per_sample, void* stream);
 
+/* ---- volumetric evaluation (csrc/occupancy.hip): occupancy of a primitive assembly and of a triangle mesh at
+ * query points, and the intersection over union of two occupancies per sample with the per-class bookkeeping of an epoch on
+ * the device.  DEVICE pointers.  queries fp32: [Q,3] shared by the batch (shared_queries != 0) or [B,Q,3] (0); both are read by
+ * the same code (a sample stride of 0), so repeating a shared set B times gives the same bits.
+ * vpn_occupancy_prims: one launch.  params fp32 [B,K,VPN_PARAM_STRIDE], kinds int32 [K].  Per primitive x~ = R^T (x - t) / v, R
+ *   from q as the sampler and the raster form it, v the half-extents; m = x~.x~ (VPN_SPHERE) or max |x~_i| (any other kind: a
+ *   cuboid); inside iff m <= 1, every operation in fp32 and rounded by itself; a NaN is outside.  occ uint8 [B,Q] = 0 / 1, the
+ *   OR over k; owner int32 [B,Q] = the lowest k that holds the point, -1 for none.  occ or owner may be NULL: not written.
+ * vpn_winding_number: three launches (face records, the scan over (256-query tile, face slice, sample), the merge).  The
+ *   generalized winding number w = sum_f 2 atan2(a . (b x c), |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|) / 4 pi with a, b, c the
+ *   corners of face f minus x (Van Oosterom and Strackee), the terms in fp32 and exactly 0 where the numerator is 0 (a face of no
+ *   area, a query on the face's plane or on a vertex), the sum in fp64 in ONE order (ascending faces within a slice, ascending
+ *   slices), divided by 4 pi in fp64 and rounded to fp32 once.  A face with a vertex index outside its mesh adds nothing and reads
+ *   nothing out of range, nor does a face whose edge cross product (v1 - v0) x (v2 - v0) is (0,0,0) in fp32; a live face with a corner that is not finite, or a query that is not finite, makes w NaN.
+ *   batched layout (vert_offset and face_offset NULL): verts fp32 [B,P,3], ONE faces int32 [F,3]; max_faces is not used.
+ *   ragged layout (both given; a packed mesh batch): verts [P,3] with P = sumP, faces [F,3] with F = sumF and MESH-LOCAL vertex
+ *     indices, vert_offset / face_offset int32 [B+1]; sample b is mesh b.  max_faces: the largest face count of a mesh, known
+ *     on the host (1 .. F); it sizes the grid only: a mesh with more faces is still summed whole, by its last slice.  An
+ *     offset entry that does not describe the packed arrays names no face.
+ *   xforms fp32 [B,3,4] or NULL: affine rows applied to the corners first, as vpn_face_normals_at does; a map of negative
+ *     determinant negates w.
+ *   w fp32 [B,Q] and occ uint8 [B,Q] = (w > 0.5, on the rounded value; NaN is outside) may each be NULL (not both).
+ *   workspace: at least vpn_winding_workspace(B, Q, F, ragged, max_faces) bytes (0: rejected shapes), 16-byte aligned.
+ *   vpn_winding_plan returns the number of face slices (or a negative code) and writes the faces per slice: a function of (B,
+ *   Q, max_faces) alone (about 1024 workgroups, a slice of at least VPN_WINDING_MIN_SLICE faces but for the last, at most
+ *   VPN_WINDING_MAX_SLICES slices), so a shape always adds in the same order.
+ * vpn_voliou_accumulate: two launches (one workgroup per sample, then ONE workgroup for the bookkeeping).  occ_pred, occ_gt
+ *   uint8 [B,Q] (non-zero = inside); class_index int32 [B].  Writes counts int32 [B,4] = (I = #and, U = #or, Np, Ng) and rows
+ *   fp32 [B,VPN_VOLIOU_WIDTH] = (iou I / U, precision I / Np, recall I / Ng, vol_pred Np / Q, vol_gt Ng / Q), each quotient
+ *   formed in fp64 from the integers and rounded once, 0 where its denominator is 0.
+ *   state: vpn_voliou_state_size(C) bytes (0: rejected sizes), 8-byte aligned, ZEROED BY THE CALLER before the first batch of
+ *   an epoch: (1 + C) W doubles -- total[W], then class_sum[C][W] -- followed by 4 + C int64 -- n_samples, n_batches, n_empty
+ *   (samples with U = 0), n_invalid, class_n[C].  Sums in sample order in fp64, totals SAMPLE-weighted, a class index outside
+ *   [0, C) enters the totals and n_invalid only, two states merge by adding: the rules of vpn_surfeval_accumulate.
+ * Nothing is allocated, no host synchronisation, no atomics, capturable, bit-equal from run to run.  A null pointer (xforms
+ * may be NULL; occ / owner and w / occ as said), a non-positive size, one offset table without the other, max_faces outside 1 ..
+ * F in the ragged layout, a workspace that is short or misaligned, a misaligned state: VPN_E_BADARG.  B > 65535, Q, P, F or C
+ * above VPN_OCCUPANCY_MAX_ITEMS, K > VPN_MAX_PRIMS: VPN_E_TOOBIG.  All before any HIP call.  Added without a change of
+ * VPN_ABI_VERSION. */
+#define VPN_OCCUPANCY_TILE 256           /* queries per workgroup */
+#define VPN_OCCUPANCY_MAX_ITEMS 16777216
+#define VPN_WINDING_MIN_SLICE 128        /* a face slice of the winding scan has at least this many faces (but for the last) */
+#define VPN_WINDING_MAX_SLICES 64
+#define VPN_VOLIOU_WIDTH 5
+int vpn_occupancy_prims(const float* params, const int32_t* kinds, const float* queries, int shared_queries, int B, int K, int Q,
+                        uint8_t* occ, int32_t* owner, void* stream);
+int vpn_winding_plan(int B, int Q, int max_faces, int* slice_faces);
+size_t vpn_winding_workspace(int B, int Q, int F, int ragged, int max_faces);
+int vpn_winding_number(const float* verts, const int32_t* faces, const int32_t* vert_offset, const int32_t* face_offset,
+                       const float* xforms, const float* queries, int shared_queries, int B, int Q, int P, int F, int max_faces,
+                       void* workspace, size_t workspace_bytes, float* w, uint8_t* occ, void* stream);
+size_t vpn_voliou_state_size(int num_classes);
+int vpn_voliou_accumulate(const uint8_t* occ_pred, const uint8_t* occ_gt, const int32_t* class_index, int B, int Q, int num_classes,
+                          void* state, float* rows, int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

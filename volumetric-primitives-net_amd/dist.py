@@ -132,3 +132,20 @@ def all_reduce_surfeval_state(state, C, T, group=None):
     out[:nd].copy_(buf[:nd])
     out[nd:].view(torch.int64).copy_(buf[nd:].round().to(torch.int64))
     return out
+
+
+def all_reduce_voliou_state(state, C, group=None):
+    """all_reduce_eval_state for the state of the volumetric evaluation (VolumeEvaluationMeter; (1 + C) 5 float64 sums, then
+    4 + C int64 counts in one float64 tensor): the sum over the ranks of `group`, on every rank, by ONE all-reduce.  Returns a
+    new tensor; `state` is left as it is."""
+    nd = (1 + C) * 5
+    if state.dtype != torch.float64 or state.numel() != nd + 4 + C:
+        raise ValueError('not a volumetric evaluation state of %d classes' % C)
+    if not dist.is_initialized():
+        raise RuntimeError('all_reduce_voliou_state needs an initialised process group')
+    buf = torch.cat([state[:nd], state[nd:].view(torch.int64).to(torch.float64)])
+    dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+    out = torch.empty_like(state)
+    out[:nd].copy_(buf[:nd])
+    out[nd:].view(torch.int64).copy_(buf[nd:].round().to(torch.int64))
+    return out

@@ -15,7 +15,7 @@ from .augmentation import (cut_mix_data, cut_mix_batch_points, adjust_point_num,
                            points_to_meshes_and_colors, points_to_mesh_batch, meshes_to_imgs, generate_point_mixup_data,
                            acd, augment, acd_mix_meshes, acd_mix_data)
 from . import evaluation
-from .evaluation import EvaluationMeter, SurfaceEvaluationMeter
+from .evaluation import EvaluationMeter, SurfaceEvaluationMeter, VolumeEvaluationMeter
 from . import visualize
 from .visualize import Visualizer
 from . import optim

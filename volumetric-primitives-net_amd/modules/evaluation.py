@@ -22,7 +22,11 @@ The visual dumps of the evaluation scripts (Visualizer.render_*, test.py:110-124
 
 SurfaceEvaluationMeter (csrc/surfeval.hip) is the same kind of meter for the metrics the reference does not
 report: Chamfer-L2 / -L1, precision / recall / F-score at distance thresholds and normal consistency on points sampled from
-the predicted SURFACE, which, unlike the vertices, see a triangle that cuts through empty space."""
+the predicted SURFACE, which, unlike the vertices, see a triangle that cuts through empty space.
+
+VolumeEvaluationMeter (csrc/occupancy.hip) is the meter for volumetric IoU: the prediction -- a primitive
+assembly with its closed-form inside test, or a triangle mesh through its generalized winding number -- and the ground-truth
+mesh are asked "is x inside" on one grid of query points, and the occupied sets are compared per sample."""
 import math
 
 import torch
@@ -293,6 +297,156 @@ class SurfaceEvaluationMeter:
             line('total', lambda k: res[k])
         else:
             print('total \t\tno samples')
+        if res['n_invalid']:
+            print('n_invalid = %d (class index outside [0, %d): in the total, in no class)' % (res['n_invalid'], self.C))
+        return res
+
+
+class VolumeEvaluationMeter:
+    """Per-class volumetric IoU of an evaluation epoch, kept on the device (csrc/occupancy.hip):
+
+        meter = VolumeEvaluationMeter(class_names, device, resolution=32)
+        for data in dataloader:
+            ...
+            meter.update_primitives(params, kinds, gt_batch, data['class_index'], gt_xforms=view)
+        meter.report(epoch)
+
+    The prediction and the ground truth are asked "is x inside" at the same query points -- by default the resolution^3 cell
+    centres of the cube `bounds`^3 (ops.grid_queries), or any `queries` fp32 [Q,3] -- and compared per sample:
+        iou = #(pred and gt) / #(pred or gt), precision = #and / #pred, recall = #and / #gt, vol_pred = #pred / Q, vol_gt = #gt / Q
+    each 0 where its denominator is 0; a sample whose union is empty counts in n_empty.  A primitive assembly is inside where
+    any primitive's closed-form test holds (ops.primitive_occupancy); a triangle mesh where its generalized winding number
+    exceeds 0.5 (ops.mesh_occupancy), which also serves meshes with holes and overlapping closed components.
+
+    Like SurfaceEvaluationMeter, `update` makes no host synchronisation, can be captured into a HIP graph and is bit-equal
+    from run to run; `result` is the ONE device-to-host copy of an epoch; the totals are SAMPLE-weighted; a class index
+    outside [0, C) enters the totals, no class, and n_invalid."""
+
+    def __init__(self, class_names, device, resolution=32, bounds=(-0.5, 0.5), queries=None):
+        self.class_names = [str(c) for c in class_names]
+        if not self.class_names:
+            raise ValueError('VolumeEvaluationMeter needs at least one class name')
+        self.C = len(self.class_names)
+        self.device = torch.device(device)
+        self.W = ops.VOLIOU_WIDTH
+        if queries is None:
+            self.resolution, self.bounds = int(resolution), (float(bounds[0]), float(bounds[1]))
+            self.queries = ops.grid_queries(self.resolution, self.bounds[0], self.bounds[1], self.device)
+        else:
+            if (not isinstance(queries, torch.Tensor) or queries.dim() != 2 or queries.shape[1] != 3 or queries.shape[0] < 1
+                    or queries.dtype != torch.float32):
+                raise ValueError('queries must be a float32 tensor [Q,3], got %r' % (tuple(getattr(queries, 'shape', ())),))
+            self.resolution, self.bounds = None, None
+            self.queries = queries.detach().to(self.device).contiguous()
+        self.state = ops.voliou_state(self.C, self.device)
+
+    _class_index = EvaluationMeter._class_index
+
+    @torch.no_grad()
+    def update(self, occ_pred, occ_gt, class_indices):
+        """One batch of occupancies uint8 [B,Q] on the device (non-zero = inside), class_indices [B] (a device tensor, a CPU
+        tensor or a list).  Returns (rows [B,5] = iou, precision, recall, vol_pred, vol_gt; counts int32 [B,4] = and, or,
+        prediction, ground truth) as device tensors."""
+        if not (isinstance(occ_pred, torch.Tensor) and isinstance(occ_gt, torch.Tensor) and occ_pred.dim() == 2):
+            raise ValueError('occ_pred and occ_gt uint8 [B,Q] expected')
+        if not (occ_pred.is_cuda and occ_gt.is_cuda):
+            raise RuntimeError('vpn_amd operators run on the GPU only (got a %s tensor); there is no CPU path'
+                               % occ_pred.device.type)
+        return ops.voliou_step(occ_pred, occ_gt, self._class_index(class_indices, occ_pred.size(0)), self.state, self.C)
+
+    def _gt_occupancy(self, gt_batch, gt_xforms, B):
+        if not hasattr(gt_batch, 'face_counts'):
+            raise TypeError('gt_batch must be a MeshBatch (MeshBatch.pack / MeshBatch.from_objs)')
+        if len(gt_batch) != B:
+            raise ValueError('%d ground-truth meshes for a batch of %d' % (len(gt_batch), B))
+        return ops.mesh_occupancy(gt_batch, None, self.queries, gt_xforms)
+
+    @torch.no_grad()
+    def update_primitives(self, params, kinds, gt_batch, class_indices, gt_xforms=None):
+        """One batch of predicted primitive assemblies: params [B,K,10], kinds [K]; gt_batch: a MeshBatch of B ground-truth
+        meshes, gt_xforms [B,3,4] the affine map that brings them into the prediction's frame (view_center_xforms).
+        ops.primitive_occupancy, ops.mesh_occupancy on the meter's queries, then `update`."""
+        if not (isinstance(params, torch.Tensor) and params.dim() == 3):
+            raise ValueError('params [B,K,10] expected')
+        occ_gt = self._gt_occupancy(gt_batch, gt_xforms, params.size(0))
+        occ_pred = ops.primitive_occupancy(params.detach().float(), kinds, self.queries)
+        return self.update(occ_pred, occ_gt, class_indices)
+
+    @torch.no_grad()
+    def update_mesh(self, verts, faces, gt_batch, class_indices, gt_xforms=None):
+        """One batch of predicted MESHES: verts [B,P,3], one faces [F,3] for the batch; the ground truth as in
+        update_primitives.  ops.mesh_occupancy for both, then `update`.  Faces are wound counter-clockwise seen from outside
+        (w = +1 inside); a mesh wound the other way has w = -1 inside and holds no point: pass faces.flip(1), as
+        examples/eval_step.py does for the uv_sphere template."""
+        if not (isinstance(verts, torch.Tensor) and verts.dim() == 3 and verts.size(-1) == 3):
+            raise ValueError('verts [B,P,3] expected')
+        occ_gt = self._gt_occupancy(gt_batch, gt_xforms, verts.size(0))
+        occ_pred = ops.mesh_occupancy(verts.detach().float(), faces, self.queries)
+        return self.update(occ_pred, occ_gt, class_indices)
+
+    def reset(self):
+        self.state.zero_()
+
+    def load_state(self, state):
+        """Replace the meter's state by a copy of `state` (a state tensor of the same number of classes, any device)."""
+        ops.voliou_state_fields(state, self.C)
+        self.state.copy_(state)
+
+    @staticmethod
+    def merge(state_a, state_b):
+        """The state of two evaluations taken together: the field-wise sum of two state tensors of the same classes (sums
+        as float64, counts as int64).  What result(group=...) does across ranks, without a process group; works on CPU
+        tensors.  The number of classes follows from the size."""
+        W = ops.VOLIOU_WIDTH
+        if state_a.shape != state_b.shape or state_a.dim() != 1 or state_a.numel() < 2 * W + 5 or (state_a.numel() - 4 - W) % (W + 1):
+            raise ValueError('merge needs two volumetric evaluation states of the same number of classes')
+        C = (state_a.numel() - 4 - W) // (W + 1)
+        out = torch.empty_like(state_a)
+        (sa, na), (sb, nb), (so, no) = (ops.voliou_state_fields(t, C) for t in (state_a, state_b.to(state_a.device), out))
+        torch.add(sa, sb, out=so)
+        torch.add(na, nb, out=no)
+        return out
+
+    def result(self, group=None):
+        """The epoch so far as plain Python.  Epoch figures 'iou', 'precision', 'recall', 'vol_pred', 'vol_gt' (None without
+        samples); per class the same keys as 'class_*' lists, None for a class that never occurred; 'class_n', 'n_samples',
+        'n_batches', 'n_empty', 'n_invalid'.  group: a torch.distributed process group whose ranks each evaluated a shard:
+        their states are summed by one all-reduce first.  One device-to-host copy."""
+        state = self.state if group is None else vdist.all_reduce_voliou_state(self.state, self.C, group)
+        sums, counts = ops.voliou_state_fields(state.cpu(), self.C)
+        sums, counts = sums.tolist(), counts.tolist()
+        C, W, keys = self.C, self.W, ops.VOLIOU_COLUMNS
+        n_samples, n_batches, n_empty, n_invalid, class_n = counts[0], counts[1], counts[2], counts[3], counts[4:]
+        figures = lambda row, n: [v / n for v in row] if n else None
+        total = figures(sums[:W], n_samples)
+        per_class = [figures(sums[(1 + c) * W:(2 + c) * W], class_n[c]) for c in range(C)]
+        res = {k: None if total is None else total[i] for i, k in enumerate(keys)}
+        for i, k in enumerate(keys):
+            res['class_' + k] = [None if f is None else f[i] for f in per_class]
+        res.update(class_n=class_n, n_samples=n_samples, n_batches=n_batches, n_empty=n_empty, n_invalid=n_invalid)
+        return res
+
+    def report(self, epoch=None, group=None):
+        """Prints one line per class that occurred, then the total; a line each for n_empty and n_invalid when not zero.
+        Returns result()."""
+        res = self.result(group)
+        head = '\nEpoch %d\n' % epoch if epoch is not None else ''
+        print(head + '=' * 30)
+
+        def line(name, get):
+            print('%s \t\tvolume iou = %.4f (P %.4f, R %.4f), vol_pred = %.4f, vol_gt = %.4f'
+                  % (name, get('iou'), get('precision'), get('recall'), get('vol_pred'), get('vol_gt')))
+
+        for i, name in enumerate(self.class_names):
+            if res['class_n'][i]:
+                line(name, lambda k, i=i: res['class_' + k][i])
+        print('=' * 30)
+        if res['n_samples']:
+            line('total', lambda k: res[k])
+        else:
+            print('total \t\tno samples')
+        if res['n_empty']:
+            print('n_empty = %d (neither the prediction nor the ground truth holds a query point: iou 0)' % res['n_empty'])
         if res['n_invalid']:
             print('n_invalid = %d (class index outside [0, %d): in the total, in no class)' % (res['n_invalid'], self.C))
         return res

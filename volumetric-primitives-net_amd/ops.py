@@ -2408,6 +2408,241 @@ def surfeval_step(predict_points, gt_points, class_index, state, C, thr2, predic
     return per_sample
 
 
+# ---- volumetric evaluation (csrc/occupancy.hip): occupancy of a primitive assembly and of a triangle mesh at
+# query points, volumetric IoU per sample and its bookkeeping.  Plain functions: reported values, nothing is differentiable.
+
+OCCUPANCY_MAX_ITEMS = _H['VPN_OCCUPANCY_MAX_ITEMS']
+VOLIOU_WIDTH = _H['VPN_VOLIOU_WIDTH']
+VOLIOU_COLUMNS = ('iou', 'precision', 'recall', 'vol_pred', 'vol_gt')
+
+
+def grid_queries(R, lo=-0.5, hi=0.5, device=None):
+    """The R^3 cell centres of the cube [lo, hi]^3 as fp32 [R^3,3]: index (iz R + iy) R + ix, coordinate lo + (i + 0.5) (hi -
+    lo) / R formed in float64 and rounded once.  device None: a host tensor."""
+    R, lo, hi = int(R), float(lo), float(hi)
+    if R < 1 or R ** 3 > OCCUPANCY_MAX_ITEMS:
+        raise ValueError('grid_queries: the resolution must be 1 .. %d, got %d' % (int(round(OCCUPANCY_MAX_ITEMS ** (1 / 3))), R))
+    if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi):
+        raise ValueError('grid_queries: bounds must be finite with lo < hi, got (%r, %r)' % (lo, hi))
+    c = lo + (torch.arange(R, dtype=torch.float64) + 0.5) * (hi - lo) / R
+    z, y, x = torch.meshgrid(c, c, c, indexing='ij')
+    q = torch.stack([x, y, z], -1).reshape(-1, 3).float().contiguous()
+    if device is None or torch.device(device).type != 'cuda':
+        return q
+    return q.pin_memory().to(device, non_blocking=True)
+
+
+def _queries_check(name, queries, B, dev):
+    """queries fp32 [Q,3] (shared by the batch) or [B,Q,3] on `dev` -> (contiguous tensor, shared flag, Q)."""
+    if (not isinstance(queries, torch.Tensor) or queries.dim() not in (2, 3) or queries.shape[-1] != 3 or min(queries.shape) < 1
+            or queries.dtype != torch.float32):
+        raise ValueError('%s: queries must be float32 [Q,3] or [B,Q,3], got %s %r'
+                         % (name, getattr(queries, 'dtype', None), tuple(getattr(queries, 'shape', ()))))
+    if queries.dim() == 3 and queries.shape[0] != B:
+        raise ValueError('%s: queries [B,Q,3] must have B = %d, got %d' % (name, B, queries.shape[0]))
+    Q = int(queries.shape[-2])
+    if B > 65535 or Q > OCCUPANCY_MAX_ITEMS:
+        raise ValueError('%s: at most 65535 samples of %d queries, got B = %d, Q = %d' % (name, OCCUPANCY_MAX_ITEMS, B, Q))
+    if queries.device != dev:
+        raise ValueError('%s: queries must be on %s, got %s' % (name, dev, queries.device))
+    return queries.detach().contiguous(), int(queries.dim() == 2), Q
+
+
+def _gpu_only(t):
+    if not t.is_cuda:
+        raise RuntimeError('vpn_amd operators run on the GPU only (got a %s tensor); there is no CPU path' % t.device.type)
+
+
+@torch.no_grad()
+def primitive_occupancy(params, kinds, queries, owner=False):
+    """Occupancy of the union of K primitives at query points (vpn_occupancy_prims, one launch): params [B,K,10] fp32 (v, q, t
+    as the sampler reads them), kinds [K] (a list or a device tensor), queries fp32 [Q,3] shared by the batch or [B,Q,3] ->
+    occ uint8 [B,Q] (1 inside); owner=True: (occ, owner int32 [B,Q]), the lowest primitive that holds the point, -1 for
+    none.  A point is inside primitive k iff m <= 1 with x~ = R^T (x - t) / v and m = x~.x~ (sphere) or max |x~_i| (cuboid);
+    a NaN is outside.  No host synchronisation; everything is validated before the launch."""
+    if (not isinstance(params, torch.Tensor) or params.dim() != 3 or params.shape[2] != PARAM_STRIDE or min(params.shape) < 1
+            or params.dtype != torch.float32):
+        raise ValueError('primitive_occupancy: params must be float32 [B,K,%d], got %s %r'
+                         % (PARAM_STRIDE, getattr(params, 'dtype', None), tuple(getattr(params, 'shape', ()))))
+    B, K = int(params.shape[0]), int(params.shape[1])
+    if K > _H['VPN_MAX_PRIMS']:
+        raise ValueError('primitive_occupancy: at most %d primitives, got %d' % (_H['VPN_MAX_PRIMS'], K))
+    n_kinds = kinds.numel() if isinstance(kinds, torch.Tensor) else len(kinds)
+    if n_kinds != K:
+        raise ValueError('primitive_occupancy: %d kinds for %d primitives' % (n_kinds, K))
+    if not isinstance(kinds, torch.Tensor):
+        _check_kinds(tuple(int(k) for k in kinds))
+    q, shared, Q = _queries_check('primitive_occupancy', queries, B, params.device)
+    _gpu_only(params)
+    dev = params.device
+    kt = kinds_tensor(kinds, dev)
+    occ = torch.empty((B, Q), dtype=torch.uint8, device=dev)
+    own = torch.empty((B, Q), dtype=torch.int32, device=dev) if owner else None
+    _lib.call('vpn_occupancy_prims', params.detach().contiguous(), kt, q, shared, B, K, Q, occ, own, _lib.stream())
+    return (occ, own) if owner else occ
+
+
+def winding_plan(B, Q, max_faces):
+    """(slices, faces per slice) of the winding scan for B samples of Q queries against meshes of at most max_faces faces
+    (vpn_winding_plan): a function of the three numbers alone."""
+    slice_faces = ctypes.c_int(0)
+    slices = _lib.lib().vpn_winding_plan(int(B), int(Q), int(max_faces), ctypes.byref(slice_faces))
+    if slices < 0:
+        raise ValueError('winding_plan: rejected shape B = %d, Q = %d, max_faces = %d' % (B, Q, max_faces))
+    return slices, slice_faces.value
+
+
+def _winding_launch(name, verts, faces, vert_offset, face_offset, max_faces, queries, xforms, B, want_w, want_occ):
+    dev = verts.device
+    q, shared, Q = _queries_check(name, queries, B, dev)
+    if xforms is not None and tuple(getattr(xforms, 'shape', ())) != (B, 3, 4):
+        raise ValueError('%s: xforms must be %r, got %r' % (name, (B, 3, 4), tuple(getattr(xforms, 'shape', ()))))
+    _gpu_only(verts)
+    P, F =int(verts.shape[-2]), int(faces.shape[0])
+    if xforms is not None:
+        xforms = _draw_tensor('xforms', xforms, (B, 3, 4), torch.float32, dev)
+    ragged = int(vert_offset is not None)
+    ws = _workspace('vpn_winding_workspace', B, Q, F, ragged, int(max_faces), dev=dev, dtype=torch.float64)
+    w = torch.empty((B, Q), dtype=torch.float32, device=dev) if want_w else None
+    occ = torch.empty((B, Q), dtype=torch.uint8, device=dev) if want_occ else None
+    _lib.call('vpn_winding_number', verts.detach().contiguous(), faces_i32(faces, dev), vert_offset, face_offset, xforms, q, shared,
+              B, Q, P, F, int(max_faces), ws, ws.numel() * 8, w, occ, _lib.stream())
+    return w, occ
+
+
+def _winding_batched(name, verts, faces, queries, xforms, want_w, want_occ):
+    if (not isinstance(verts, torch.Tensor) or verts.dim() != 3 or verts.shape[2] != 3 or min(verts.shape) < 1
+            or verts.dtype != torch.float32):
+        raise ValueError('%s: verts must be float32 [B,P,3], got %s %r'
+                         % (name, getattr(verts, 'dtype', None), tuple(getattr(verts, 'shape', ()))))
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise ValueError('%s: faces must be [F,3], one topology for the batch, got %r' % (name, tuple(getattr(faces, 'shape', ()))))
+    if faces.dtype not in (torch.int32, torch.int64):
+        raise ValueError('%s: faces must be int32 or int64, got %s' % (name, faces.dtype))
+    if max(verts.shape[1], faces.shape[0]) > OCCUPANCY_MAX_ITEMS:
+        raise ValueError('%s: at most %d vertices or faces' % (name, OCCUPANCY_MAX_ITEMS))
+    return _winding_launch(name, verts, faces, None, None, faces.shape[0], queries, xforms, int(verts.shape[0]), want_w, want_occ)
+
+
+def _winding_ragged(name, batch, queries, xforms, want_w, want_occ):
+    """batch: a MeshBatch on the device, or (verts [sumP,3], faces [sumF,3] mesh-local, vert_offset [S+1], face_offset [S+1],
+    max_faces) with the largest face count of a mesh as a host number."""
+    if hasattr(batch, 'face_counts'):
+        if batch.verts is None:
+            raise RuntimeError('vpn_amd operators run on the GPU only: pack the MeshBatch with a device; there is no CPU path')
+        verts, faces, vert_offset, face_offset, max_faces = (batch.verts, batch.faces, batch.vert_offset, batch.face_offset,
+                                                             max(batch.face_counts))
+    else:
+        try:
+            verts, faces, vert_offset, face_offset, max_faces = batch
+        except (TypeError, ValueError):
+            raise ValueError('%s: a MeshBatch or (verts, faces, vert_offset, face_offset, max_faces) expected' % name)
+    if (not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] < 1
+            or verts.dtype != torch.float32):
+        raise ValueError('%s: verts must be float32 [sumP,3], got %s %r'
+                         % (name, getattr(verts, 'dtype', None), tuple(getattr(verts, 'shape', ()))))
+    if (not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1
+            or faces.dtype not in (torch.int32, torch.int64)):
+        raise ValueError('%s: faces must be int32 or int64 [sumF,3], got %r' % (name, tuple(getattr(faces, 'shape', ()))))
+    for what, t in (('vert_offset', vert_offset), ('face_offset', face_offset)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.numel() < 2:
+            raise ValueError('%s: %s must be an int32 tensor of S + 1 entries' % (name, what))
+    S = vert_offset.numel() - 1
+    if face_offset.numel() != S + 1:
+        raise ValueError('%s: the two offset tables must have S + 1 entries each' % name)
+    max_faces = int(max_faces)
+    if not 1 <= max_faces <= faces.shape[0]:
+        raise ValueError('%s: max_faces must be 1 .. %d (the largest face count of a mesh), got %d' % (name, faces.shape[0], max_faces))
+    if max(verts.shape[0], faces.shape[0]) > OCCUPANCY_MAX_ITEMS:
+        raise ValueError('%s: at most %d vertices or faces' % (name, OCCUPANCY_MAX_ITEMS))
+    if verts.is_cuda and not (vert_offset.is_cuda and face_offset.is_cuda):
+        raise ValueError('%s: the offset tables must be on the device' % name)
+    return _winding_launch(name, verts, faces, vert_offset.contiguous(), face_offset.contiguous(), max_faces, queries, xforms, S,
+                           want_w, want_occ)
+
+
+@torch.no_grad()
+def winding_number(verts, faces, queries, xforms=None):
+    """The generalized winding number of the meshes verts [B,P,3] fp32 over ONE faces [F,3] (int32 or int64, host or device) at
+    queries fp32 [Q,3] (shared) or [B,Q,3] -> w fp32 [B,Q] (vpn_winding_number, the batched layout): 1 inside a closed
+    outward-oriented surface, 0 outside, 2 where two closed components overlap, a fraction near a hole.  xforms [B,3,4]:
+    affine rows applied to the corners first; a reflection negates w.  A face of no area, a query on a face's plane or on a
+    vertex and a face with a vertex index outside [0,P) add exactly 0; a coordinate that is not finite gives NaN.  Three
+    launches, no host synchronisation; everything is validated before them."""
+    return _winding_batched('winding_number', verts, faces, queries, xforms, True, False)[0]
+
+
+@torch.no_grad()
+def ragged_winding_number(batch_or_arrays, queries, xforms=None):
+    """winding_number for the packed meshes of a MeshBatch (or the arrays (verts [sumP,3], faces [sumF,3] mesh-local,
+    vert_offset, face_offset [S+1] int32 on the device, max_faces)): sample b is mesh b, queries [Q,3] or [S,Q,3], xforms
+    [S,3,4] -> w [S,Q].  The grid follows from the face counts the host knows: nothing is read back."""
+    return _winding_ragged('ragged_winding_number', batch_or_arrays, queries, xforms, True, False)[0]
+
+
+@torch.no_grad()
+def mesh_occupancy(verts_or_batch, faces, queries, xforms=None):
+    """Occupancy of triangle meshes at query points: uint8 [B,Q], 1 where the winding number (as fp32) exceeds 0.5; NaN is
+    outside.  Batched layout: mesh_occupancy(verts [B,P,3], faces [F,3], queries); ragged layout: mesh_occupancy(batch, None,
+    queries) with a MeshBatch or the arrays ragged_winding_number takes."""
+    if faces is None:
+        return _winding_ragged('mesh_occupancy', verts_or_batch, queries, xforms, False, True)[1]
+    return _winding_batched('mesh_occupancy', verts_or_batch, faces, queries, xforms, False, True)[1]
+
+
+def voliou_state(C, device):
+    """A zeroed state of the volumetric evaluation for C classes (include/vpn_hip.h, vpn_voliou_accumulate): one float64 tensor
+    of (1 + C) 5 + 4 + C elements, the last 4 + C of which hold int64 bit patterns (voliou_state_fields splits it)."""
+    nbytes = _lib.lib().vpn_voliou_state_size(int(C))
+    if nbytes == 0:
+        raise ValueError('the volumetric evaluation state needs 1 .. %d classes, got %d' % (OCCUPANCY_MAX_ITEMS, int(C)))
+    return torch.zeros((nbytes // 8,), dtype=torch.float64, device=device)
+
+
+def voliou_state_fields(state, C):
+    """Views of a state tensor (any device): (sums float64 [(1 + C) 5]: total[5] then class_sum[C][5]; counts int64 [4 + C]:
+    n_samples, n_batches, n_empty, n_invalid, class_n[C])."""
+    nd = (1 + int(C)) * VOLIOU_WIDTH
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.float64 or state.dim() != 1 or state.numel() != nd + 4 + C:
+        raise ValueError('not a volumetric evaluation state of %d classes' % C)
+    return state[:nd], state[nd:].view(torch.int64)
+
+
+@torch.no_grad()
+def voliou_step(occ_pred, occ_gt, class_index, state, C):
+    """One batch of the volumetric evaluation (vpn_voliou_accumulate, two launches): occ_pred, occ_gt uint8 [B,Q] on the
+    device (non-zero = inside), class_index [B] int32 on the device, state from voliou_state.  Writes the per-sample rows
+    and adds the batch to `state`.  No host synchronisation; everything is validated before a launch.
+    -> (rows fp32 [B,5] = iou, precision, recall, vol_pred, vol_gt; counts int32 [B,4] = and, or, prediction, ground truth)."""
+    for what, t in (('occ_pred', occ_pred), ('occ_gt', occ_gt)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or min(t.shape) < 1 or t.dtype != torch.uint8:
+            raise ValueError('voliou_step: %s must be uint8 [B,Q], got %s %r'
+                             % (what, getattr(t, 'dtype', None), tuple(getattr(t, 'shape', ()))))
+    if occ_pred.shape != occ_gt.shape:
+        raise ValueError('voliou_step: occ_pred and occ_gt must have one shape, got %r and %r'
+                         % (tuple(occ_pred.shape), tuple(occ_gt.shape)))
+    B, Q = int(occ_pred.shape[0]), int(occ_pred.shape[1])
+    if not isinstance(class_index, torch.Tensor) or class_index.numel() != B:
+        raise ValueError('voliou_step: occupancies and class indices must agree on the batch size')
+    if class_index.dtype != torch.int32:
+        raise ValueError('class_index must be an int32 tensor on the device')
+    if B > 65535 or Q > OCCUPANCY_MAX_ITEMS:
+        raise ValueError('voliou_step: at most 65535 samples of %d queries, got B = %d, Q = %d' % (OCCUPANCY_MAX_ITEMS, B, Q))
+    voliou_state_fields(state, C)
+    _gpu_only(occ_pred)
+    dev = occ_pred.device
+    for what, t in (('occ_gt', occ_gt), ('class_index', class_index), ('state', state)):
+        if t.device != dev:
+            raise ValueError('voliou_step: %s must be on %s, got %s' % (what, dev, t.device))
+    if not state.is_contiguous():
+        raise ValueError('voliou_step: the state must be contiguous')
+    rows = torch.empty((B, VOLIOU_WIDTH), dtype=torch.float32, device=dev)
+    counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    _lib.call('vpn_voliou_accumulate', occ_pred.contiguous(), occ_gt.contiguous(), class_index.reshape(-1).contiguous(), B, Q, int(C),
+              state, rows, counts, _lib.stream())
+    return rows, counts
+
+
 # ---- the visualisation stage (csrc/visualize.hip; modules/visualize/render.py:13-24).  Plain functions: a picture has no
 # gradient.
 
