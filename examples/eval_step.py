@@ -6,6 +6,7 @@
     python examples/eval_step.py --dump DIR [--three-elev] [--gcn]  # also write the visual dump of sample 0 every third batch
     python examples/eval_step.py --surface [--thresholds 0.01,0.02] [--gcn]        # also the surface metrics
     python examples/eval_step.py --volume [--resolution 32] [--gcn]                # also volumetric IoU
+    python examples/eval_step.py --surface --outer [--outer-resolution 64] [--gcn] # the surface metrics on the OUTER surface (4.30)
 
 The trained networks and the dataset are out of scope; what the loops do with a batch is
 the reference's, under torch.no_grad():
@@ -17,6 +18,11 @@ the reference's, under torch.no_grad():
     --surface     SurfaceEvaluationMeter beside the meter above: F-score at the thresholds, Chamfer-L1 and -L2; with --gcn on
                   points sampled from the refined SURFACE with normal consistency (the stand-in ground-truth normals point away
                   from the origin), without it on the sampled primitive points, which carry no normals
+    --outer       with --surface: the points are drawn from the boundary of the UNION instead: without --gcn
+                  SurfaceEvaluationMeter.update_primitives (the primitive field's zero level on an outer-resolution^3 lattice), with
+                  it the zero level of the refined mesh's signed distance (ops.mesh_signed_distance -> ops.isosurface ->
+                  update_surface); no point lies on a wall inside another primitive.  With --dump sample 0's union mesh is saved
+                  as an OBJ file
     --volume      VolumeEvaluationMeter beside them: IoU, precision and recall of the occupied volume on a resolution^3 grid; the
                   prediction is the primitive assembly's closed-form occupancy (with --gcn the refined mesh's winding number), the
                   stand-in ground truth a packed batch of ellipsoid meshes
@@ -72,7 +78,13 @@ def test(args, dev):
         params = vpn_amd.pack_head_outputs(*model(feats))
         predict_points = vpn_amd.Sampling.sample_primitives(params, kinds, SAMPLE_NUM, seed=100 + it)
         meter.update(predict_points, view_points, class_indices)
-        if surface is not None:
+        if surface is not None and args.outer:
+            surface.update_primitives(params, kinds, view_points, class_indices, resolution=args.outer_resolution,
+                                      n=VP_NUM * SAMPLE_NUM, seed=100 + it)
+            if args.dump and it % 3 == 0:
+                union = vpn_amd.Meshing.union_meshes(params[:1], kinds, resolution=args.outer_resolution)
+                union.meshes()[0].save_mesh(os.path.join(args.dump, 'union_%03d.obj' % it))
+        elif surface is not None:
             surface.update(predict_points, view_points, class_indices)
         if volume is not None:
             volume.update_primitives(params, kinds, gt_meshes(b, it, dev), class_indices)
@@ -105,7 +117,16 @@ def test_gcn(args, dev):
         predict_meshes = compose_vp_meshes(vp_meshes)
         predict_vertices = gcn(predict_meshes, rgbs, perceptual_features, global_features)
         meter.update(predict_vertices, gt_points, class_indices)
-        if surface is not None:                                          # one face list for the batch: the composed topology
+        if surface is not None and args.outer:
+            # the refined mesh re-meshed without its interior faces; the composed template is wound clockwise seen from outside
+            cx, cy, cz, nodes = vpn_amd.lattice(args.outer_resolution, -0.5, 0.5, dev)
+            distance = vpn_amd.mesh_signed_distance(predict_vertices, predict_meshes[0].faces.flip(1), nodes)
+            union = vpn_amd.isosurface(distance.view(b, cz.numel(), cy.numel(), cx.numel()), (cx, cy, cz))
+            surface.update_surface(union, gt_points, class_indices, n=gt_points.size(1), seed=200 + it,
+                                   gt_normals=torch.nn.functional.normalize(gt_points, dim=-1))
+            if args.dump and it % 3 == 0:
+                union.meshes()[0].save_mesh(os.path.join(args.dump, 'union_%03d.obj' % it))
+        elif surface is not None:                                        # one face list for the batch: the composed topology
             gt_normals = torch.nn.functional.normalize(gt_points, dim=-1)
             surface.update_mesh(predict_vertices, predict_meshes[0].faces, gt_points, class_indices, n=gt_points.size(1),
                                 seed=200 + it, gt_normals=gt_normals)
@@ -139,10 +160,15 @@ def main(argv=None):
                     help='also run SurfaceEvaluationMeter: F-score, Chamfer-L1 / -L2 and (with --gcn) normal consistency')
     ap.add_argument('--thresholds', default=(0.01, 0.02), type=lambda s: tuple(float(t) for t in s.split(',')),
                     help='with --surface: the distance thresholds of the F-score, comma separated (default 0.01,0.02)')
+    ap.add_argument('--outer', action='store_true',
+                    help='with --surface: score points drawn from the outer surface of the union (surface nets, DESIGN.md 4.30)')
+    ap.add_argument('--outer-resolution', type=int, default=64, help='with --outer: the lattice has outer-resolution^3 nodes')
     ap.add_argument('--volume', action='store_true',
                     help='also run VolumeEvaluationMeter: volumetric IoU, precision and recall against stand-in ground-truth meshes')
     ap.add_argument('--resolution', type=int, default=32, help='with --volume: the query grid has resolution^3 cell centres')
     args = ap.parse_args(argv)
+    if args.outer and not args.surface:
+        ap.error('--outer chooses where --surface draws its points: give --surface too')
     if args.dump:
         os.makedirs(args.dump, exist_ok=True)
     torch.manual_seed(1234)

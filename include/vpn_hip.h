@@ -1304,6 +1304,40 @@ size_t vpn_voliou_state_size(int num_classes);
 int vpn_voliou_accumulate(const uint8_t* occ_pred, const uint8_t* occ_gt, const int32_t* class_index, int B, int Q, int num_classes,
                           void* state, float* rows, int32_t* counts, void* stream);
 
+/* ---- outer-surface extraction (csrc/isosurface.hip): the implicit field of a primitive assembly, and surface
+ * nets on a lattice: ONE closed mesh per sample from a field, of a size that depends on the data.  DEVICE pointers.
+ * vpn_primitive_field: one launch.  params, kinds, queries, shared_queries as vpn_occupancy_prims reads them.  f fp32 [B,Q] =
+ *   min_k (m_k - 1) with m_k exactly as vpn_occupancy_prims forms it, so (f <= 0) is its occ bit for bit; a primitive whose
+ *   m_k is a NaN is skipped, +inf when no primitive is left.
+ * vpn_isosurface: four launches (count, scan, vertices, faces).  field fp32 [B,Nz,Ny,Nx], node (iz Ny + iy) Nx + ix; cx [Nx],
+ *   cy [Ny], cz [Nz] fp32 node coordinates, strictly increasing (the caller's word: they are not read on the host).
+ *   s = field - level, NaN -> +FLT_MAX, clamped to +-FLT_MAX; a node is inside iff s <= 0.  Cell (cx,cy,cz) has index (cz (Ny-1)
+ *   + cy) (Nx-1) + cx and is active iff its 8 corners are neither all inside nor all outside.
+ *   verts fp32 [B,max_verts,3]: the vertex of an active cell is the mean of the crossing points of its sign-changing edges, taken
+ *     in the order axis x, y, z and within an axis by the offsets (0,0), (1,0), (0,1), (1,1) along the two other axes in cyclic
+ *     order (x: y z, y: z x, z: x y); on edge a -> b the point is c_a + t (c_b - c_a) with t = s_a / (s_a - s_b) along the axis
+ *     and the node coordinates on the other two; the sum in fp32 in that order, then divided by the count.  A vertex's number is
+ *     the rank of its cell among the sample's active cells in cell-index order.
+ *   faces int32 [B,max_faces,3], MESH-LOCAL: a sign-changing lattice edge with four cells around it gives the quad of their
+ *     vertices, the cells counter-clockwise seen from the edge's positive direction (offsets (-,-), (0,-), (0,0), (-,0) in the
+ *     cyclic plane), as triangles (c0,c1,c2), (c0,c2,c3) when the edge runs from inside to outside and with c1 and c3 swapped
+ *     otherwise: counter-clockwise seen from outside, the convention of vpn_winding_number.  The quad belongs to the cell whose
+ *     minimum corner is the edge's first node; faces are ordered by owner cell, then axis, then the two triangles.
+ *   counts int32 [B,4] = (n_verts, n_faces, n_open, overflow).  n_open: the sign-changing edges in the six boundary faces of the
+ *     lattice, which give no face; 0 means the mesh is closed.  Rows past the counts are written as 0 / (0,0,0): a padding face
+ *     has no area.  n_verts > max_verts or n_faces > max_faces: overflow = 1, the true counts, every row of the sample padding.
+ *   workspace: at least vpn_isosurface_workspace(B, Nx, Ny, Nz) bytes (0: rejected shapes), 16-byte aligned.
+ * Nothing is allocated, no host synchronisation, no atomics, capturable, bit-equal from run to run.  A null pointer, a
+ * non-positive size, a dimension below 2, a level that is not finite, a workspace that is short or misaligned: VPN_E_BADARG.
+ * B > 65535, Q, Nx Ny Nz, max_verts or max_faces above VPN_OCCUPANCY_MAX_ITEMS, K > VPN_MAX_PRIMS: VPN_E_TOOBIG.  All before any
+ * HIP call.  Added without a change of VPN_ABI_VERSION. */
+int vpn_primitive_field(const float* params, const int32_t* kinds, const float* queries, int shared_queries, int B, int K, int Q,
+                        float* f, void* stream);
+size_t vpn_isosurface_workspace(int B, int Nx, int Ny, int Nz);
+int vpn_isosurface(const float* field, const float* cx, const float* cy, const float* cz, float level, int B, int Nx, int Ny, int Nz,
+                   int max_verts, int max_faces, void* workspace, size_t workspace_bytes, float* verts, int32_t* faces,
+                   int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

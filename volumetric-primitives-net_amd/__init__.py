@@ -8,7 +8,8 @@ from .ops import (SPHERE, CUBOID, SampleFunction, TransformFunction, ChamferFunc
                   CameraTransformFunction, RasterFunction,
                   RasterLossFunction, RasterTotalFunction, HotPathLossFunction, TrainStepLossFunction, chamfer_nn, kinds_tensor,
                   emd_recovered_samples, emd_last_group, eval_step, surfeval_step, face_normals_at, ragged_face_normals,
-                  primitive_occupancy, winding_number, ragged_winding_number, mesh_occupancy, grid_queries, voliou_state, voliou_step, vis_primitives, vis_mesh, phong_mesh,
+                  primitive_occupancy, winding_number, ragged_winding_number, mesh_occupancy, grid_queries, voliou_state, voliou_step,
+                  primitive_field, lattice, isosurface, IsoSurface, PaddedMeshArrays, mesh_signed_distance, vis_primitives, vis_mesh, phong_mesh,
                   cluster_points, support_hulls, hull_meshes, hull_augment, union_surface, acd_mix_points,
                   GcnFactoredInputFunction, gcn_factored_input,
                   GcnAggregate2Function, gcn_aggregate2, GcnProjectFunction, gcn_project, gcn_blocks,

@@ -27,17 +27,18 @@
 // Built with -ffp-contract=off: every product and sum below is rounded by itself, as tests/occupancy_ref.py states them; a
 // face whose three corners coincide then has a numerator of exactly 0 whatever the query is.
 #include "vpn_common.h"
+#include "occupancy_prim.h"
 #include <float.h>
 
 namespace {
 
 constexpr int OC_TILE = VPN_OCCUPANCY_TILE;          // queries per workgroup
-constexpr int OC_STAGE = 256;                        // primitives staged in LDS at a time: one per lane
+using vpn::OC_STAGE;                                 // primitives staged in LDS at a time: one per lane (occupancy_prim.h)
+using vpn::OcPrim;
 constexpr int OC_W = VPN_VOLIOU_WIDTH;               // iou precision recall vol_pred vol_gt
 constexpr int OC_CHUNK = 256;                        // samples of a batch the bookkeeping stages in LDS at a time
 constexpr int OC_MAX_ITEMS = VPN_OCCUPANCY_MAX_ITEMS;    // Q, P, F, C
 
-struct OcPrim { float r[9]; float tx, ty, tz, vx, vy, vz; int sphere; };
 struct __attribute__((aligned(16))) OcFace { float ax, ay, az, bx, by, bz, cx, cy, cz; int live, pad0, pad1; };
 static_assert(sizeof(OcFace) == 48, "a face record is 12 words");
 
@@ -64,26 +65,12 @@ __global__ __launch_bounds__(256) void occ_prims_kernel(const float* __restrict_
     for (int base = 0; base < K; base += OC_STAGE) {
         const int m = min(OC_STAGE, K - base);
         __syncthreads();                                 // the previous records have been read
-        if (tid < m) {
-            const float* prm = params + ((size_t)b * K + base + tid) * VPN_PARAM_STRIDE;
-            const vpn::Pose pose = vpn::make_pose(prm[3], prm[4], prm[5], prm[6]);
-            OcPrim& p = s_p[tid];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) p.r[r * 3 + c] = pose.R.m[r][c];
-            }
-            p.vx = prm[0]; p.vy = prm[1]; p.vz = prm[2];
-            p.tx = prm[7]; p.ty = prm[8]; p.tz = prm[9];
-            p.sphere = kinds[base + tid] == VPN_SPHERE;
-        }
+        if (tid < m) vpn::oc_stage_prim(s_p[tid], params, kinds, b, K, base + tid);
         __syncthreads();
         for (int k = 0; k < m; ++k) {
             const OcPrim& p = s_p[k];                    // the same address for every lane: an LDS broadcast
-            const float dx = x.x - p.tx, dy = x.y - p.ty, dz = x.z - p.tz;
-            const float y0 = (p.r[0] * dx + p.r[3] * dy + p.r[6] * dz) / p.vx;       // R^T d: column i of R
-            const float y1 = (p.r[1] * dx + p.r[4] * dy + p.r[7] * dz) / p.vy;
-            const float y2 = (p.r[2] * dx + p.r[5] * dy + p.r[8] * dz) / p.vz;
+            const vpn::F3 y = vpn::oc_local(p, x);
+            const float y0 = y.x, y1 = y.y, y2 = y.z;
             // a NaN fails every comparison: outside
             const bool in = p.sphere ? (y0 * y0 + y1 * y1 + y2 * y2 <= 1.0f)
                                      : (fabsf(y0) <= 1.0f && fabsf(y1) <= 1.0f && fabsf(y2) <= 1.0f);

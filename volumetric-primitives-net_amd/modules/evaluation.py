@@ -217,6 +217,39 @@ class SurfaceEvaluationMeter:
         normals = None if gt_normals is None else ops.face_normals_at(verts.float().contiguous(), f32, fidx)
         return self.update(points, gt_points, class_indices, normals, gt_normals)
 
+    @torch.no_grad()
+    def update_surface(self, surface, gt_points, class_indices, *, n=2048, seed, mesh_base=0, gt_normals=None):
+        """One batch of EXTRACTED surfaces (ops.IsoSurface): one closed mesh per sample whose size the host
+        does not know.  ops.ragged_sample draws n area-weighted points per mesh on the padded layout (Philox(seed; mesh_base
+        + b, point), as update_mesh; a padding face has no area and is never drawn); with gt_normals [B,M,3] the normals of
+        their faces are taken (ops.ragged_face_normals); a sample whose counts say no faces or overflow gets class index -1
+        on the device, so it lands in n_invalid and in no class; then `update`.  No host synchronisation.  Returns the
+        per-sample rows."""
+        if not (hasattr(surface, 'arrays') and hasattr(surface, 'counts')):
+            raise TypeError('surface must be an ops.IsoSurface (ops.isosurface / Meshing.union_meshes)')
+        if not surface.verts.is_cuda:
+            raise RuntimeError('vpn_amd operators run on the GPU only (got a %s tensor); there is no CPU path' % surface.verts.device.type)
+        B = len(surface)
+        arrays = surface.arrays()
+        points, fidx, _ = ops.ragged_sample(*arrays, n, seed=seed, mesh_base=mesh_base, return_faces=True)
+        normals = None
+        if gt_normals is not None:
+            normals = ops.ragged_face_normals(arrays.verts, arrays.faces, arrays.vert_offset, arrays.face_offset, fidx)[:, 0].contiguous()
+        idx = self._class_index(class_indices, B)
+        unusable = (surface.counts[:, 1] == 0) | (surface.counts[:, 3] != 0)
+        return self.update(points[:, 0].contiguous(), gt_points, torch.where(unusable, torch.full_like(idx, -1), idx), normals,
+                           gt_normals)
+
+    @torch.no_grad()
+    def update_primitives(self, params, kinds, gt_points, class_indices, *, resolution=64, bounds=(-0.5, 0.5), n=2048, seed,
+                          mesh_base=0, gt_normals=None, level=0.0, **capacity):
+        """One batch of predicted primitive assemblies, scored on their OUTER surface: Meshing.union_meshes(params, kinds,
+        resolution, bounds, level, **capacity), then update_surface.  Points sampled from the primitives one by one
+        (Sampling.sample_primitives) also lie on the walls inside another primitive; these do not."""
+        from .meshing import Meshing
+        surface = Meshing.union_meshes(params, kinds, resolution=resolution, bounds=bounds, level=level, **capacity)
+        return self.update_surface(surface, gt_points, class_indices, n=n, seed=seed, mesh_base=mesh_base, gt_normals=gt_normals)
+
     def reset(self):
         self.state.zero_()
         self.has_normals = False

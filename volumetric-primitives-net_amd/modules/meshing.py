@@ -251,6 +251,30 @@ class Meshing:
                                    tpl[SPHERE][0] if SPHERE in tpl else None, tpl[CUBOID][0] if CUBOID in tpl else None, ptot)
         return verts, faces
 
+    _lattices = {}           # (resolution, bounds, device) -> (cx, cy, cz, queries) on that device
+
+    @classmethod
+    def union_meshes(cls, params, kinds, resolution=64, bounds=(-0.5, 0.5), level=0.0, **capacity):
+        """The outer surface of every sample's primitive assembly as ONE closed mesh: params (B,K,10), kinds
+        -> ops.IsoSurface.  ops.lattice(resolution, *bounds) -> ops.primitive_field -> ops.isosurface(level, **capacity:
+        max_verts, max_faces); resolution and the two bounds are each one number or one per axis (x, y, z).  Unlike mesh_primitives + compose_meshes, no face lies inside another primitive.  The lattice
+        is uploaded once per (resolution, bounds, device); five launches, no host synchronisation, no autograd node."""
+        from .. import ops
+        if not (isinstance(params, torch.Tensor) and params.dim() == 3):
+            raise ValueError('params [B,K,10] expected')
+        if not isinstance(bounds, (tuple, list)) or len(bounds) != 2:
+            raise ValueError('bounds must be (lo, hi), each one number or three (x, y, z), got %r' % (bounds,))
+        # resolution, lo and hi: one number or one per axis, as ops.lattice takes them (it raises ValueError for anything else)
+        freeze = lambda x: tuple(x) if isinstance(x, (tuple, list)) else x
+        key = (freeze(resolution), freeze(bounds[0]), freeze(bounds[1]), str(params.device))
+        if key not in cls._lattices:
+            if len(cls._lattices) > 16:
+                cls._lattices.clear()
+            cls._lattices[key] = ops.lattice(resolution, bounds[0], bounds[1], params.device)
+        cx, cy, cz, queries = cls._lattices[key]
+        field = ops.primitive_field(params.detach().float(), kinds, queries)
+        return ops.isosurface(field.view(params.shape[0], cz.numel(), cy.numel(), cx.numel()), (cx, cy, cz), level, **capacity)
+
     @classmethod
     def _one_kind(cls, v, q, t, kind):
         cls.check_parameters(v, q, t)

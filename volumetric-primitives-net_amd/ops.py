@@ -4,6 +4,7 @@ Pattern follows the reference's own native op, emdFunction (modules/loss/emd/
 emd_module.py:29-70): forward allocates the outputs, calls native code, saves what
 backward needs; backward returns one gradient per tensor input and None for the rest.
 Unlike it, a non-zero return code raises."""
+import collections
 import ctypes
 import math
 import os
@@ -2453,6 +2454,26 @@ def _gpu_only(t):
         raise RuntimeError('vpn_amd operators run on the GPU only (got a %s tensor); there is no CPU path' % t.device.type)
 
 
+def _prims_check(name, params, kinds, queries):
+    """The inputs of a call that asks a primitive assembly about query points: ValueError from shapes and dtypes alone, then
+    the GPU -> (B, K, Q, contiguous queries, shared flag, kinds on the device)."""
+    if (not isinstance(params, torch.Tensor) or params.dim() != 3 or params.shape[2] != PARAM_STRIDE or min(params.shape) < 1
+            or params.dtype != torch.float32):
+        raise ValueError('%s: params must be float32 [B,K,%d], got %s %r'
+                         % (name, PARAM_STRIDE, getattr(params, 'dtype', None), tuple(getattr(params, 'shape', ()))))
+    B, K = int(params.shape[0]), int(params.shape[1])
+    if K > _H['VPN_MAX_PRIMS']:
+        raise ValueError('%s: at most %d primitives, got %d' % (name, _H['VPN_MAX_PRIMS'], K))
+    n_kinds = kinds.numel() if isinstance(kinds, torch.Tensor) else len(kinds)
+    if n_kinds != K:
+        raise ValueError('%s: %d kinds for %d primitives' % (name, n_kinds, K))
+    if not isinstance(kinds, torch.Tensor):
+        _check_kinds(tuple(int(k) for k in kinds))
+    q, shared, Q = _queries_check(name, queries, B, params.device)
+    _gpu_only(params)
+    return B, K, Q, q, shared, kinds_tensor(kinds, params.device)
+
+
 @torch.no_grad()
 def primitive_occupancy(params, kinds, queries, owner=False):
     """Occupancy of the union of K primitives at query points (vpn_occupancy_prims, one launch): params [B,K,10] fp32 (v, q, t
@@ -2460,22 +2481,8 @@ def primitive_occupancy(params, kinds, queries, owner=False):
     occ uint8 [B,Q] (1 inside); owner=True: (occ, owner int32 [B,Q]), the lowest primitive that holds the point, -1 for
     none.  A point is inside primitive k iff m <= 1 with x~ = R^T (x - t) / v and m = x~.x~ (sphere) or max |x~_i| (cuboid);
     a NaN is outside.  No host synchronisation; everything is validated before the launch."""
-    if (not isinstance(params, torch.Tensor) or params.dim() != 3 or params.shape[2] != PARAM_STRIDE or min(params.shape) < 1
-            or params.dtype != torch.float32):
-        raise ValueError('primitive_occupancy: params must be float32 [B,K,%d], got %s %r'
-                         % (PARAM_STRIDE, getattr(params, 'dtype', None), tuple(getattr(params, 'shape', ()))))
-    B, K = int(params.shape[0]), int(params.shape[1])
-    if K > _H['VPN_MAX_PRIMS']:
-        raise ValueError('primitive_occupancy: at most %d primitives, got %d' % (_H['VPN_MAX_PRIMS'], K))
-    n_kinds = kinds.numel() if isinstance(kinds, torch.Tensor) else len(kinds)
-    if n_kinds != K:
-        raise ValueError('primitive_occupancy: %d kinds for %d primitives' % (n_kinds, K))
-    if not isinstance(kinds, torch.Tensor):
-        _check_kinds(tuple(int(k) for k in kinds))
-    q, shared, Q = _queries_check('primitive_occupancy', queries, B, params.device)
-    _gpu_only(params)
+    B, K, Q, q, shared, kt = _prims_check('primitive_occupancy', params, kinds, queries)
     dev = params.device
-    kt = kinds_tensor(kinds, dev)
     occ = torch.empty((B, Q), dtype=torch.uint8, device=dev)
     own = torch.empty((B, Q), dtype=torch.int32, device=dev) if owner else None
     _lib.call('vpn_occupancy_prims', params.detach().contiguous(), kt, q, shared, B, K, Q, occ, own, _lib.stream())
@@ -2641,6 +2648,196 @@ def voliou_step(occ_pred, occ_gt, class_index, state, C):
     _lib.call('vpn_voliou_accumulate', occ_pred.contiguous(), occ_gt.contiguous(), class_index.reshape(-1).contiguous(), B, Q, int(C),
               state, rows, counts, _lib.stream())
     return rows, counts
+
+
+# ---- outer-surface extraction (csrc/isosurface.hip): the implicit field of a primitive assembly, surface nets
+# on a lattice, and the padded mesh batch the ragged operators take.  Plain functions: nothing is differentiable.
+
+@torch.no_grad()
+def primitive_field(params, kinds, queries):
+    """The implicit field of the union of K primitives at query points (vpn_primitive_field, one launch): params, kinds and
+    queries as primitive_occupancy takes them -> f fp32 [B,Q] = min_k (m_k - 1), negative inside, with m_k as
+    primitive_occupancy forms it: (f <= 0) equals its result bit for bit.  A primitive whose m_k is a NaN is skipped; +inf
+    where no primitive is left.  No host synchronisation; everything is validated before the launch."""
+    B, K, Q, q, shared, kt = _prims_check('primitive_field', params, kinds, queries)
+    f = torch.empty((B, Q), dtype=torch.float32, device=params.device)
+    _lib.call('vpn_primitive_field', params.detach().contiguous(), kt, q, shared, B, K, Q, f, _lib.stream())
+    return f
+
+
+def _triple(name, value, cast):
+    try:
+        out = tuple(cast(x) for x in value) if isinstance(value, (tuple, list)) else (cast(value),) * 3
+    except (TypeError, ValueError):
+        out = ()
+    if len(out) != 3:
+        raise ValueError('lattice: %s must be one number or three (x, y, z), got %r' % (name, value))
+    return out
+
+
+def lattice(dims, lo=-0.5, hi=0.5, device=None):
+    """The lattice of an extraction: dims = N or (Nx, Ny, Nz) nodes at the cell centres of the box [lo, hi] (numbers, or one
+    per axis) -> (cx [Nx], cy [Ny], cz [Nz], queries [Nz Ny Nx, 3]) fp32, node (iz Ny + iy) Nx + ix, coordinate lo + (i + 0.5)
+    (hi - lo) / N formed in float64 and rounded once: lattice(R, lo, hi) holds grid_queries(R, lo, hi) bit for bit.
+    device None: host tensors."""
+    dims, lo, hi = _triple('dims', dims, int), _triple('lo', lo, float), _triple('hi', hi, float)
+    if min(dims) < 2 or dims[0] * dims[1] * dims[2] > OCCUPANCY_MAX_ITEMS:
+        raise ValueError('lattice: every dimension must be at least 2 and their product at most %d, got %r' % (OCCUPANCY_MAX_ITEMS, dims))
+    if not all(math.isfinite(a) and math.isfinite(b) and a < b for a, b in zip(lo, hi)):
+        raise ValueError('lattice: bounds must be finite with lo < hi, got (%r, %r)' % (lo, hi))
+    c = [lo[a] + (torch.arange(dims[a], dtype=torch.float64) + 0.5) * (hi[a] - lo[a]) / dims[a] for a in range(3)]
+    z, y, x = torch.meshgrid(c[2], c[1], c[0], indexing='ij')
+    out = [t.float().contiguous() for t in c] + [torch.stack([x, y, z], -1).reshape(-1, 3).float().contiguous()]
+    if device is None or torch.device(device).type != 'cuda':
+        return tuple(out)
+    return tuple(t.pin_memory().to(device, non_blocking=True) for t in out)
+
+
+_PADDED_TABLES = {}
+
+
+def _padded_tables(B, max_verts, max_faces, device):
+    """The offset and chunk tables of B meshes of max_verts vertices and max_faces faces each: known on the host from the
+    capacities alone, uploaded once per (shape, device)."""
+    key = (B, max_verts, max_faces, str(torch.device(device)))
+    hit = _PADDED_TABLES.get(key)
+    if hit is None:
+        chunk = _H['VPN_RAGGED_CHUNK']
+        rows, chunk_offset = [], [0]
+        for b in range(B):
+            rows += [(b, b * max_faces + start, min(chunk, max_faces - start)) for start in range(0, max_faces, chunk)]
+            chunk_offset.append(len(rows))
+        host = [torch.arange(B + 1, dtype=torch.int64) * max_verts, torch.arange(B + 1, dtype=torch.int64) * max_faces,
+                torch.tensor(chunk_offset), torch.tensor(rows)]
+        host = [t.to(torch.int32).contiguous() for t in host]
+        if torch.device(device).type == 'cuda':
+            host = [t.pin_memory().to(device, non_blocking=True) for t in host]
+        if len(_PADDED_TABLES) > 64:
+            _PADDED_TABLES.clear()
+        hit = _PADDED_TABLES[key] = tuple(host)
+    return hit
+
+
+class PaddedMeshArrays(collections.namedtuple('PaddedMeshArrays', ('verts', 'faces', 'vert_offset', 'face_offset', 'chunk_offset',
+                                                                   'chunks'))):
+    """The six arrays of a MeshBatch for B meshes of one capacity each (IsoSurface.arrays): ragged_sample(*arrays, n) and
+    ragged_winding_number(arrays, queries) take it as it is; the counts are the capacities, which the host knows."""
+    __slots__ = ()
+
+    @property
+    def num_meshes(self):
+        return self.vert_offset.numel() - 1
+
+    @property
+    def vert_counts(self):
+        return [self.verts.shape[0] // self.num_meshes] * self.num_meshes
+
+    @property
+    def face_counts(self):
+        return [self.faces.shape[0] // self.num_meshes] * self.num_meshes
+
+
+class IsoSurface:
+    """What isosurface returns: verts fp32 [B,max_verts,3], faces int32 [B,max_faces,3] (mesh-local, wound counter-clockwise
+    seen from outside), counts int32 [B,4] = (n_verts, n_faces, n_open, overflow) on the device, dims = (Nx, Ny, Nz).  Rows
+    past the counts are padding: vertices (0,0,0) and faces (0,0,0), which have no area, so the ragged sampler never draws
+    them and they add nothing to a winding number.  A sample that overflowed its capacity is all padding."""
+
+    def __init__(self, verts, faces, counts, dims):
+        self.verts, self.faces, self.counts, self.dims = verts, faces, counts, tuple(dims)
+
+    def __len__(self):
+        return self.verts.shape[0]
+
+    def arrays(self):
+        """The padded layout as the six arrays of a MeshBatch (PaddedMeshArrays): mesh b owns max_verts vertices and max_faces
+        faces.  The tables follow from the capacities and are cached per shape: no read-back, so the ragged operators take
+        the result inside a captured graph (after one call outside it has filled the cache)."""
+        B, max_verts, max_faces = self.verts.shape[0], self.verts.shape[1], self.faces.shape[1]
+        return PaddedMeshArrays(self.verts.reshape(-1, 3), self.faces.reshape(-1, 3),
+                                *_padded_tables(B, max_verts, max_faces, self.verts.device))
+
+    def host_counts(self):
+        """counts as a list of B rows: the ONE device-to-host copy."""
+        return self.counts.cpu().tolist()
+
+    def to_mesh_batch(self, device=None):
+        """The trimmed meshes as a MeshBatch (one device-to-host copy of counts, then of the rows that count).  A sample
+        without faces (empty, or overflowed) cannot be packed: ValueError names it."""
+        from .modules.dataset import MeshBatch
+        return MeshBatch.pack([(m.vertices, m.faces) for m in self.meshes()], self.verts.device if device is None else device)
+
+    def meshes(self):
+        """The trimmed meshes as a list of B TriangleMesh on the host (faces int64), for save_mesh: one device-to-host copy of
+        counts, then of the arrays.  An empty or overflowed sample gives a mesh without vertices and faces."""
+        from .modules.meshing import TriangleMesh
+        counts, verts, faces = self.host_counts(), self.verts.cpu(), self.faces.cpu()
+        out = []
+        for b, (nv, nf, _open, overflow) in enumerate(counts):
+            nv, nf = (0, 0) if overflow else (nv, nf)
+            out.append(TriangleMesh(verts[b, :nv].clone(), faces[b, :nf].long()))
+        return out
+
+
+@torch.no_grad()
+def isosurface(field, coords, level=0.0, max_verts=None, max_faces=None):
+    """Surface nets of a field on a lattice (vpn_isosurface, four launches): field fp32 [B,Nz,Ny,Nx] on the device, coords =
+    (cx [Nx], cy [Ny], cz [Nz]) fp32 on the device, strictly increasing (ops.lattice) -> IsoSurface: ONE mesh per sample, the
+    boundary of {field <= level}, closed when the set stays inside the lattice (counts[:, 2] = 0), faces wound
+    counter-clockwise seen from outside.  Capacities default to 8 N^2 vertices and 16 N^2 faces per sample with N the
+    largest dimension; a sample that needs more is flagged (counts[:, 3]) and left empty.  Include/vpn_hip.h has the
+    definition.  No host synchronisation; everything is validated before the first launch."""
+    if not isinstance(field, torch.Tensor) or field.dim() != 4 or field.dtype != torch.float32 or min(field.shape) < 1:
+        raise ValueError('isosurface: field must be float32 [B,Nz,Ny,Nx], got %s %r'
+                         % (getattr(field, 'dtype', None), tuple(getattr(field, 'shape', ()))))
+    B, Nz, Ny, Nx = (int(x) for x in field.shape)
+    if min(Nx, Ny, Nz) < 2:
+        raise ValueError('isosurface: every lattice dimension must be at least 2, got (Nx, Ny, Nz) = %r' % ((Nx, Ny, Nz),))
+    if B > 65535 or Nx * Ny * Nz > OCCUPANCY_MAX_ITEMS:
+        raise ValueError('isosurface: at most 65535 samples of %d nodes, got B = %d, %d nodes' % (OCCUPANCY_MAX_ITEMS, B, Nx * Ny * Nz))
+    try:
+        cx, cy, cz = coords
+    except (TypeError, ValueError):
+        raise ValueError('isosurface: coords must be (cx, cy, cz)')
+    for what, t, n in (('cx', cx, Nx), ('cy', cy, Ny), ('cz', cz, Nz)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (n,):
+            raise ValueError('isosurface: %s must be float32 [%d], got %s %r'
+                             % (what, n, getattr(t, 'dtype', None), tuple(getattr(t, 'shape', ()))))
+        if t.device != field.device:
+            raise ValueError('isosurface: %s must be on %s, got %s' % (what, field.device, t.device))
+    level = float(level)
+    if not math.isfinite(level):
+        raise ValueError('isosurface: the level must be finite, got %r' % level)
+    N = max(Nx, Ny, Nz)
+    max_verts = 8 * N * N if max_verts is None else int(max_verts)
+    max_faces = 16 * N * N if max_faces is None else int(max_faces)
+    if not (1 <= max_verts <= OCCUPANCY_MAX_ITEMS and 1 <= max_faces <= OCCUPANCY_MAX_ITEMS):
+        raise ValueError('isosurface: capacities must be 1 .. %d, got max_verts = %d, max_faces = %d'
+                         % (OCCUPANCY_MAX_ITEMS, max_verts, max_faces))
+    _gpu_only(field)
+    dev = field.device
+    ws = _workspace('vpn_isosurface_workspace', B, Nx, Ny, Nz, dev=dev, dtype=torch.float64)
+    verts = torch.empty((B, max_verts, 3), dtype=torch.float32, device=dev)
+    faces = torch.empty((B, max_faces, 3), dtype=torch.int32, device=dev)
+    counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    _lib.call('vpn_isosurface', field.detach().contiguous(), cx.contiguous(), cy.contiguous(), cz.contiguous(), level, B, Nx, Ny, Nz,
+              max_verts, max_faces, ws, ws.numel() * 8, verts, faces, counts, _lib.stream())
+    return IsoSurface(verts, faces, counts, (Nx, Ny, Nz))
+
+
+@torch.no_grad()
+def mesh_signed_distance(verts, faces, queries):
+    """The signed distance to triangle meshes at query points: verts [B,P,3] fp32 over ONE faces [F,3], queries fp32 [Q,3]
+    (shared) or [B,Q,3] -> fp32 [B,Q]: the distance to the nearest triangle (the square root of point_mesh_nearest's dist_p),
+    negative where mesh_occupancy says inside (winding number above 0.5, so overlapping closed components count as one
+    solid).  The field whose zero level re-meshes a refined mesh without its interior faces.  The two operators do the work;
+    they are combined by four small elementwise torch launches (root, compare, negate, select), not by a kernel of this
+    library, and a shared query set is copied B times first because point_mesh_nearest reads [B,Q,3]."""
+    occ = mesh_occupancy(verts, faces, queries)
+    B = verts.shape[0]
+    points = queries if queries.dim() == 3 else queries[None].expand(B, -1, -1)
+    dist = point_mesh_nearest(points.contiguous(), verts, faces)[0].sqrt()
+    return torch.where(occ != 0, -dist, dist)
 
 
 # ---- the visualisation stage (csrc/visualize.hip; modules/visualize/render.py:13-24).  Plain functions: a picture has no
