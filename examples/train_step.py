@@ -1,6 +1,6 @@
 """A training step of the reference (train.py:221-268) on the drop-in surface, with a stand-in network.
 
-    python examples/train_step.py [--steps 20] [--net standin|vpnet_oneres|vpnet_twores] [--optimizer torch|hip] [--trunk-norm torch|hip|hip+pool] [--trunk-conv torch|hip|all] [--trunk-tail torch|hip]
+    python examples/train_step.py [--steps 20] [--net standin|vpnet_oneres|vpnet_twores] [--optimizer torch|hip] [--trunk-norm torch|hip|hip+pool] [--trunk-conv torch|hip|all] [--trunk-tail torch|hip] [--occupancy-loss W_OCC,W_OV[,TAU]]
 
 By default a two-layer MLP on a random feature vector produces the three head outputs (volumes [B,3K], rotates [B,4K],
 translates [B,3K]); --net vpnet_oneres / vpnet_twores trains the reference's network instead (modules/network.py: a
@@ -15,6 +15,11 @@ code path of the reference, through vpn_amd's mirror of its modules:
     silhouette loss          train.py:176                SilhouetteLoss
     VP diversity loss        train.py:185                VPDiverseLoss
     EMD loss                 train.py:193                EarthMoverDistanceLoss
+
+--occupancy-loss W_OCC,W_OV[,TAU] (off by default; not in the reference; the non-fused path only) adds
+vpn_amd.OccupancyLoss(W_OCC, W_OV, TAU): the cross-entropy of the soft union of the predicted primitives against the
+occupancy of the target assembly, and the overlap penalty, at the cell centres of a 16^3 grid plus the ground-truth points
+jittered by a fixed-seed normal.
 """
 import argparse
 import os
@@ -48,8 +53,9 @@ def head_params(net, feats, gt_sil):
     return out[0] if isinstance(out, tuple) else out
 
 
-def training_losses(net, feats, gt_points, gt_sil, dists, elevs, azims, angles, kinds, sample_num, weights, seed):
-    """total loss of train.py:243-262 (w = (L_VIEW_CD, L_CAN_CD, L_SIL, L_VP_DIV, L_EMD)) and its parts."""
+def training_losses(net, feats, gt_points, gt_sil, dists, elevs, azims, angles, kinds, sample_num, weights, seed, occupancy=None):
+    """total loss of train.py:243-262 (w = (L_VIEW_CD, L_CAN_CD, L_SIL, L_VP_DIV, L_EMD)) and its parts.  occupancy: None, or
+    (vpn_amd.OccupancyLoss, queries, labels), whose weighted sum is added as the part 'occ'."""
     K = len(kinds)
     params = head_params(net, feats, gt_sil)                                      # [B,K,10]
     volumes, rotates, translates = vpn_amd.split_primitives(params)
@@ -64,7 +70,12 @@ def training_losses(net, feats, gt_points, gt_sil, dists, elevs, azims, angles, 
     emd = torch.sqrt(dist).mean()
     w = weights
     total = w[0] * view_cd + w[1] * obj_cd + w[2] * sil + w[3] * div + w[4] * emd
-    return total, {'view_cd': view_cd, 'obj_cd': obj_cd, 'sil': sil, 'vp_div': div, 'emd': emd}
+    parts = {'view_cd': view_cd, 'obj_cd': obj_cd, 'sil': sil, 'vp_div': div, 'emd': emd}
+    if occupancy is not None:
+        occ_loss, queries, labels = occupancy
+        parts['occ'] = occ_loss(params, kinds, queries, labels)
+        total = total + parts['occ']
+    return total, parts
 
 
 def training_losses_fused(net, feats, gt_points, gt_sil, dists, elevs, azims, angles, kinds, sample_num, weights, seed):
@@ -78,13 +89,19 @@ def training_losses_fused(net, feats, gt_points, gt_sil, dists, elevs, azims, an
     return total, {'view_cd': view_cd, 'obj_cd': obj_cd, 'sil': sil, 'vp_div': div, 'emd': emd}   # the WEIGHTED terms
 
 
-def make_batch(B, K, sample_num, size, dev, seed=0):
+def draw_inputs(B, K, seed=0):
+    """The random inputs of a batch, on the host: (feats [B,64], target [B,K,10]), the target K random ellipsoids.  The one place
+    these draws are made: make_batch and target_assembly both come here."""
     g = torch.Generator().manual_seed(seed)
-    M = K * sample_num
-    feats = torch.randn(B, 64, generator=g).to(dev)
-    # a target made of K random ellipsoids: its surface points and its silhouette
+    feats = torch.randn(B, 64, generator=g)
     v = (torch.rand(B, K, 3, generator=g) + 0.1) / torch.tensor([8.0, 10.0, 10.0])
-    target = torch.cat([v, torch.rand(B, K, 4, generator=g), 0.3 * (torch.rand(B, K, 3, generator=g) * 2 - 1)], 2).to(dev)
+    target = torch.cat([v, torch.rand(B, K, 4, generator=g), 0.3 * (torch.rand(B, K, 3, generator=g) * 2 - 1)], 2)
+    return feats, target
+
+
+def make_batch(B, K, sample_num, size, dev, seed=0):
+    # a target made of K random ellipsoids: its surface points and its silhouette
+    feats, target = (t.to(dev) for t in draw_inputs(B, K, seed))
     kinds = [vpn_amd.SPHERE] * K
     with torch.no_grad():
         gt_points = vpn_amd.Sampling.sample_primitives(target, kinds, sample_num, seed=99)
@@ -95,6 +112,21 @@ def make_batch(B, K, sample_num, size, dev, seed=0):
                                                     image_size=(size, size))
         gt_sil = (alpha.reshape(B, 1, size, size) > 0.5).float()
     return feats, gt_points, gt_sil, dists, elevs, azims, torch.zeros(B, device=dev), kinds
+
+
+def target_assembly(B, K, dev, seed=0):
+    """The target of make_batch(B, K, ..., seed): params [B,K,10] of its K random ellipsoids."""
+    return draw_inputs(B, K, seed)[1].to(dev)
+
+
+def occupancy_queries(gt_points, target, kinds, jitter=0.02, seed=77):
+    """(queries [B, 16^3 + M, 3], labels uint8 [B, 16^3 + M]): the cell centres of a 16^3 grid over the unit cube and the
+    ground-truth points moved by a fixed-seed normal of scale `jitter`, labelled by the occupancy of the target assembly."""
+    B, dev = gt_points.shape[0], gt_points.device
+    noise = torch.randn(gt_points.shape, generator=torch.Generator().manual_seed(seed)).to(dev)
+    grid = vpn_amd.grid_queries(16, device=dev)
+    queries = torch.cat([grid[None].expand(B, -1, -1), gt_points + jitter * noise], 1).contiguous()
+    return queries, vpn_amd.primitive_occupancy(target, kinds, queries)
 
 
 def augment_batch(batch, which, it):
@@ -151,9 +183,21 @@ def main():
     ap.add_argument('--trunk-conv', default='torch', choices=('torch', 'hip', 'all'),
                     help='hip: the 13 stride-1 3x3 convolutions of the ResNet-18 trunk run on the f32-input MFMA (csrc/trunkconv.hip); '
                          'all: the seven stride-2 ones as well (csrc/trunkstride.hip): no library convolution is left in the trunk')
+    ap.add_argument('--occupancy-loss', default=None, metavar='W_OCC,W_OV[,TAU]',
+                    help='add vpn_amd.OccupancyLoss(W_OCC, W_OV, TAU): the soft union of the predicted primitives against the occupancy '
+                         'of the target assembly, and the overlap penalty (not in the reference; the non-fused path, no augmentation)')
     args = ap.parse_args()
     augment = [a for a in args.augment.split(',') if a]
     assert set(augment) <= {'rotate', 'cutmix', 'mixup', 'pointmixup', 'acdmix'}, augment
+    occ_args = None
+    if args.occupancy_loss is not None:
+        try:
+            occ_args = [float(w) for w in args.occupancy_loss.split(',')]
+            assert len(occ_args) in (2, 3)
+        except (ValueError, AssertionError):
+            ap.error('--occupancy-loss takes two or three numbers W_OCC,W_OV[,TAU]')
+        if args.fused or augment:
+            ap.error('--occupancy-loss belongs to the non-fused path without --augment: its labels are those of the target assembly')
     losses = training_losses_fused if args.fused else training_losses
     dev = torch.device('cuda')
     torch.manual_seed(1234)
@@ -170,14 +214,18 @@ def main():
     else:
         opt = torch.optim.Adam(net.parameters(), lr=1e-3)
     weights = (1.0, 1.0, 1.0, 0.1, 1.0)
+    extra, occ_loss = {}, None
+    if occ_args is not None:
+        occ_loss = vpn_amd.OccupancyLoss(*occ_args)
+        extra['occupancy'] = (occ_loss,) + occupancy_queries(batch[1], target_assembly(args.batch, args.prims, dev), batch[7])
     for it in range(args.steps):
         opt.zero_grad()
         total, parts = losses(net, *(augment_batch(batch, augment, it) if augment else batch), args.sample_num, weights,
-                              seed=1000 + it)
+                              seed=1000 + it, **extra)
         total.backward()
         opt.step()
-        print('step %3d  total %.5f  ' % (it, float(total.detach())) + '  '.join('%s %.5f' % (k, float(v.detach())) for k, v in parts.items()),
-              flush=True)
+        print('step %3d  total %.5f  ' % (it, float(total.detach())) + '  '.join('%s %.5f' % (k, float(v.detach())) for k, v in parts.items())
+              + ('' if occ_loss is None else ' (occupancy %.5f, overlap %.5f)' % tuple(occ_loss.last.tolist())), flush=True)
 
 
 if __name__ == '__main__':

@@ -1338,6 +1338,58 @@ int vpn_isosurface(const float* field, const float* cx, const float* cy, const f
                    int max_verts, int max_faces, void* workspace, size_t workspace_bytes, float* verts, int32_t* faces,
                    int32_t* counts, void* stream);
 
+/* ---- occupancy loss (csrc/occloss.hip): the soft union of a primitive assembly against occupancy labels at
+ * query points, with an overlap penalty, differentiable to the parameters.  DEVICE pointers.  params fp32 [B,K,VPN_PARAM_STRIDE],
+ * kinds int32 [K], queries fp32 [Q,3] (shared_queries != 0) or [B,Q,3], read as vpn_primitive_field reads them (a sample stride
+ * of 0: repeating a shared set B times gives the same bits).  labels [B,Q]: uint8 (labels_u8 != 0; non-zero = 1, what
+ * vpn_occupancy_prims and vpn_winding_number write) or fp32 in [0,1] (the range is the caller's word).  tau: finite, > 0.
+ *   per primitive   x~ = R^T (x - t) / v and m_k exactly as vpn_primitive_field forms them; d_k = m_k - 1, z_k = -d_k / tau, each
+ *                   operation in fp32 and rounded by itself.  A primitive whose m_k is not finite (NaN or inf) is left out of
+ *                   everything below, for that query.
+ *   union logit     l = logsumexp_k z_k = zmax + log sum_k exp(z_k - zmax) (formed online, primitive by primitive: the running sum
+ *                   is rescaled by exp(old max - new max) when the maximum grows); -inf when no primitive is left or every z_k is
+ *                   -inf, +inf when a z_k is.  The soft occupancy is sigmoid(l).
+ *   overlap sum     s = sum_k sigmoid(z_k), sigmoid(z) = 1 / (1 + exp(-z)) for z >= 0 and exp(z) / (1 + exp(z)) below.
+ *   per query       bce = softplus(l) - y l with softplus(l) = max(l, 0) + log1p(exp(-|l|));  ov = relu(s - 1)^2.
+ *   out [2]         (sum bce, sum ov) / (B Q).
+ *   skipped         a query with a coordinate that is not finite, a NaN label, or an l that is not finite adds 0 to both sums and
+ *                   to every gradient and 1 to n_skipped; the divisor stays B Q.
+ * vpn_occloss_fwd: two launches (one work-item per (query, sample) with the records of 256 primitives at a time in LDS and one
+ *   row of sums per workgroup -- xor tree over the wave, the four waves (0 + 1) + (2 + 3) --; then ONE workgroup that adds the
+ *   rows in fp64: lane t rows t, t + 256, ... ascending, the lanes by a tree).  lse [B,Q] = l and s [B,Q], both or neither (NULL:
+ *   not written): all the backward needs.  out [2] and n_skipped int32 [1] (may be NULL; saturates at INT_MAX); out NULL: the soft
+ *   occupancy alone, one launch, labels and workspace are not used and n_skipped must be NULL.  lse or out must be given.
+ * vpn_occloss_bwd: two launches.  grad DEVICE fp32 [2], first order:
+ *     c_k = (grad[0] (sigmoid(l) - y) exp(z_k - l) + grad[1] 2 relu(s - 1) sigmoid(z_k) (1 - sigmoid(z_k))) / (B Q)
+ *     (B Q is the exact product in fp64 in both calls: each of the two query factors of c_k is divided by it in fp64 and rounded once)
+ *     dL/dm_k = -c_k / tau;  dm/dx~ = 2 x~ (sphere) or sign(x~_a) e_a with a the LOWEST axis attaining max |x~_i| and sign(0) = 0
+ *     with gamma = dL/dx~ summed over the queries of (b, k):  dL/dt = -R (sum gamma / v),  dL/dv_i = -sum gamma_i x~_i / v_i,
+ *     dL/dR[j][i] = sum gamma_i d_j / v_i with d = x - t = R (v o x~), and dL/dR -> q by the sampler's chain rule (the half-angle
+ *     map of q3 included).  Twelve sums a primitive: sum gamma [3] and sum gamma_i x~_l [3][3].
+ *   One workgroup per (query slice, sample); a lane keeps its slice's queries in registers, accumulates the twelve sums of a
+ *   primitive over them in fp32, the wave adds them by the xor tree and writes a row; then per (b, k) the rows are added in fp64
+ *   in ascending (slice, wave) order, the chain rule is applied in fp64 up to dL/dR and dparams [B,K,VPN_PARAM_STRIDE] is written
+ *   whole.  A primitive with an extent that is 0 or not finite, or a t or a rotation that is not finite, has no finite m_k at any
+ *   query: its row of dparams is 0.  No gradient to queries or labels.  lse and s as the forward wrote them for the same inputs.
+ * vpn_occloss_plan returns the number of query slices (or a negative code) and writes the queries per slice = 256 qpl: qpl is the
+ *   largest of 8, 4, 2, 1 that still gives VPN_OCCLOSS_MIN_GROUPS workgroups (else 1), a function of (B, Q) alone, so a shape
+ *   always adds in the same order.
+ * workspace: at least vpn_occloss_workspace(B, K, Q) bytes (0: rejected shapes), 16-byte aligned; it serves either call.
+ * Nothing is allocated, no host synchronisation, no atomics, capturable, bit-equal from run to run.  A null pointer (but for
+ * those said to be optional), a non-positive size, lse without s, neither lse nor out, n_skipped without out, a tau that is not
+ * finite or not > 0, a workspace that is short or misaligned: VPN_E_BADARG.  B > 65535, Q > VPN_OCCUPANCY_MAX_ITEMS, K >
+ * VPN_MAX_PRIMS: VPN_E_TOOBIG.  All before any HIP call.  Added without a change of VPN_ABI_VERSION. */
+#define VPN_OCCLOSS_MAX_QPL 8            /* queries a lane of the backward keeps in registers, at most */
+#define VPN_OCCLOSS_MIN_GROUPS 256       /* the backward halves its slice until it launches this many workgroups */
+int vpn_occloss_plan(int B, int Q, int* slice_queries);
+size_t vpn_occloss_workspace(int B, int K, int Q);
+int vpn_occloss_fwd(const float* params, const int32_t* kinds, const float* queries, int shared_queries, const void* labels,
+                    int labels_u8, int B, int K, int Q, float tau, void* workspace, size_t workspace_bytes, float* lse, float* s,
+                    float* out, int32_t* n_skipped, void* stream);
+int vpn_occloss_bwd(const float* grad, const float* params, const int32_t* kinds, const float* queries, int shared_queries,
+                    const void* labels, int labels_u8, const float* lse, const float* s, int B, int K, int Q, float tau,
+                    void* workspace, size_t workspace_bytes, float* dparams, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

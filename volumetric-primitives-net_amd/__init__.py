@@ -14,9 +14,10 @@ from .ops import (SPHERE, CUBOID, SampleFunction, TransformFunction, ChamferFunc
                   GcnFactoredInputFunction, gcn_factored_input,
                   GcnAggregate2Function, gcn_aggregate2, GcnProjectFunction, gcn_project, gcn_blocks,
                   MeshRegFunction, mesh_regularizers, mesh_topology,
-                  PointMeshFunction, point_mesh_distance, point_mesh_nearest, mesh_incidence)
+                  PointMeshFunction, point_mesh_distance, point_mesh_nearest, mesh_incidence,
+                  OccupancyLossFunction, primitive_occupancy_loss, primitive_soft_occupancy, occloss_plan)
 from .primitives import PrimitivePack, pack_primitives, kinds_from_counts
-from .modules import (Sampling, ChamferDistanceLoss, EarthMoverDistanceLoss, SilhouetteLoss, VPDiverseLoss, MeshRegularizationLoss, PointMeshDistanceLoss, VertexRenderer, PhongRenderer,
+from .modules import (Sampling, ChamferDistanceLoss, EarthMoverDistanceLoss, SilhouetteLoss, VPDiverseLoss, MeshRegularizationLoss, PointMeshDistanceLoss, OccupancyLoss, VertexRenderer, PhongRenderer,
                       transform_points, rotate_points, translate_points, view_to_obj_points,
                       obj_to_view_points, rotate_points_forward_x_axis, pack_head_outputs, split_primitives, Meshing, TriangleMesh, load_obj, merge_meshes,
                       cut_mix_data, cut_mix_batch_points, adjust_point_num, mixup_points, point_mixup_data,

@@ -13,7 +13,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libvpn_hip.so')
-SOURCES = ['vpn_api.hip', 'sampler.hip', 'chamfer.hip', 'raster.hip', 'emd.hip', 'head.hip', 'mesh.hip', 'trainstep.hip', 'gcn.hip', 'augment.hip', 'evaluate.hip', 'visualize.hip', 'phong.hip', 'reconstruct.hip', 'acdmix.hip', 'input.hip', 'gtpoints.hip', 'fcstack.hip', 'optim.hip', 'trunknorm.hip', 'trunkconv.hip', 'trunkstride.hip', 'gcnpair.hip', 'trunkfold.hip', 'meshreg.hip', 'pointmesh.hip', 'surfeval.hip', 'occupancy.hip', 'isosurface.hip']
+SOURCES = ['vpn_api.hip', 'sampler.hip', 'chamfer.hip', 'raster.hip', 'emd.hip', 'head.hip', 'mesh.hip', 'trainstep.hip', 'gcn.hip', 'augment.hip', 'evaluate.hip', 'visualize.hip', 'phong.hip', 'reconstruct.hip', 'acdmix.hip', 'input.hip', 'gtpoints.hip', 'fcstack.hip', 'optim.hip', 'trunknorm.hip', 'trunkconv.hip', 'trunkstride.hip', 'gcnpair.hip', 'trunkfold.hip', 'meshreg.hip', 'pointmesh.hip', 'surfeval.hip', 'occupancy.hip', 'isosurface.hip', 'occloss.hip']
 COMMON = ['-O3', '--offload-arch=gfx950', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function']
 COMMON += os.environ.get('VPN_EXTRA_FLAGS', '').split()      # experiments only (e.g. -DVPN_CHAMFER_DEBUG)
 RASTER_EXTRA = os.environ.get('VPN_RASTER_FLAGS', '').split()  # experiments only: extra flags for raster.hip alone
@@ -36,6 +36,7 @@ PER_FILE = {
     'surfeval.hip': ['-ffp-contract=off'],                      # normals and fp64 sums as tests/surfeval_ref.py states them: every operation rounded by itself
     'occupancy.hip': ['-ffp-contract=off'],                     # inside tests and solid angles as tests/occupancy_ref.py states them; a face of no area adds exactly 0
     'isosurface.hip': ['-ffp-contract=off'],                    # the field's m_k as occupancy.hip forms it; crossing points and vertex means as tests/isosurface_ref.py states them
+    'occloss.hip': ['-ffp-contract=off'],                       # the loss's m_k is the field's bit for bit; logit, sums and gradient as tests/occloss_ref.py states them
     # the raster is compared with a 1e-4 tolerance: 1-ulp v_rcp/v_sqrt instead of the IEEE sequences
     # -fgpu-flush-denormals-to-zero: no denormal-safe scaling around v_rcp / v_sqrt / v_exp
     # -fno-slp-vectorize: packed fp32 is half rate here and the packing costs v_mov shuffles and 25 VGPRs

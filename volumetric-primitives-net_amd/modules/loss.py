@@ -4,7 +4,7 @@ import torch
 import torch.nn as nn
 
 from .. import config
-from ..ops import ChamferFunction, EmdFunction, RasterTotalFunction, const_tensor, mesh_regularizers, point_mesh_distance
+from ..ops import ChamferFunction, EmdFunction, RasterTotalFunction, const_tensor, mesh_regularizers, point_mesh_distance, primitive_occupancy_loss
 from ..primitives import PrimitivePack
 from .render import VertexRenderer
 
@@ -126,4 +126,26 @@ class PointMeshDistanceLoss(nn.Module):
     def forward(self, points: torch.Tensor, vertices: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
         parts = point_mesh_distance(points, vertices, faces)
         self.last = parts.detach()
+        return (parts * const_tensor(self.weights, torch.float32, parts.device)).sum()
+
+
+class OccupancyLoss(nn.Module):
+    """The volumetric term the point and pixel losses lack (the coverage / consistency pair of Tulsiani et al., the occupancy
+    loss of Paschalidou et al., CvxNet and BSP-Net; not part of the reference): w_occ * (cross-entropy of the soft union of
+    the primitives against occupancy labels at query points) + w_overlap * (mean of relu(sum_k sigmoid(z_k) - 1)^2, a point
+    claimed by more than one primitive) of ops.primitive_occupancy_loss, at temperature tau.  Both parts come out of one
+    scan, so a weight of 0 only drops its part from the sum and from the gradient.  `.last` keeps the two parts of the
+    latest call and `.last_skipped` the number of queries left out (int32 [1]), detached and on the device (reading them is
+    the caller's synchronisation, not this module's)."""
+
+    def __init__(self, w_occ=1.0, w_overlap=0.0, tau=0.05):
+        super().__init__()
+        self.weights = (float(w_occ), float(w_overlap))
+        self.tau = float(tau)
+        self.last = None
+        self.last_skipped = None
+
+    def forward(self, params: torch.Tensor, kinds, queries: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        parts, skipped = primitive_occupancy_loss(params, kinds, queries, labels, self.tau, return_skipped=True)
+        self.last, self.last_skipped = parts.detach(), skipped
         return (parts * const_tensor(self.weights, torch.float32, parts.device)).sum()

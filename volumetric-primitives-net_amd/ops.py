@@ -2454,9 +2454,9 @@ def _gpu_only(t):
         raise RuntimeError('vpn_amd operators run on the GPU only (got a %s tensor); there is no CPU path' % t.device.type)
 
 
-def _prims_check(name, params, kinds, queries):
-    """The inputs of a call that asks a primitive assembly about query points: ValueError from shapes and dtypes alone, then
-    the GPU -> (B, K, Q, contiguous queries, shared flag, kinds on the device)."""
+def _prims_shapes(name, params, kinds, queries):
+    """The inputs of a call that asks a primitive assembly about query points: ValueError from shapes and dtypes alone ->
+    (B, K, Q, contiguous queries, shared flag).  Nothing here needs the GPU."""
     if (not isinstance(params, torch.Tensor) or params.dim() != 3 or params.shape[2] != PARAM_STRIDE or min(params.shape) < 1
             or params.dtype != torch.float32):
         raise ValueError('%s: params must be float32 [B,K,%d], got %s %r'
@@ -2470,6 +2470,12 @@ def _prims_check(name, params, kinds, queries):
     if not isinstance(kinds, torch.Tensor):
         _check_kinds(tuple(int(k) for k in kinds))
     q, shared, Q = _queries_check(name, queries, B, params.device)
+    return B, K, Q, q, shared
+
+
+def _prims_check(name, params, kinds, queries):
+    """_prims_shapes, then the GPU -> (B, K, Q, contiguous queries, shared flag, kinds on the device)."""
+    B, K, Q, q, shared = _prims_shapes(name, params, kinds, queries)
     _gpu_only(params)
     return B, K, Q, q, shared, kinds_tensor(kinds, params.device)
 
@@ -2663,6 +2669,112 @@ def primitive_field(params, kinds, queries):
     f = torch.empty((B, Q), dtype=torch.float32, device=params.device)
     _lib.call('vpn_primitive_field', params.detach().contiguous(), kt, q, shared, B, K, Q, f, _lib.stream())
     return f
+
+
+# ---- the occupancy loss (csrc/occloss.hip): the soft union of the primitives against occupancy labels and
+# an overlap penalty, differentiable to the parameters
+
+def occloss_plan(B, Q):
+    """(slices, queries per slice) of the occupancy loss's backward for B samples of Q queries (vpn_occloss_plan): a function
+    of the two numbers alone."""
+    slice_queries = ctypes.c_int(0)
+    slices = _lib.lib().vpn_occloss_plan(int(B), int(Q), ctypes.byref(slice_queries))
+    if slices < 0:
+        raise ValueError('occloss_plan: rejected shape B = %d, Q = %d' % (B, Q))
+    return slices, slice_queries.value
+
+
+def _occloss_check(name, params, kinds, queries, labels, tau, need_labels):
+    """The contract of primitive_occupancy_loss / primitive_soft_occupancy, from shapes, dtypes and devices alone: ValueError
+    before any launch -> (B, K, Q, contiguous queries, shared flag, kinds on the device, contiguous labels or None, tau)."""
+    tau = float(tau)
+    if not (math.isfinite(tau) and tau > 0.0):
+        raise ValueError('%s: tau must be finite and > 0, got %r' % (name, tau))
+    B, K, Q, q, shared = _prims_shapes(name, params, kinds, queries)
+    if need_labels:
+        if (not isinstance(labels, torch.Tensor) or tuple(labels.shape) != (B, Q) or labels.dtype not in (torch.uint8, torch.float32)):
+            raise ValueError('%s: labels must be uint8 or float32 [%d,%d], got %s %r'
+                             % (name, B, Q, getattr(labels, 'dtype', None), tuple(getattr(labels, 'shape', ()))))
+        if labels.device != params.device:
+            raise ValueError('%s: labels must be on %s, got %s' % (name, params.device, labels.device))
+        labels = labels.detach().contiguous()
+    if not params.is_cuda:
+        raise ValueError('%s: vpn_amd operators run on the GPU only (got %s tensors); there is no CPU path' % (name, params.device.type))
+    return B, K, Q, q, shared, kinds_tensor(kinds, params.device), labels, tau
+
+
+class OccupancyLossFunction(Function):
+    """(out [2], n_skipped int32 [1]) of vpn_occloss_fwd: out = (mean soft-union cross-entropy, mean overlap penalty) of params
+    [B,K,10] with kinds [K] at queries [Q,3] (shared != 0) or [B,Q,3] against labels uint8 or fp32 [B,Q] (see include/vpn_hip.h
+    for the definitions): two launches forward, two backward, no atomics, bit-equal from run to run.  The gradient goes to
+    params alone and is first order (once_differentiable); the upstream gradient [2] stays on the device.  Only the logit and
+    the overlap sum per query are saved, and only when params needs a gradient; otherwise they are not written."""
+
+    @staticmethod
+    def forward(ctx, params, kt, q, shared, labels, tau):
+        if (params.dim() != 3 or params.shape[2] != PARAM_STRIDE or params.dtype != torch.float32 or kt.numel() != params.shape[1]
+                or tuple(labels.shape) != (params.shape[0], q.shape[-2]) or labels.dtype not in (torch.uint8, torch.float32)):
+            raise ValueError('OccupancyLossFunction: params must be float32 [B,K,%d] with K kinds and labels uint8 or float32 [B,Q], '
+                             'got %r, %d kinds, %s %r' % (PARAM_STRIDE, tuple(params.shape), kt.numel(), labels.dtype, tuple(labels.shape)))
+        params, q, labels = _f32c(params), _f32c(q), labels.contiguous()
+        B, K, Q, dev = int(params.shape[0]), int(params.shape[1]), int(q.shape[-2]), params.device
+        need = ctx.needs_input_grad[0]
+        lse = torch.empty((B, Q), dtype=torch.float32, device=dev) if need else None
+        s = torch.empty((B, Q), dtype=torch.float32, device=dev) if need else None
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        n_skipped = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = _workspace('vpn_occloss_workspace', B, K, Q, dev=dev)
+        _lib.call('vpn_occloss_fwd', params, kt, q, int(shared), labels, int(labels.dtype == torch.uint8), B, K, Q, float(tau), ws,
+                  ws.numel() * 4, lse, s, out, n_skipped, _lib.stream())
+        if need:
+            ctx.save_for_backward(params, kt, q, labels, lse, s)
+            ctx.shared, ctx.tau = int(shared), float(tau)
+        ctx.mark_non_differentiable(n_skipped)
+        return out, n_skipped
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_skipped):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None
+        params, kt, q, labels, lse, s = ctx.saved_tensors
+        B, K, Q = int(params.shape[0]), int(params.shape[1]), int(q.shape[-2])
+        dparams = torch.empty_like(params)
+        ws = _workspace('vpn_occloss_workspace', B, K, Q, dev=params.device)
+        _lib.call('vpn_occloss_bwd', _f32c(g), params, kt, q, ctx.shared, labels, int(labels.dtype == torch.uint8), lse, s, B, K, Q,
+                  ctx.tau, ws, ws.numel() * 4, dparams, _lib.stream())
+        return dparams, None, None, None, None, None
+
+
+def primitive_occupancy_loss(params, kinds, queries, labels, tau=0.05, return_skipped=False):
+    """[2] = (occupancy term, overlap term) of the union of K primitives against occupancy labels (OccupancyLossFunction):
+    params [B,K,10] fp32, kinds [K] (a list or a device tensor), queries fp32 [Q,3] shared by the batch or [B,Q,3], labels
+    uint8 [B,Q] (what primitive_occupancy and mesh_occupancy return) or fp32 [B,Q] in [0,1].
+
+        occupancy term  mean over (b, i) of softplus(l) - y l, the cross-entropy of sigmoid(l) against the label, with
+                        l = logsumexp_k z_k the logit of the soft union and z_k = (1 - m_k) / tau, m_k as primitive_field forms it
+        overlap term    mean over (b, i) of relu(sum_k sigmoid(z_k) - 1)^2: a point claimed by more than one primitive
+
+    A query with a coordinate that is not finite, a NaN label or no finite logit adds nothing to either term or to the gradient
+    and is counted; the divisor stays B Q.  Weight the two in torch.  Differentiable to params.  return_skipped=True: (the [2],
+    the count int32 [1] on the device).  Anything outside the contract raises ValueError before any launch; host tensors have
+    no path."""
+    B, K, Q, q, shared, kt, labels, tau = _occloss_check('primitive_occupancy_loss', params, kinds, queries, labels, tau, True)
+    out, n_skipped = OccupancyLossFunction.apply(params, kt, q, shared, labels, tau)
+    return (out, n_skipped) if return_skipped else out
+
+
+@torch.no_grad()
+def primitive_soft_occupancy(params, kinds, queries, tau):
+    """(logit [B,Q], overlap_sum [B,Q]) of the soft union: l = logsumexp_k z_k and s = sum_k sigmoid(z_k) per query (the
+    forward of primitive_occupancy_loss without labels, one launch); sigmoid(logit) is the soft occupancy.  -inf where no
+    primitive has a finite m_k.  No autograd node: for tests and debugging."""
+    B, K, Q, q, shared, kt, _, tau = _occloss_check('primitive_soft_occupancy', params, kinds, queries, None, tau, False)
+    lse = torch.empty((B, Q), dtype=torch.float32, device=params.device)
+    s = torch.empty((B, Q), dtype=torch.float32, device=params.device)
+    _lib.call('vpn_occloss_fwd', params.detach().contiguous(), kt, q, shared, None, 0, B, K, Q, tau, None, 0, lse, s, None, None,
+              _lib.stream())
+    return lse, s
 
 
 def _triple(name, value, cast):
